@@ -12,6 +12,14 @@ inference + fused env kernel with experience append), critic over the rollout, G
 Learn (2 epochs of shuffled 50k minibatches, fp32 forward/backward, RCCL gradient all-reduce
 for N > 1, clip_grad_norm_, AdamW).  value = env-steps/s summed over ranks (weak scaling:
 4096 arenas per GPU).  Synthetic inputs: random-init weights (seed 123), Philox kickoffs.
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline figures, the per-phase
+times and the env kernel's roofline object, all taken from the timed steps themselves.  --full adds what
+takes runs of its own after them: the learn-phase roofline (one more iteration timed per launch), the GAE
+microbenchmark, the C5 and exact-GEMM (x6) legs and the CPU baseline (--no-legs / --no-cpu-baseline drop
+the last two again).  --dump-outputs DIR writes what the last timed step left for the Learner's caller
+(the parameters and the [T, P] rollout arrays) as DIR/<name>.npy, before any of the --full runs; the seeds
+are fixed, so two builds run with the same arguments start from identical inputs.
 """
 import argparse
 import json
@@ -326,6 +334,27 @@ def extra_leg(dev, name, mesh, iters=1, **kw):
     return out
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept of each larger output array (11 arrays: at most 44 MB in all)
+
+
+def dump_outputs(L, path):
+    """--dump-outputs: the Learner's state after the last timed iteration, as its caller sees it -- the flat
+    parameters (policy, critic) and the rollout arrays of rlgpu.learner.Learner -- written as float32 .npy
+    files.  An array of more than DUMP_SAMPLE elements is cut to a fixed sample of its flat elements (sorted
+    indices from numpy's default_rng(0), the same for every run of the same shape)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {"params": L.ppo.flat(), "obs": L.obs, "masks": L.masks, "actions": L.actions, "logp": L.logp,
+              "rewards": L.rewards, "terms": L.terms, "values": L.values, "adv": L.adv, "target": L.target,
+              "ret": L.ret}
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -333,10 +362,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1, help="untimed PPO iterations")
     ap.add_argument("--arenas", type=int, default=ARENAS_PER_GPU)
     ap.add_argument("--rollout", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the learn-phase roofline, the GAE microbenchmark, the C5 / x6 "
+                         "legs and the CPU baseline (a plain run reports the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the parameters and rollout arrays left by the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--pmc-file", default=ENV_PMC_FILE,
                     help="the env kernel's PMC summary (tools/pmc_summary.py) that roofline.traffic comes from")
-    ap.add_argument("--no-legs", action="store_true", help="skip the C5 and exact-GEMM (x6) legs")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the C5 and exact-GEMM (x6) legs")
     ap.add_argument("--mesh", choices=("procedural", "synthetic"), default="procedural",
                     help="arena collision mesh: the SOCCAR-sized procedural stand-in (16 objects, 8,800 triangles: "
                          "rlgpu.mesh.procedural_soccar) or the 36-triangle synthetic arena")
@@ -477,12 +511,15 @@ def main():
                      "units_per_launch": launch_arenas, "collection_groups": args.arenas // launch_arenas,
                      "algorithmic_bytes_per_launch": b_env * launch_arenas},
     }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(L, args.dump_outputs)
     # learn-phase roofline: one more (untimed) iteration with HIP events around every training GEMM
     # and LayerNorm launch, on the stream each runs on (rlgpu_kernel_timing)
-    out["learn_roofline"] = learn_roofline(L, args.train_gemm)
-    if rank == 0 and world == 1:
+    if args.full:
+        out["learn_roofline"] = learn_roofline(L, args.train_gemm)
+    if args.full and rank == 0 and world == 1:
         out["gae_micro"] = gae_micro(dev)
-    if rank == 0 and world == 1 and not args.no_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_legs:
         L.close()
         torch.cuda.empty_cache()
         from rlgpu.ppo import GEMM_F32X6 as _X6
@@ -492,7 +529,7 @@ def main():
             extra_leg(dev, "C2 exact fp32 split (x6)", mesh, num_arenas=args.arenas, rollout_len=args.rollout,
                       train_gemm=_X6, arith=arith),
         ]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(mesh, args.mesh)
     if rank == 0:
         print(json.dumps(out), flush=True)

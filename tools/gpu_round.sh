@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round checkpoint on one GPU box (TAG names the output folder and the profile files):
-#   every -m gpu test, smoke(), the default bench line (with CPU baseline and legs), the bench under
+#   every -m gpu test, smoke(), the bench line of --full (with CPU baseline and legs), the bench under
 #   rocprofv3 --kernel-trace --stats, the env kernel's FETCH_SIZE / WRITE_SIZE passes (separate runs,
 #   MI355X_MICROARCH.md) summarised with the trace's kernel duration, and the training GEMMs' MFMA counters.
 # Every GPU step runs under its own time limit; the first failure ends the script.
@@ -16,7 +16,7 @@ if [ "$SKIP_TESTS" != 1 ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
   echo "smoke ok"
 fi
-timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
 tail -1 $O/bench.log > $O/bench_line.json
 echo "bench done"
 B1="--steps 1 --warmup 0 --no-cpu-baseline --no-legs"
