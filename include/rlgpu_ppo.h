@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct {
     int32_t obs_size;                         /* 167 (AdvancedObs) */
-    int32_t num_actions;                      /* 90 (DefaultAction) */
+    int32_t num_actions;                      /* 90 (DefaultAction); 2..128 */
     int32_t policy_layers[RLGPU_MAX_LAYERS];  /* hidden sizes (1..2048), e.g. {512, 512} */
     int32_t n_policy_layers;
     int32_t critic_layers[RLGPU_MAX_LAYERS];

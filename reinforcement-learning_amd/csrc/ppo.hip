@@ -546,6 +546,8 @@ void forward_train(rlgpu_ppo* h, int mi, const Input& x, int n, float* out, hipS
         tail_ok = false;
     }
     if (!O || head1) return;
+    // Not reached through rlgpu_ppo_create, which requires n_*_layers >= 1 (nh > 0, so head1 is set above); kept
+    // for a model without hidden layers.
     if (O->out == 1) {  // rank-1 head (critic value) of a model without hidden layers: wave-per-row dot products
         if (ld != O->in)
             throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "a rank-1 model without hidden layers needs obs_size % 4 == 0");
@@ -584,6 +586,7 @@ void backward(rlgpu_ppo* h, int mi, const Input& x, int n, const float* dout, hi
     if (!O) {
         dA_top = dout;
     } else if (O->out == 1 && nh == 0) {  // rank-1 head on the input: dA = dv w^T, dw / db partials in one pass
+        // not reached through rlgpu_ppo_create (n_*_layers >= 1), like forward_train's branch
         if (x.ld != O->in)
             throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "a rank-1 model without hidden layers needs obs_size % 4 == 0");
         int nb = (int)ceil_div(n, mlp::LNB_ROWS);
@@ -898,8 +901,9 @@ void refresh_half(rlgpu_ppo* h, hipStream_t s) {
 extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(cfg && out, "rlgpu_ppo_create: null argument");
-        RLGPU_REQUIRE(cfg->obs_size > 0 && cfg->num_actions > 0 && cfg->num_actions <= ppo::kMaxA,
-                      "num_actions must be in [1, 128]");
+        // one action has no distribution to learn: the entropy is normalised by log(num_actions), which is 0
+        RLGPU_REQUIRE(cfg->obs_size > 0 && cfg->num_actions >= 2 && cfg->num_actions <= ppo::kMaxA,
+                      "num_actions must be in [2, 128]");
         RLGPU_REQUIRE(cfg->n_policy_layers >= 1 && cfg->n_policy_layers <= RLGPU_MAX_LAYERS && cfg->n_critic_layers >= 1 &&
                           cfg->n_critic_layers <= RLGPU_MAX_LAYERS,
                       "1..8 hidden layers per model");
