@@ -621,6 +621,21 @@ DEV h16x8 tr_frag(const uint16_t* plane, int ob, int kof0, int lane) {
     return __builtin_bit_cast(h16x8, r);
 }
 
+// The H3 products of one 16-deep k step of a wave's 64 x (32 NJ) tile, from its fragments a / b [plane][block]:
+// one accumulator: the corrections, then the leading product, enter the running f32 sum (the rounding count of
+// an f32 FMA chain; a separate correction accumulator would cost 64 registers that the deeper stage uses instead)
+template <int NJ>
+DEV void h3_mfma_step(const h16x8 (&a)[2][2], const h16x8 (&b)[2][NJ], f32x16 (&acc)[2][NJ]) {
+#pragma unroll
+    for (int ti = 0; ti < 2; ti++)
+#pragma unroll
+        for (int tj = 0; tj < NJ; tj++) {
+            f32x16 c = acc[ti][tj];
+            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][ti], b[0][tj], c, 0, 0, 0);  // l h
+            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[1][tj], c, 0, 0, 0);  // h l
+            acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[0][tj], c, 0, 0, 0);  // h h
+        }
+}
 template <int XK, bool TA = false, bool TB = false, int P = XK + XPAD>
 DEV void h3_mfma_stage(const uint16_t (*As)[BM][P], const uint16_t (*Bs)[BN][P], int ra, int rb, int lane,
                        f32x16 (&acc)[2][2], f32x16 (&cor)[2][2]) {
@@ -638,18 +653,7 @@ DEV void h3_mfma_stage(const uint16_t (*As)[BM][P], const uint16_t (*Bs)[BN][P],
                 b[p][u] = TB ? tr_frag(&Bs[p][0][0], (rb & ~31) + 32 * u, ks * 16, lane)
                              : *(const h16x8*)&Bs[p][rb + 32 * u][xchunk<P, XK>(rb + 32 * u, kc) * 8];
             }
-        // one accumulator: the corrections, then the leading product, enter the running f32 sum (the
-        // rounding count of an f32 FMA chain; a separate correction accumulator would cost 64
-        // registers that the deeper stage uses instead)
-#pragma unroll
-        for (int ti = 0; ti < 2; ti++)
-#pragma unroll
-            for (int tj = 0; tj < 2; tj++) {
-                f32x16 c = acc[ti][tj];
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][ti], b[0][tj], c, 0, 0, 0);  // l h
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[1][tj], c, 0, 0, 0);  // h l
-                acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[0][tj], c, 0, 0, 0);  // h h
-            }
+        h3_mfma_step<2>(a, b, acc);
     }
 }
 
@@ -1289,6 +1293,82 @@ template <int MAXH>
 constexpr int lnf_rf() {
     return MAXH <= 8 ? 4 : (MAXH <= 16 ? 2 : 1);
 }
+// The LayerNorm forward's per-lane gamma / beta (lcol layout; 1 / 0 without LayerNorm or past H).
+template <int MAXH>
+DEV void lnf_affine(const float* gamma, const float* beta, int H, int use_ln, int lane, float (&g)[MAXH], float (&b)[MAXH]) {
+#pragma unroll
+    for (int q = 0; q < MAXH; q++) {
+        const int c = lcol<MAXH>(lane, q);
+        g[q] = (use_ln && c < H) ? gamma[c] : 1.f;
+        b[q] = (use_ln && c < H) ? beta[c] : 0.f;
+    }
+}
+// The LayerNorm forward of RF rows that a wave holds in lcol layout (v; columns past H are zeros): statistics,
+// activation, stats / max |act| / rank-1 head outputs of the rows below R.  The one statement of this
+// arithmetic: ln_act_fwd_f32 (z rows loaded from memory) and gemm_h3_rowln (z rows staged in LDS by the GEMM
+// that produced them) both call it, so their bits agree.
+template <int MAXH, int RF>
+DEV void lnf_rows(const float (&v)[RF][MAXH], const int (&row)[RF], int R, int H, const float (&g)[MAXH],
+                  const float (&b)[MAXH], float slope, int use_ln, bool vec, int lane, float* act, float2* stats,
+                  uint32_t& vmax, const float* head_w, const float* head_b, float* head_out) {
+    float mean[RF], rs[RF];
+#pragma unroll
+    for (int r = 0; r < RF; r++) {
+        mean[r] = 0.f;
+        rs[r] = 1.f;
+    }
+    if (use_ln) {
+#pragma unroll
+        for (int r = 0; r < RF; r++) {
+            float s = 0.f;
+#pragma unroll
+            for (int q = 0; q < MAXH; q++) s += v[r][q];
+            mean[r] = wave_sum_x(s) / (float)H;
+        }
+#pragma unroll
+        for (int r = 0; r < RF; r++) {
+            float s2 = 0.f;
+#pragma unroll
+            for (int q = 0; q < MAXH; q++) {
+                float d = lcol<MAXH>(lane, q) < H ? v[r][q] - mean[r] : 0.f;
+                s2 += d * d;
+            }
+            rs[r] = 1.f / sqrtf(wave_sum_x(s2) / (float)H + 1e-5f);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RF; r++) {
+        if (row[r] >= R) continue;
+        float a[MAXH];
+#pragma unroll
+        for (int q = 0; q < MAXH; q++) {
+            const float xh = use_ln ? (v[r][q] - mean[r]) * rs[r] : v[r][q];
+            const float hv = use_ln ? xh * g[q] + b[q] : xh;
+            a[q] = hv > 0.f ? hv : hv * slope;
+        }
+        float* ao = act + (int64_t)row[r] * H;
+        if (vec) {
+#pragma unroll
+            for (int q = 0; q < MAXH; q += 4) {
+                const int c = lcol<MAXH>(lane, q);
+                if (c < H) *reinterpret_cast<float4*>(ao + c) = make_float4(a[q], a[q + 1], a[q + 2], a[q + 3]);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < MAXH; q++) {
+                const int c = lcol<MAXH>(lane, q);
+                if (c < H) ao[c] = a[q];
+            }
+        }
+        if (lane == 0) stats[row[r]] = make_float2(mean[r], rs[r]);
+#pragma unroll
+        for (int q = 0; q < MAXH; q++) {
+            const uint32_t b = lcol<MAXH>(lane, q) < H ? abs_bits(a[q]) : 0u;
+            vmax = b > vmax ? b : vmax;
+        }
+        if (head_w) head1_row<MAXH>(a, head_w, head_b, H, vec, lane, head_out + row[r]);
+    }
+}
 template <int MAXH, int ROWS = LNF_ROWS, int RFX = lnf_rf<MAXH>()>
 __global__ void __launch_bounds__(256) ln_act_fwd_f32(const float* Z, const float* gamma, const float* beta, int R, int H,
                                                      float slope, int use_ln, float* act, float2* stats, float* amax,
@@ -1298,12 +1378,7 @@ __global__ void __launch_bounds__(256) ln_act_fwd_f32(const float* Z, const floa
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const bool vec = (H % 4 == 0) && (MAXH % 4 == 0);
     float g[MAXH], b[MAXH];
-#pragma unroll
-    for (int q = 0; q < MAXH; q++) {
-        const int c = lcol<MAXH>(lane, q);
-        g[q] = (use_ln && c < H) ? gamma[c] : 1.f;
-        b[q] = (use_ln && c < H) ? beta[c] : 0.f;
-    }
+    lnf_affine<MAXH>(gamma, beta, H, use_ln, lane, g, b);
     constexpr int RF = RFX;
     for (int i0 = 0; i0 < ROWS / 4; i0 += RF) {
         int row[RF];
@@ -1327,65 +1402,169 @@ __global__ void __launch_bounds__(256) ln_act_fwd_f32(const float* Z, const floa
                 }
             }
         }
-        float mean[RF], rs[RF];
+        lnf_rows<MAXH, RF>(v, row, R, H, g, b, slope, use_ln, vec, lane, act, stats, vmax, head_w, head_b, head_out);
+    }
+    if (amax) h3_amax_commit(amax, vmax);
+}
+
+// ---- Full-row H3 forward GEMM with LayerNorm + LeakyReLU in the same launch (gemm_h3_rowln): one hidden layer's
+// gemm_x6<A_IK, B_JK, pre-split B, H3> + ln_act_fwd_f32<8> pair for a 512-column output.  A workgroup owns 64
+// rows across all 512 columns, so the f32 activation slice is loaded and split once per row block (not once per
+// 128-column tile) and z never has to be read back: 4 waves, each all 64 rows x 128 columns (2 x 4 MFMA blocks).
+// No two waves share a weight column, so B does not go through LDS: every wave streams its fragments from L2
+// in fragment order (frag_weight_h3's copy of the split planes: each load instruction of a wave is one
+// contiguous 1 KB), one 16-deep k step ahead of the MFMAs that use them.  A: 32-deep stages, split into two
+// XOR-swizzled fp16 planes in a double-buffered LDS stage (one barrier per stage), the next stage prefetched
+// into registers.  Per 16-k step the products enter the one accumulator as l.h, h.l, h.h (h3_mfma_step), one K
+// chunk, and the epilogue value is gemm_x6's ldexpf(v * csc, -pa) + bias.  The finished z rows are staged in
+// LDS, 32 rows at a time (pitch 520 floats: the two half-waves of an accumulator store land on disjoint
+// banks), and each wave takes whole rows from there in lcol layout: it writes z (the backward recomputes xhat
+// from it) and runs lnf_rows, ln_act_fwd_f32's arithmetic.  Same bits as the two-kernel path.  65 KB LDS and
+// at most 256 VGPRs: two workgroups per CU, one's epilogue under the other's K loop.
+constexpr int RLN_BM = 64, RLN_J = 512, RLN_ZP = RLN_J + 8;
+constexpr int RLN_LDS = 32 * RLN_ZP * 4;  // bytes: the 32-row z stage (the K loop's A stages use the first 16 KB)
+static_assert(2 * 2 * RLN_BM * 32 * 2 <= RLN_LDS, "the A stages must fit the z stage");
+// The fragment-order copy of a layer's forward planes (split_weight_h3, trans = 0; RLN_J rows, ld multiple of 16):
+// 16-byte chunk [k step][32-column block][plane][lane] = plane row 32 block + (lane & 31), k = 16 step +
+// 8 (lane >> 5) .. + 7 -- the 32x32x16 MFMA B fragment.  Same fp16 bits, only their order changes.
+__global__ void __launch_bounds__(256) frag_weight_h3(const uint16_t* planes, int64_t plane, int ld, uint16_t* frag) {
+    const int e = blockIdx.x * 256 + threadIdx.x;  // chunk
+    if (e >= (ld / 16) * (RLN_J / 32) * 2 * 64) return;
+    const int lane = e & 63, p = (e >> 6) & 1, jb = (e >> 7) % (RLN_J / 32), ks = (e >> 7) / (RLN_J / 32);
+    const uint16_t* src = planes + p * plane + (int64_t)(jb * 32 + (lane & 31)) * ld + ks * 16 + 8 * (lane >> 5);
+    *reinterpret_cast<u32x4_t*>(frag + (int64_t)e * 8) = *reinterpret_cast<const u32x4_t*>(src);
+}
+struct RowLnArgs {
+    const float* gamma;  // LayerNorm + LeakyReLU (ln_act_fwd_f32's arguments)
+    const float* beta;
+    float slope;
+    int use_ln;
+    float* act;
+    float2* stats;
+    float* amax;
+    const float* head_w;
+    const float* head_b;
+    float* head_out;
+};
+// g.B: the fragment-order planes; g.ldb: their k extent (a multiple of 32, at least K rounded up to 32)
+__global__ void __launch_bounds__(256, 2) gemm_h3_rowln(GemmArgs g, RowLnArgs ln) {
+    constexpr int XK = 32, KG = XK / 8, MAXH = RLN_J / 64, RF = lnf_rf<MAXH>();
+    constexpr int KSTEP = (RLN_J / 32) * 2 * 64 * 8;  // halves per k step of the fragment-order planes
+    __shared__ __attribute__((aligned(16))) unsigned char smem[RLN_LDS];
+    auto As = reinterpret_cast<uint16_t (*)[2][RLN_BM][XK]>(smem);  // [buffer][plane][row][k]
+    float* zs = reinterpret_cast<float*>(smem);                      // epilogue: [32][RLN_ZP]
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int i0 = blockIdx.x * RLN_BM;
+    const int ke = g.K;
+    f32x16 acc[2][4];
 #pragma unroll
-        for (int r = 0; r < RF; r++) {
-            mean[r] = 0.f;
-            rs[r] = 1.f;
-        }
-        if (use_ln) {
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
+    // this thread's share of an A stage: row t / KG, k group t % KG (8 floats)
+    const int srow = t / KG, kg = t % KG;
+    const float* arow = i0 + srow < g.I ? g.A + (int64_t)(i0 + srow) * g.lda : nullptr;
+    f32x4_t va[2];
+    const int pa = h3_pow(shard_max_bits(g.amax_a));
+    const float sa = pow2f(pa);
+    auto load_a = [&](int k0) {  // past K it reads the zero row
+        va[0] = load4v<true>(arow, k0 + kg * 8, ke);
+        va[1] = load4v<true>(arow, k0 + kg * 8 + 4, ke);
+    };
+    auto store_a = [&](int buf) {
+        u32x4_t h, l;
+        split2h(va, sa, h, l);
+        const int c = xchunk<XK, XK>(srow, kg) * 8;
+        *reinterpret_cast<u32x4_t*>(&As[buf][0][srow][c]) = h;
+        *reinterpret_cast<u32x4_t*>(&As[buf][1][srow][c]) = l;
+    };
+    // this wave's B fragments of k step s (clamped to the planes' last: the prefetch past the end reloads it)
+    const uint16_t* Bw = reinterpret_cast<const uint16_t*>(g.B) + (w * 4 * 2 * 64 + lane) * 8;
+    const int last = (int)g.ldb / 16 - 1;
+    auto load_b = [&](h16x8 (&b)[2][4], int s) {
+        const uint16_t* q = Bw + (int64_t)min(s, last) * KSTEP;
+#pragma unroll
+        for (int tj = 0; tj < 4; tj++)
+#pragma unroll
+            for (int p = 0; p < 2; p++) b[p][tj] = *reinterpret_cast<const h16x8*>(q + (tj * 2 + p) * 64 * 8);
+    };
+    const int l32 = lane & 31, hh = lane >> 5;
+    auto mfma_step = [&](int buf, int ks, const h16x8 (&b)[2][4]) {
+        const int kc = 2 * ks + hh;  // logical 16-byte chunk of this lane's 8 k
+        h16x8 a[2][2];
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+            for (int u = 0; u < 2; u++) a[p][u] = *(const h16x8*)&As[buf][p][l32 + 32 * u][xchunk<XK, XK>(l32 + 32 * u, kc) * 8];
+        h3_mfma_step<4>(a, b, acc);
+    };
+    h16x8 b0[2][4], b1[2][4];
+    load_a(0);
+    load_b(b0, 0);
+    store_a(0);
+    __syncthreads();
+    load_a(XK);
+    int buf = 0;
+    for (int k0 = 0; k0 < ke; k0 += XK) {
+        const int s = k0 / 16;
+        // each k step's fragments are requested a whole step of MFMAs before their use (pinned: left alone, the
+        // scheduler sinks the loads to just before the MFMAs that wait for them)
+        load_b(b1, s + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma_step(buf, 0, b0);
+        __builtin_amdgcn_sched_barrier(0);
+        load_b(b0, s + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma_step(buf, 1, b1);
+        store_a(buf ^ 1);
+        load_a(k0 + 2 * XK);
+        __syncthreads();
+        buf ^= 1;
+    }
+    // epilogue: z = ldexpf(v * csc, -pa) + bias into the LDS stage, then LayerNorm + LeakyReLU per row
+    float csc[4], bj[4];
+#pragma unroll
+    for (int tj = 0; tj < 4; tj++) {
+        const int j = w * 128 + tj * 32 + l32;
+        csc[tj] = g.bscale[j];
+        bj[tj] = g.bias ? g.bias[j] : 0.f;
+    }
+    float lg[MAXH], lb[MAXH];
+    lnf_affine<MAXH>(ln.gamma, ln.beta, RLN_J, ln.use_ln, lane, lg, lb);
+    uint32_t vmax = 0;
+#pragma unroll
+    for (int ti = 0; ti < 2; ti++) {
+        if (ti) __syncthreads();  // the first half's rows are consumed
+#pragma unroll
+        for (int tj = 0; tj < 4; tj++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float v = acc[ti][tj][r] + 0.f;  // gemm_x6's sum with its (zero) correction accumulator
+                zs[((r & 3) + 8 * (r >> 2) + 4 * hh) * RLN_ZP + w * 128 + tj * 32 + l32] = ldexpf(v * csc[tj], -pa) + bj[tj];
+            }
+        __syncthreads();
+        for (int b0 = 0; b0 < 32 / 4; b0 += RF) {  // this wave's 8 rows of the half, RF at a time
+            int row[RF];
+            float v[RF][MAXH];
 #pragma unroll
             for (int r = 0; r < RF; r++) {
-                float s = 0.f;
-#pragma unroll
-                for (int q = 0; q < MAXH; q++) s += v[r][q];
-                mean[r] = wave_sum_x(s) / (float)H;
-            }
-#pragma unroll
-            for (int r = 0; r < RF; r++) {
-                float s2 = 0.f;
-#pragma unroll
-                for (int q = 0; q < MAXH; q++) {
-                    float d = lcol<MAXH>(lane, q) < H ? v[r][q] - mean[r] : 0.f;
-                    s2 += d * d;
-                }
-                rs[r] = 1.f / sqrtf(wave_sum_x(s2) / (float)H + 1e-5f);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < RF; r++) {
-            if (row[r] >= R) continue;
-            float a[MAXH];
-#pragma unroll
-            for (int q = 0; q < MAXH; q++) {
-                const float xh = use_ln ? (v[r][q] - mean[r]) * rs[r] : v[r][q];
-                const float hv = use_ln ? xh * g[q] + b[q] : xh;
-                a[q] = hv > 0.f ? hv : hv * slope;
-            }
-            float* ao = act + (int64_t)row[r] * H;
-            if (vec) {
+                const int zr = w * (32 / 4) + b0 + r;
+                row[r] = i0 + ti * 32 + zr;
 #pragma unroll
                 for (int q = 0; q < MAXH; q += 4) {
                     const int c = lcol<MAXH>(lane, q);
-                    if (c < H) *reinterpret_cast<float4*>(ao + c) = make_float4(a[q], a[q + 1], a[q + 2], a[q + 3]);
-                }
-            } else {
-#pragma unroll
-                for (int q = 0; q < MAXH; q++) {
-                    const int c = lcol<MAXH>(lane, q);
-                    if (c < H) ao[c] = a[q];
+                    const float4 x = *reinterpret_cast<const float4*>(zs + zr * RLN_ZP + c);
+                    v[r][q] = x.x; v[r][q + 1] = x.y; v[r][q + 2] = x.z; v[r][q + 3] = x.w;
+                    if (row[r] < g.I) *reinterpret_cast<float4*>(g.C + (int64_t)row[r] * g.ldc + c) = x;
                 }
             }
-            if (lane == 0) stats[row[r]] = make_float2(mean[r], rs[r]);
-#pragma unroll
-            for (int q = 0; q < MAXH; q++) {
-                const uint32_t b = lcol<MAXH>(lane, q) < H ? abs_bits(a[q]) : 0u;
-                vmax = b > vmax ? b : vmax;
-            }
-            if (head_w) head1_row<MAXH>(a, head_w, head_b, H, vec, lane, head_out + row[r]);
+            lnf_rows<MAXH, RF>(v, row, g.I, RLN_J, lg, lb, ln.slope, ln.use_ln, true, lane, ln.act, ln.stats, vmax, ln.head_w,
+                               ln.head_b, ln.head_out);
         }
     }
-    if (amax) h3_amax_commit(amax, vmax);
+    if (ln.amax) h3_amax_commit(ln.amax, vmax);
 }
 
 // bf16 inference variant: Z bf16 in, bf16(LeakyReLU(bf16(LN(Z)))) out (torch bf16 module chain).

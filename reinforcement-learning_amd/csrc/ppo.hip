@@ -34,6 +34,7 @@ struct Layer {
     int64_t sf = -1, sb = -1;
     int sf_rows = 0, sf_ld = 0, sb_rows = 0, sb_ld = 0;
     int64_t sfs = -1, sbs = -1;  // H3: per-row inverse scales of the planes (offsets into Model::wscale)
+    int64_t sq = -1;  // H3, hidden layers of mlp::RLN_J columns: the forward planes in fragment order (mlp::frag_weight_h3)
 };
 
 struct Model {
@@ -84,6 +85,21 @@ inline bool h3_quad(int J) {
     }();
     if (J % mlp::BQ != 0) return false;
     return mode == 1 ? true : (mode == 0 ? false : J >= 1024);
+}
+// Hidden layers of forward_train on the full-row kernel mlp::gemm_h3_rowln (the H3 forward GEMM with its
+// LayerNorm + LeakyReLU in the same launch; same bits as gemm_x6 + ln_act_fwd_f32).  Eligible output width:
+// exactly 512 columns (mlp::RLN_J: the kernel's tile is the whole row, and its LayerNorm part is
+// ln_act_fwd_f32<8>'s column layout); every other width keeps the two-kernel path.  RLGPU_H3_ROWFUSE=0:
+// never, 1: every eligible layer; unset: on (C2 minibatch 1.57 -> 1.49 ms, learn phase 126.9 -> 120.2 ms per
+// iteration against the two-kernel path, profiles/r07a_rowfuse_bench_pairs.txt).
+constexpr bool kRowFuseDefault = true;
+inline bool h3_rowfuse(int J) {
+    static const int mode = [] {
+        const char* e = getenv("RLGPU_H3_ROWFUSE");
+        return e ? atoi(e) : -1;
+    }();
+    if (J != mlp::RLN_J) return false;
+    return mode == 1 ? true : (mode == 0 ? false : kRowFuseDefault);
 }
 inline bool split_mode_(int mode) { return mode == RLGPU_GEMM_F32X6 || mode == RLGPU_GEMM_F16X3; }
 inline int gemm_slots(int mode) {
@@ -336,6 +352,9 @@ void split_weights(const float* P, Model& m, hipStream_t s) {
             if (L.sf >= 0)
                 hipLaunchKernelGGL(mlp::split_weight_h3, dim3(L.sf_rows), dim3(256), 0, s, P + L.w, L.out, L.in, (int64_t)L.in, 0, L.sf_ld,
                                    m.wsplit + L.sf, (int64_t)L.sf_rows * L.sf_ld, m.wscale + L.sfs);
+            if (L.sq >= 0 && h3_rowfuse(L.out))
+                hipLaunchKernelGGL(mlp::frag_weight_h3, dim3(L.sf_ld / 16 * (mlp::RLN_J / 32) * 2 * 64 / 256), dim3(256), 0, s,
+                                   m.wsplit + L.sf, (int64_t)L.sf_rows * L.sf_ld, L.sf_ld, m.wsplit + L.sq);
             if (L.sb >= 0)
                 hipLaunchKernelGGL(mlp::split_weight_h3, dim3(L.sb_rows), dim3(256), 0, s, P + L.w, L.out, L.in, (int64_t)L.in, 1, L.sb_ld,
                                    m.wsplit + L.sb, (int64_t)L.sb_rows * L.sb_ld, m.wscale + L.sbs);
@@ -526,6 +545,33 @@ void forward_train(rlgpu_ppo* h, int mi, const Input& x, int n, float* out, hipS
         const float* gg = L.g >= 0 ? P + L.g : nullptr;
         const float* bb = L.be >= 0 ? P + L.be : nullptr;
         const bool fuse = head1 && l == nh - 1;
+        const bool av = (ld % 4 == 0) && ((uintptr_t)in % 16 == 0) && (L.in % 4 == 0 || tail_ok);  // gemm_x6_pre's float4 test
+        if (m.mode == RLGPU_GEMM_F16X3 && L.sf >= 0 && L.sq >= 0 && av && h3_rowfuse(L.out)) {
+            if (!in_amax) throw rlgpu::Error(RLGPU_ERR_STATE, "H3 GEMM without operand scales");
+            ktime::Span span(ktime::FWD_GEMM, 2.0 * n * L.out * L.in, s);
+            mlp::GemmArgs g{};
+            g.A = in;
+            g.B = reinterpret_cast<const float*>(m.wsplit + L.sq);
+            g.C = m.xhat[l];
+            g.bias = P + L.b;
+            g.lda = ld;
+            g.ldb = L.sf_ld;
+            g.ldc = L.out;
+            g.I = n;
+            g.J = L.out;
+            g.K = L.in;
+            g.amax_a = in_amax;
+            g.bscale = wscale_at(m, L.sfs);
+            const mlp::RowLnArgs ln{gg, bb, h->cfg.leaky_slope, h->cfg.layer_norm, m.act[l], reinterpret_cast<float2*>(m.rstd[l]),
+                                    amax_slot(m, l), fuse ? P + O->w : nullptr, fuse ? P + O->b : nullptr, fuse ? out : nullptr};
+            hipLaunchKernelGGL(mlp::gemm_h3_rowln, dim3(ceil_div(n, mlp::RLN_BM)), dim3(256), 0, s, g, ln);
+            RLGPU_CHECK_HIP(hipGetLastError());
+            in = m.act[l];
+            in_amax = amax_slot(m, l);
+            ld = L.out;
+            tail_ok = false;
+            continue;
+        }
         if (L.sf >= 0)
             gemm_x6_pre(in, ld, m.wsplit + L.sf, L.sf_ld, (int64_t)L.sf_rows * L.sf_ld, m.xhat[l], L.out, P + L.b, n, L.out,
                         L.in, s, tail_ok, in_amax, wscale_at(m, L.sfs));
@@ -849,6 +895,10 @@ void build_model(rlgpu_ppo* h, Model& m, int in, const int32_t* layers, int nl, 
             m.nsplit += np * (int64_t)L.sf_rows * L.sf_ld;
             L.sfs = m.nscale;
             m.nscale += L.sf_rows;
+            if (m.mode == RLGPU_GEMM_F16X3 && hidden && L.out == mlp::RLN_J) {
+                L.sq = m.nsplit;
+                m.nsplit += 2 * (int64_t)mlp::RLN_J * L.sf_ld;
+            }
             if (l > 0 || input_grad) {  // dA of the first layer only behind the shared head
                 L.sb_rows = (int)ceil_div(L.in, rpad) * rpad;
                 L.sb_ld = (int)ceil_div(L.out, mlp::XKMAX) * mlp::XKMAX;

@@ -1,0 +1,91 @@
+"""The full-row H3 forward GEMM with LayerNorm + LeakyReLU in the same launch (mlp::gemm_h3_rowln,
+RLGPU_H3_ROWFUSE) against the two-kernel path it replaces (gemm_x6 + ln_act_fwd_f32): same bits, and a
+kernel that keeps its registers and its two workgroups per CU."""
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "reinforcement-learning_amd")
+
+# (rows, obs, policy layers, critic layers, layer_norm, leaky_slope).  The kernel's tile is 64 rows x 512 columns
+# (the only eligible width), its z stage 32 rows: 1 row, one below / above the tile height, several tiles with a
+# ragged last block; K = 167 (rows padded to 168 floats, the 16-byte loads straddle the row end), K = 168 and the
+# hidden K = 512; the critic's last layer carries the fused rank-1 head.  (510, 512): the first layer falls
+# back to the two-kernel path (ragged width), the second is fused behind it.
+CASES = [
+    (1, 167, (512, 512), (512, 512), True, 0.01),
+    (63, 168, (512, 512), (512, 512), True, 0.01),
+    (65, 167, (512, 512), (512, 512), True, 0.01),
+    (1000, 167, (512, 512), (512, 512), True, 0.01),
+    (1000, 168, (512, 512), (512, 512), True, 0.01),
+    (1000, 167, (510, 512), (510, 512), True, 0.01),
+    (65, 167, (512, 512), (512, 512), False, 0.01),
+    (193, 167, (512, 512), (512, 512), True, 0.2),
+]
+
+_CHILD = r"""
+import sys, numpy as np, torch
+sys.path[:0] = [sys.argv[2], sys.argv[2] + "/reinforcement-learning_amd", sys.argv[2] + "/tests"]
+from rlgpu.ppo import PPO
+from test_ppo import make_batch
+from test_ppo_rowfuse import CASES
+dev = torch.device("cuda:0")
+out = []
+for n, obs_size, pol, crit, ln, slope in CASES:
+    p = PPO(obs_size=obs_size, policy_layers=pol, critic_layers=crit, layer_norm=ln, leaky_slope=slope, max_rows=1024, seed=5)
+    obs, masks, acts, old, adv, tgt = make_batch(np.random.default_rng(n + obs_size), n, obs_size=obs_size)
+    d = [torch.from_numpy(v).to(dev) for v in (obs, masks, acts, old, adv, tgt)]
+    if n > 1:
+        p.adv_normalizer(d[4])
+    p.zero_grad()
+    p.minibatch(*d, None, 0, n, n)
+    out += [p.flat(grads=True).cpu().numpy(), p.forward(0, d[0]).cpu().numpy().ravel(), p.forward(1, d[0]).cpu().numpy().ravel()]
+np.save(sys.argv[1], np.concatenate(out))
+"""
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(120)
+def test_rowfuse_bit_identical(gpu, tmp_path):
+    """RLGPU_H3_ROWFUSE=1 (every 512-column hidden layer on gemm_h3_rowln) gives the same minibatch gradients,
+    policy forward and critic values, bit for bit, as RLGPU_H3_ROWFUSE=0 (gemm_x6 + ln_act_fwd_f32): the same
+    products in the same order into one accumulator, the same epilogue value, and the LayerNorm forward's own
+    arithmetic on those bits.  The knob is read once per process: child processes."""
+    res = {}
+    for v in ("0", "1"):
+        f = str(tmp_path / f"r{v}.npy")
+        r = subprocess.run(["timeout", "-k", "10", "90", sys.executable, "-c", _CHILD, f, ROOT],
+                           env=dict(os.environ, RLGPU_H3_ROWFUSE=v), capture_output=True, text=True, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        res[v] = np.load(f)
+    assert res["0"].shape == res["1"].shape
+    assert np.isfinite(res["0"]).all()
+    np.testing.assert_array_equal(res["0"].view(np.uint32), res["1"].view(np.uint32))
+
+
+def test_rowfuse_kernel_resources(tmp_path):
+    """The compiler's resource-usage remarks for gemm_h3_rowln (device code of csrc/mlp_kernels.hpp alone, the
+    library's flags): no VGPR spill, no scratch, and two workgroups per CU -- 256 threads with at most 256
+    VGPRs (2 waves / SIMD) and at most half of the CU's 160 KB of LDS."""
+    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    assert os.path.exists(hipcc), "hipcc not found"
+    src = tmp_path / "rowln.hip"
+    src.write_text('#include "%s"\n' % os.path.join(PKG, "csrc", "mlp_kernels.hpp"))
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "--cuda-device-only", "-O3", "-std=c++17", "-fno-slp-vectorize",
+                        "-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o", str(tmp_path / "rowln.o")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    blocks = r.stderr.split("Function Name: ")
+    mine = [b for b in blocks if "gemm_h3_rowln" in b.splitlines()[0]]
+    assert len(mine) == 1, [b.splitlines()[0] for b in blocks[1:]]
+    val = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", mine[0])}
+    print(val)
+    assert val["VGPRs Spill"] == 0 and val["SGPRs Spill"] == 0 and val["ScratchSize"] == 0, val
+    assert val["VGPRs"] + val["AGPRs"] <= 256 and val["Occupancy"] >= 2, val
+    assert val["LDS Size"] <= 160 * 1024 // 2, val
