@@ -1446,17 +1446,17 @@ struct RowLnArgs {
     const float* head_b;
     float* head_out;
 };
+// The full-row kernels' prologue and K loop (gemm_h3_rowln and gemm_h3_row_lnbwd): the workgroup's 64 x 512
+// products into acc; returns the A operand's scale exponent for the epilogue's ldexpf.  Ends on a barrier:
+// the A stages in smem are free.
 // g.B: the fragment-order planes; g.ldb: their k extent (a multiple of 32, at least K rounded up to 32)
-__global__ void __launch_bounds__(256, 2) gemm_h3_rowln(GemmArgs g, RowLnArgs ln) {
-    constexpr int XK = 32, KG = XK / 8, MAXH = RLN_J / 64, RF = lnf_rf<MAXH>();
+DEV int h3_row_kloop(const GemmArgs& g, unsigned char* smem, f32x16 (&acc)[2][4]) {
+    constexpr int XK = 32, KG = XK / 8;
     constexpr int KSTEP = (RLN_J / 32) * 2 * 64 * 8;  // halves per k step of the fragment-order planes
-    __shared__ __attribute__((aligned(16))) unsigned char smem[RLN_LDS];
     auto As = reinterpret_cast<uint16_t (*)[2][RLN_BM][XK]>(smem);  // [buffer][plane][row][k]
-    float* zs = reinterpret_cast<float*>(smem);                      // epilogue: [32][RLN_ZP]
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int i0 = blockIdx.x * RLN_BM;
     const int ke = g.K;
-    f32x16 acc[2][4];
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
@@ -1523,6 +1523,17 @@ __global__ void __launch_bounds__(256, 2) gemm_h3_rowln(GemmArgs g, RowLnArgs ln
         __syncthreads();
         buf ^= 1;
     }
+    return pa;
+}
+__global__ void __launch_bounds__(256, 2) gemm_h3_rowln(GemmArgs g, RowLnArgs ln) {
+    constexpr int MAXH = RLN_J / 64, RF = lnf_rf<MAXH>();
+    __shared__ __attribute__((aligned(16))) unsigned char smem[RLN_LDS];
+    float* zs = reinterpret_cast<float*>(smem);  // epilogue: [32][RLN_ZP]
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int i0 = blockIdx.x * RLN_BM;
+    const int l32 = lane & 31, hh = lane >> 5;
+    f32x16 acc[2][4];
+    const int pa = h3_row_kloop(g, smem, acc);
     // epilogue: z = ldexpf(v * csc, -pa) + bias into the LDS stage, then LayerNorm + LeakyReLU per row
     float csc[4], bj[4];
 #pragma unroll
@@ -1658,6 +1669,66 @@ __global__ void __launch_bounds__(256) ln_act_fwd_bf16(const uint16_t* Z, const 
 // waves walks LNB_ROWS/4 rows.
 constexpr int LNB_ROWS = 32;
 constexpr int LNB_ROWS_MIN = 16;  // fewest rows per block of any variant (partial buffers are sized for it)
+// The LayerNorm + LeakyReLU backward of one row that a wave holds in lcol layout: x the pre-norm z (left as
+// xhat), av the activation's gradient, st the row's (mean, rstd); writes the dZ row and adds the row to the
+// wave's column partials pz / pg / pb (and, HEAD, the rank-1 head's ph / phb with the row's dv) and to max |dZ|.
+// The one statement of this arithmetic: ln_act_bwd (dA rows loaded from memory) and gemm_h3_row_lnbwd (dA rows
+// staged in LDS by the GEMM that produced them) both call it, so their bits agree.
+template <int MAXH, bool HEAD>
+DEV void lnb_row(float (&x)[MAXH], const float (&av)[MAXH], const float2 st, float dv, const float (&g)[MAXH],
+                 const float (&b)[MAXH], float slope, int use_ln, int H, bool vec, int lane, float* dz, float (&pz)[MAXH],
+                 float (&pg)[MAXH], float (&pb)[MAXH], float (&ph)[MAXH], float& phb, uint32_t& vmax) {
+    float dh[MAXH];
+    if (use_ln) {
+#pragma unroll
+        for (int q = 0; q < MAXH; q++) x[q] = (x[q] - st.x) * st.y;  // the forward's xhat, same ops
+    }
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < MAXH; q++) {
+        float h = x[q] * g[q] + b[q];
+        dh[q] = h > 0.f ? av[q] : av[q] * slope;
+        float gg = dh[q] * g[q];
+        s1 += gg;
+        s2 += gg * x[q];
+        // the rank-1 head's weight gradient dv * act, act recomputed as the forward made it
+        // (head1_bwd's per-lane sums in its row order: the same bits)
+        if (HEAD && lcol<MAXH>(lane, q) < H) ph[q] += dv * (h > 0.f ? h : h * slope);
+    }
+    if (HEAD) phb += dv;
+    float d[MAXH];
+    if (use_ln) {
+        float m1 = wave_sum_x(s1) / (float)H, m2 = wave_sum_x(s2) / (float)H;  // == wave_sum
+        float rs = st.y;
+#pragma unroll
+        for (int q = 0; q < MAXH; q++) d[q] = rs * (dh[q] * g[q] - m1 - x[q] * m2);
+    } else {
+#pragma unroll
+        for (int q = 0; q < MAXH; q++) d[q] = dh[q];
+    }
+    if (vec) {
+#pragma unroll
+        for (int q = 0; q < MAXH; q += 4) {
+            const int c = lcol<MAXH>(lane, q);
+            if (c < H) *reinterpret_cast<float4*>(dz + c) = make_float4(d[q], d[q + 1], d[q + 2], d[q + 3]);
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < MAXH; q++) {
+            const int c = lcol<MAXH>(lane, q);
+            if (c < H) dz[c] = d[q];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < MAXH; q++) {
+        bool in = lcol<MAXH>(lane, q) < H;
+        pz[q] += in ? d[q] : 0.f;
+        pg[q] += in ? dh[q] * x[q] : 0.f;
+        pb[q] += in ? dh[q] : 0.f;
+        const uint32_t bb = in ? abs_bits(d[q]) : 0u;
+        vmax = bb > vmax ? bb : vmax;
+    }
+}
 // ROWS rows per block, PR rows per wave and pass (loads issued before the reductions); every wave
 // adds its rows to its partials in ascending order whatever PR is, so PR changes no bit
 template <int MAXH, bool HEAD = false, int ROWS = LNB_ROWS, int PR = 2>
@@ -1725,62 +1796,10 @@ __global__ void __launch_bounds__(256) ln_act_bwd(const float* dA, const float* 
         }
 #pragma unroll
         for (int j = 0; j < PR; j++) {
-        const int row = r0 + rr + 4 * j;
-        if (row >= R) break;
-        const float2 st = sts[j];
-        float* x = xs[j];
-        const float* av = as[j];
-        float dh[MAXH];
-        if (use_ln) {
-#pragma unroll
-            for (int q = 0; q < MAXH; q++) x[q] = (x[q] - st.x) * st.y;  // the forward's xhat, same ops
-        }
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int q = 0; q < MAXH; q++) {
-            float h = x[q] * g[q] + b[q];
-            dh[q] = h > 0.f ? av[q] : av[q] * slope;
-            float gg = dh[q] * g[q];
-            s1 += gg;
-            s2 += gg * x[q];
-            // the rank-1 head's weight gradient dv * act, act recomputed as the forward made it
-            // (head1_bwd's per-lane sums in its row order: the same bits)
-            if (HEAD && lcol<MAXH>(lane, q) < H) ph[q] += dvs[j] * (h > 0.f ? h : h * slope);
-        }
-        if (HEAD) phb += dvs[j];
-        float* dz = dZ + (int64_t)row * H;
-        float d[MAXH];
-        if (use_ln) {
-            float m1 = wave_sum_x(s1) / (float)H, m2 = wave_sum_x(s2) / (float)H;  // == wave_sum
-            float rs = st.y;
-#pragma unroll
-            for (int q = 0; q < MAXH; q++) d[q] = rs * (dh[q] * g[q] - m1 - x[q] * m2);
-        } else {
-#pragma unroll
-            for (int q = 0; q < MAXH; q++) d[q] = dh[q];
-        }
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < MAXH; q += 4) {
-                const int c = lcol<MAXH>(lane, q);
-                if (c < H) *reinterpret_cast<float4*>(dz + c) = make_float4(d[q], d[q + 1], d[q + 2], d[q + 3]);
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < MAXH; q++) {
-                const int c = lcol<MAXH>(lane, q);
-                if (c < H) dz[c] = d[q];
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < MAXH; q++) {
-            bool in = lcol<MAXH>(lane, q) < H;
-            pz[q] += in ? d[q] : 0.f;
-            pg[q] += in ? dh[q] * x[q] : 0.f;
-            pb[q] += in ? dh[q] : 0.f;
-            const uint32_t bb = in ? abs_bits(d[q]) : 0u;
-            vmax = bb > vmax ? bb : vmax;
-        }
+            const int row = r0 + rr + 4 * j;
+            if (row >= R) break;
+            lnb_row<MAXH, HEAD>(xs[j], as[j], sts[j], dvs[j], g, b, slope, use_ln, H, vec, lane, dZ + (int64_t)row * H, pz, pg,
+                                pb, ph, phb, vmax);
         }
     }
 #pragma unroll
@@ -1808,6 +1827,109 @@ __global__ void __launch_bounds__(256) ln_act_bwd(const float* dA, const float* 
             ho[H] = hred[0][64 * MAXH] + hred[1][64 * MAXH] + hred[2][64 * MAXH] + hred[3][64 * MAXH];
     }
     if (amax) h3_amax_commit(amax, vmax);
+}
+
+// ---- Full-row H3 input-gradient GEMM with the LayerNorm + LeakyReLU backward of the layer below in the same
+// launch (gemm_h3_row_lnbwd): a gemm_x6<A_IK, B_JK, pre-split B, H3> dA GEMM of 512 output columns + the
+// ln_act_bwd<8> that reads it.  gemm_h3_rowln's tile, prologue and K loop (h3_row_kloop) on the fragment-order
+// copy of the layer's backward planes; the epilogue value is gemm_x6's ldexpf(v * csc, -pa) + 0 (no bias).
+// The finished dA rows are staged in LDS, 32 rows at a time, and never reach memory: each wave takes whole
+// rows from the stage in lcol layout, loads the matching z row and (mean, rstd), and runs lnb_row.  The 32-row
+// half is one ln_act_bwd<8> block: wave w takes the rows w, w + 4, ... of the half in ascending order, the four
+// waves' partials are added as red[0] + red[1] + red[2] + red[3] (red reuses the stage once the half's rows are
+// consumed) into partial block 2 blockIdx.x + half, and a half wholly past I writes none -- part holds
+// ceil(I / 32) blocks with ln_act_bwd's bits.
+struct RowLnBwdArgs {
+    const float* gamma;  // of the layer below (ln_act_bwd's arguments)
+    const float* beta;
+    float slope;
+    int use_ln;
+    const float* z;  // its pre-norm z [I][RLN_J] and (mean, rstd)
+    const float2* stats;
+    float* dz;    // out: its dZ [I][RLN_J]
+    float* part;  // out: [ceil(I / 32)][3][RLN_J]
+    float* amax;  // max |dZ| shards
+};
+__global__ void __launch_bounds__(256, 2) gemm_h3_row_lnbwd(GemmArgs g, RowLnBwdArgs ln) {
+    constexpr int MAXH = RLN_J / 64, PR = 2;
+    // the row width as ln_act_bwd sees it, a run-time value: with a constant the column guards fold and the
+    // compiler contracts lnb_row's guarded products into other FMAs than the stand-alone kernel's
+    const int H = g.J;
+    static_assert(4 * 3 * RLN_J * 4 <= RLN_LDS, "the wave partials must fit the dA stage");
+    __shared__ __attribute__((aligned(16))) unsigned char smem[RLN_LDS];
+    float* zs = reinterpret_cast<float*>(smem);                        // epilogue: [32][RLN_ZP]
+    auto red = reinterpret_cast<float (*)[3][RLN_J]>(smem);            // then the waves' partials [4][3][RLN_J]
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int i0 = blockIdx.x * RLN_BM;
+    const int l32 = lane & 31, hh = lane >> 5;
+    f32x16 acc[2][4];
+    const int pa = h3_row_kloop(g, smem, acc);
+    float csc[4];
+#pragma unroll
+    for (int tj = 0; tj < 4; tj++) csc[tj] = g.bscale[w * 128 + tj * 32 + l32];
+    uint32_t vmax = 0;
+#pragma unroll
+    for (int ti = 0; ti < 2; ti++) {
+        const int r0 = i0 + ti * 32;
+        if (ti) {
+            if (r0 >= g.I) break;  // no row in this half: no partial block
+            __syncthreads();       // the first half's partials are summed
+        }
+#pragma unroll
+        for (int tj = 0; tj < 4; tj++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float v = acc[ti][tj][r] + 0.f;  // gemm_x6's sum with its (zero) correction accumulator
+                zs[((r & 3) + 8 * (r >> 2) + 4 * hh) * RLN_ZP + w * 128 + tj * 32 + l32] = ldexpf(v * csc[tj], -pa) + 0.f;
+            }
+        __syncthreads();
+        float lg[MAXH], lb[MAXH], pg[MAXH], pb[MAXH], pz[MAXH], ph[MAXH];
+        float phb = 0.f;
+        lnf_affine<MAXH>(ln.gamma, ln.beta, H, ln.use_ln, lane, lg, lb);
+#pragma unroll
+        for (int q = 0; q < MAXH; q++) pg[q] = pb[q] = pz[q] = ph[q] = 0.f;
+        for (int rr = w; rr < 32; rr += 4 * PR) {
+            float xs[PR][MAXH], as[PR][MAXH];
+            float2 sts[PR];
+#pragma unroll
+            for (int j = 0; j < PR; j++) {
+                const int row = r0 + rr + 4 * j;
+                const int rw = row < g.I ? row : g.I - 1;  // a valid row (its values are not used)
+                const float* xh = ln.z + (int64_t)rw * H;
+                sts[j] = ln.stats[rw];
+#pragma unroll
+                for (int q = 0; q < MAXH; q += 4) {
+                    const int c = lcol<MAXH>(lane, q);
+                    const float4 x = *reinterpret_cast<const float4*>(xh + c);
+                    const float4 u = *reinterpret_cast<const float4*>(zs + (rr + 4 * j) * RLN_ZP + c);
+                    xs[j][q] = x.x; xs[j][q + 1] = x.y; xs[j][q + 2] = x.z; xs[j][q + 3] = x.w;
+                    as[j][q] = u.x; as[j][q + 1] = u.y; as[j][q + 2] = u.z; as[j][q + 3] = u.w;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < PR; j++) {
+                const int row = r0 + rr + 4 * j;
+                if (row >= g.I) break;
+                lnb_row<MAXH, false>(xs[j], as[j], sts[j], 0.f, lg, lb, ln.slope, ln.use_ln, H, true, lane,
+                                     ln.dz + (int64_t)row * H, pz, pg, pb, ph, phb, vmax);
+            }
+        }
+        __syncthreads();  // the half's rows are consumed: the stage becomes red
+#pragma unroll
+        for (int q = 0; q < MAXH; q += 4) {
+            const int c = lcol<MAXH>(lane, q);
+            *reinterpret_cast<float4*>(&red[w][0][c]) = make_float4(pz[q], pz[q + 1], pz[q + 2], pz[q + 3]);
+            *reinterpret_cast<float4*>(&red[w][1][c]) = make_float4(pg[q], pg[q + 1], pg[q + 2], pg[q + 3]);
+            *reinterpret_cast<float4*>(&red[w][2][c]) = make_float4(pb[q], pb[q + 1], pb[q + 2], pb[q + 3]);
+        }
+        __syncthreads();
+        float* out = ln.part + (int64_t)(2 * blockIdx.x + ti) * 3 * H;
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+#pragma unroll
+            for (int c = t; c < H; c += 256) out[k * H + c] = red[0][k][c] + red[1][k][c] + red[2][k][c] + red[3][k][c];
+    }
+    if (ln.amax) h3_amax_commit(ln.amax, vmax);
 }
 
 // Wide rows (H > 512, H % 4 == 0; C5's 2048): the wave-per-row kernels above hold a whole row per lane set

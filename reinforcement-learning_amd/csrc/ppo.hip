@@ -35,6 +35,7 @@ struct Layer {
     int sf_rows = 0, sf_ld = 0, sb_rows = 0, sb_ld = 0;
     int64_t sfs = -1, sbs = -1;  // H3: per-row inverse scales of the planes (offsets into Model::wscale)
     int64_t sq = -1;  // H3, hidden layers of mlp::RLN_J columns: the forward planes in fragment order (mlp::frag_weight_h3)
+    int64_t sqb = -1;  // H3, layers of mlp::RLN_J inputs above a hidden layer: the backward planes in fragment order
 };
 
 struct Model {
@@ -100,6 +101,20 @@ inline bool h3_rowfuse(int J) {
     }();
     if (J != mlp::RLN_J) return false;
     return mode == 1 ? true : (mode == 0 ? false : kRowFuseDefault);
+}
+// Input-gradient GEMMs of backward on the full-row kernel mlp::gemm_h3_row_lnbwd (the H3 dA GEMM of a layer with
+// the LayerNorm + LeakyReLU backward of the hidden layer below it in the same launch; dA is never stored; same
+// bits as gemm_x6 + ln_act_bwd<8>).  Eligible: a layer of exactly 512 inputs (mlp::RLN_J) above a hidden layer;
+// everything else keeps the two-kernel path.  RLGPU_H3_ROWFUSE_BWD=0: never, 1: every eligible layer; unset: on
+// (C2 minibatch 1.49 -> 1.36 ms, learn phase 122.1 -> 110.8 ms per iteration against the two-kernel path,
+// profiles/r08a_rowfuse_bwd_bench_pairs.txt).  Independent of RLGPU_H3_ROWFUSE.
+constexpr bool kRowFuseBwdDefault = true;
+inline bool h3_rowfuse_bwd() {
+    static const int mode = [] {
+        const char* e = getenv("RLGPU_H3_ROWFUSE_BWD");
+        return e ? atoi(e) : -1;
+    }();
+    return mode == 1 ? true : (mode == 0 ? false : kRowFuseBwdDefault);
 }
 inline bool split_mode_(int mode) { return mode == RLGPU_GEMM_F32X6 || mode == RLGPU_GEMM_F16X3; }
 inline int gemm_slots(int mode) {
@@ -358,6 +373,10 @@ void split_weights(const float* P, Model& m, hipStream_t s) {
             if (L.sb >= 0)
                 hipLaunchKernelGGL(mlp::split_weight_h3, dim3(L.sb_rows), dim3(256), 0, s, P + L.w, L.out, L.in, (int64_t)L.in, 1, L.sb_ld,
                                    m.wsplit + L.sb, (int64_t)L.sb_rows * L.sb_ld, m.wscale + L.sbs);
+            // the backward planes are [in rows][out as k]: the forward planes' shape, the same reordering
+            if (L.sqb >= 0 && h3_rowfuse_bwd())
+                hipLaunchKernelGGL(mlp::frag_weight_h3, dim3(L.sb_ld / 16 * (mlp::RLN_J / 32) * 2 * 64 / 256), dim3(256), 0, s,
+                                   m.wsplit + L.sb, (int64_t)L.sb_rows * L.sb_ld, L.sb_ld, m.wsplit + L.sqb);
         }
         RLGPU_CHECK_HIP(hipGetLastError());
         return;
@@ -610,6 +629,39 @@ void forward_train(rlgpu_ppo* h, int mi, const Input& x, int n, float* out, hipS
                  false, in_amax);
 }
 
+// The input gradient of layer l (dA = A . W_l, A = the layer's dZ or the loss gradient: n rows of lda floats,
+// zero-padded to a multiple of 4 when a_tail_ok) and the LayerNorm backward of hidden layer l - 1 in one launch
+// of mlp::gemm_h3_row_lnbwd: writes that layer's dZ to dz_out (not A), its column partials to m.cpart_l[l - 1]
+// and max |dZ| to its slot; dA is not stored.  False (nothing launched) when the pair is not eligible.
+bool dA_ln_bwd_fused(rlgpu_ppo* h, Model& m, int l, const float* A, int64_t lda, bool a_tail_ok, const float* amax_a, int n,
+                     float* dz_out, hipStream_t s) {
+    if (m.mode != RLGPU_GEMM_F16X3 || l < 1 || !h3_rowfuse_bwd()) return false;
+    const Layer& L = m.L[l];
+    const Layer& C = m.L[l - 1];  // the consumer: a hidden layer on ln_act_bwd<8>, never the rank-1 head's variant
+    if (L.sb < 0 || L.sqb < 0 || L.in != mlp::RLN_J || C.out != mlp::RLN_J) return false;
+    const bool av = (lda % 4 == 0) && ((uintptr_t)A % 16 == 0) && (L.out % 4 == 0 || a_tail_ok);  // gemm_x6_pre's float4 test
+    if (!av) return false;
+    if (!amax_a) throw rlgpu::Error(RLGPU_ERR_STATE, "H3 GEMM without operand scales");
+    const float* P = h->params;
+    ktime::Span span(ktime::FWD_GEMM, 2.0 * n * L.in * L.out, s);
+    mlp::GemmArgs g{};
+    g.A = A;
+    g.B = reinterpret_cast<const float*>(m.wsplit + L.sqb);
+    g.lda = lda;
+    g.ldb = L.sb_ld;
+    g.I = n;
+    g.J = L.in;
+    g.K = L.out;
+    g.amax_a = amax_a;
+    g.bscale = wscale_at(m, L.sbs);
+    const mlp::RowLnBwdArgs ln{C.g >= 0 ? P + C.g : nullptr, C.be >= 0 ? P + C.be : nullptr, h->cfg.leaky_slope, h->cfg.layer_norm,
+                               m.xhat[l - 1], reinterpret_cast<const float2*>(m.rstd[l - 1]), dz_out, m.cpart_l[l - 1],
+                               amax_slot(m, kAmaxDZ + l - 1)};
+    hipLaunchKernelGGL(mlp::gemm_h3_row_lnbwd, dim3(ceil_div(n, mlp::RLN_BM)), dim3(256), 0, s, g, ln);
+    RLGPU_CHECK_HIP(hipGetLastError());
+    return true;
+}
+
 // backward of model mi (input x) from dout into the grad buffer (accumulating).  dout: the loss
 // gradient [n, out] of the output layer, or -- the shared head -- the gradient of its last
 // activation [n, H].  dout_part: optional per-block column partials of dout (dout_nblk rows of `out`
@@ -624,6 +676,9 @@ void backward(rlgpu_ppo* h, int mi, const Input& x, int n, const float* dout, hi
     const int nh = nhid(m);
     const float* dA_top = m.dA;  // gradient of the last hidden layer's activation
     bool rank1 = false;          // rank-1 output layer folded into the last LayerNorm backward
+    // the next layer's dZ when the launch above it already ran its LayerNorm backward (dA_ln_bwd_fused); those
+    // launches alternate between m.dZ and m.dA, which no dA occupies on a fused layer, so none runs in place
+    float* fused_dz = nullptr;
     // the pass's bias / LayerNorm / weight-gradient reductions, launched together at its end
     Reducer red;
     red.m = &m;
@@ -661,7 +716,9 @@ void backward(rlgpu_ppo* h, int mi, const Input& x, int n, const float* dout, hi
             throw rlgpu::Error(RLGPU_ERR_STATE, "backward: padded dout needs the loss kernel's bias partials");
         // dA = dout . W_out (into the input gradient when the output layer reads the model input)
         float* dA = nh > 0 ? m.dA : m.dX;
-        if (dA) {
+        if (nh > 0 && dA_ln_bwd_fused(h, m, nh, dout, dld, dld > O->out, amax_slot(m, kAmaxOut), n, m.dZ, s)) {
+            fused_dz = m.dZ;
+        } else if (dA) {
             if (O->sb >= 0)
                 gemm_x6_pre(dout, dld, m.wsplit + O->sb, O->sb_ld, (int64_t)O->sb_rows * O->sb_ld, dA, O->in, nullptr, n, O->in,
                             O->out, s, dld > O->out, amax_slot(m, kAmaxOut), wscale_at(m, O->sbs));
@@ -670,6 +727,7 @@ void backward(rlgpu_ppo* h, int mi, const Input& x, int n, const float* dout, hi
                          dld > O->out, false, amax_slot(m, kAmaxOut), nullptr);
         }
     }
+    const float* dA_in = dA_top;  // the gradient of the current layer's activation, unless fused_dz
     for (int l = nh - 1; l >= 0; l--) {
         const Layer& L = m.L[l];
         const float* gg = L.g >= 0 ? P + L.g : nullptr;
@@ -677,15 +735,15 @@ void backward(rlgpu_ppo* h, int mi, const Input& x, int n, const float* dout, hi
         const bool r1 = rank1 && l == nh - 1;  // dA of the rank-1 head, recomputed in the kernel
         int lnb_rows = 0;
         const auto lnb = mlp::ln_act_bwd_pick(L.out, r1, &lnb_rows);
-        const float* dA_in = l == nh - 1 ? dA_top : m.dA;
-        float* dz = m.dZ;  // this layer's dZ
+        // this layer's dZ: never the buffer its dA is in
+        float* dz = fused_dz ? fused_dz : (dA_in == m.dZ ? m.dA : m.dZ);
         const int nb = (int)ceil_div(n, lnb_rows);
-        {
+        if (!fused_dz) {
             // bytes: dA (recomputed for the rank-1 head: its dv instead), z, stats read; dZ written
             ktime::Span span(ktime::LN_BWD, (double)n * ((r1 ? 4.0 : 4.0 * L.out) + 8.0 * L.out + 8.0), s);
             hipLaunchKernelGGL(lnb, dim3(nb), dim3(256), 0, s, r1 ? nullptr : dA_in, m.xhat[l],
                                reinterpret_cast<const float2*>(m.rstd[l]), gg, bb, n, L.out, h->cfg.leaky_slope,
-                               h->cfg.layer_norm, m.dZ, m.cpart_l[l], amax_slot(m, kAmaxDZ + l), r1 ? dout : nullptr,
+                               h->cfg.layer_norm, dz, m.cpart_l[l], amax_slot(m, kAmaxDZ + l), r1 ? dout : nullptr,
                                r1 ? P + O->w : nullptr, r1 ? m.hpart : nullptr);
             RLGPU_CHECK_HIP(hipGetLastError());
         }
@@ -697,8 +755,15 @@ void backward(rlgpu_ppo* h, int mi, const Input& x, int n, const float* dout, hi
         const Input a = l > 0 ? Input{m.act[l - 1], L.in, amax_slot(m, l - 1), false} : x;
         weight_grad(m, dz, L.out, a.X, a.ld, L.in, n, G + L.w, s, a.tail_ok, amax_slot(m, kAmaxDZ + l), a.amax, 0, R,
                     m.wpart_l[l]);
-        float* dA = l > 0 ? m.dA : m.dX;  // the first layer's only when the input gradient is wanted
+        float* other = dz == m.dZ ? m.dA : m.dZ;  // free: takes this layer's dA, or the next layer's dZ
+        float* dA = l > 0 ? other : m.dX;         // the first layer's only when the input gradient is wanted
+        fused_dz = nullptr;
         if (!dA) continue;
+        if (dA_ln_bwd_fused(h, m, l, dz, L.out, false, amax_slot(m, kAmaxDZ + l), n, other, s)) {
+            fused_dz = other;
+            continue;
+        }
+        dA_in = dA;
         if (L.sb >= 0)
             gemm_x6_pre(dz, L.out, m.wsplit + L.sb, L.sb_ld, (int64_t)L.sb_rows * L.sb_ld, dA, L.in, nullptr, n, L.in,
                         L.out, s, false, amax_slot(m, kAmaxDZ + l), wscale_at(m, L.sbs));
@@ -906,6 +971,11 @@ void build_model(rlgpu_ppo* h, Model& m, int in, const int32_t* layers, int nl, 
                 m.nsplit += np * (int64_t)L.sb_rows * L.sb_ld;
                 L.sbs = m.nscale;
                 m.nscale += L.sb_rows;
+                // a hidden layer below consumes this layer's dA (the first layer's goes to the model input)
+                if (m.mode == RLGPU_GEMM_F16X3 && l > 0 && L.in == mlp::RLN_J) {
+                    L.sqb = m.nsplit;
+                    m.nsplit += 2 * (int64_t)mlp::RLN_J * L.sb_ld;
+                }
             }
         }
         m.L.push_back(L);
