@@ -9,7 +9,7 @@
 //                    optional row gather idx[k])
 // fp32 path: v_mfma_f32_32x32x2_f32 (exact f32 products, f32 accumulate) -- training.
 // bf16 path: v_mfma_f32_32x32x16_bf16 (fp32 accumulate, bf16 output) -- inference.
-// Split-K (grid.z) writes per-split partial tiles; reduce_splits() sums them in a fixed
+// Split-K (grid.z) writes per-split partial tiles; reduce_batch() sums them in a fixed
 // order, so every result is deterministic run to run.
 #pragma once
 #include <hip/hip_bf16.h>
@@ -1170,35 +1170,6 @@ __global__ void __launch_bounds__(256) gather_rows(const float* src, int C, cons
     if (amax) h3_amax_commit(amax, m);
 }
 
-__global__ void reduce_splits(const float* part, int splits, int64_t stride, int64_t n, float* out, int accumulate) {
-    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    float s = 0.f;
-    for (int k = 0; k < splits; k++) s += part[k * stride + e];
-    out[e] = accumulate ? out[e] + s : s;
-}
-// the same sums, 4 columns per thread (n, stride multiples of 4, 16-byte aligned pointers); the
-// split loop is unrolled so several partial loads are in flight
-__global__ void reduce_splits4(const float* part, int splits, int64_t stride, int64_t n, float* out, int accumulate) {
-    int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (e >= n) return;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 4
-    for (int k = 0; k < splits; k++) {
-        float4 v = *reinterpret_cast<const float4*>(part + k * stride + e);
-        s.x += v.x;
-        s.y += v.y;
-        s.z += v.z;
-        s.w += v.w;
-    }
-    float4* o = reinterpret_cast<float4*>(out + e);
-    if (accumulate) {
-        float4 v = *o;
-        s = make_float4(v.x + s.x, v.y + s.y, v.z + s.z, v.w + s.w);
-    }
-    *o = s;
-}
-
 // ---------------------------------------------------------------- wave helpers
 DEV float wave_sum(float v) {
 #pragma unroll
@@ -1265,9 +1236,8 @@ DEV int lcol(int lane, int q) {
 // registers.  Each wave walks LNF_ROWS/4 rows, lnf_rf<MAXH>() of them at a time: their loads are
 // issued together before the first reduction and their wave reductions interleave, so a wave keeps
 // that many rows of HBM traffic in flight (the per-row arithmetic and its order are unchanged).
-// The rank-1 head (critic value) of one row already in registers, lcol layout: the arithmetic of
-// head1_fwd (same per-lane order, same reduction), so fusing it into the LayerNorm forward that
-// produces the row changes no bit; lane 0 writes *out.
+// The rank-1 head (critic value) of one row already in registers, lcol layout: a wave-per-row dot product
+// (each lane's columns in order, then wave_sum, then the bias); lane 0 writes *out.
 template <int MAXH>
 DEV void head1_row(const float (&x)[MAXH], const float* w, const float* b, int H, bool vec, int lane, float* out) {
     float s = 0.f;
@@ -1692,7 +1662,7 @@ DEV void lnb_row(float (&x)[MAXH], const float (&av)[MAXH], const float2 st, flo
         s1 += gg;
         s2 += gg * x[q];
         // the rank-1 head's weight gradient dv * act, act recomputed as the forward made it
-        // (head1_bwd's per-lane sums in its row order: the same bits)
+        // (per-lane sums over the wave's rows in row order)
         if (HEAD && lcol<MAXH>(lane, q) < H) ph[q] += dv * (h > 0.f ? h : h * slope);
     }
     if (HEAD) phb += dv;
@@ -1787,7 +1757,7 @@ __global__ void __launch_bounds__(256) ln_act_bwd(const float* dA, const float* 
                     if (dA) as[j][q] = in ? da[c] : 0.f;
                 }
             }
-            if (!dA) {  // rank-1 head: dA[row, c] = dv[row] * w[c], the product head1_bwd would have stored
+            if (!dA) {  // rank-1 head: dA[row, c] = dv[row] * w[c], never stored
                 const float dv = head_dv[rw];
                 dvs[j] = dv;
 #pragma unroll
@@ -1820,7 +1790,7 @@ __global__ void __launch_bounds__(256) ln_act_bwd(const float* dA, const float* 
     for (int k = 0; k < 3; k++)
         for (int c = threadIdx.x; c < H; c += 256)
             out[k * H + c] = red[0][k][c] + red[1][k][c] + red[2][k][c] + red[3][k][c];
-    if (HEAD) {  // [blk][w | b], head1_bwd's layout and order
+    if (HEAD) {  // [blk][w | b]: the four waves' sums in wave order
         float* ho = head_part + (int64_t)blockIdx.x * (H + 1);
         for (int c = threadIdx.x; c < H; c += 256) ho[c] = hred[0][c] + hred[1][c] + hred[2][c] + hred[3][c];
         if (threadIdx.x == 0)
@@ -2196,119 +2166,10 @@ inline decltype(&ln_act_bwd<8>) ln_act_bwd_pick(int H, bool head, int* rows) {
     return head ? ln_act_bwd_head_any(H) : ln_act_bwd_any(H);
 }
 
-// Rank-1 output layer (the critic's Linear(H, 1)): GEMM tiles would be 1/128 occupied, so the
-// head runs as wave-per-row dot products.  Columns per lane: lcol (float4 loads when H is a
-// multiple of 4); w stays in registers and each wave walks H1_ROWS/4 rows.
-constexpr int H1_ROWS = 16;
-template <int MAXH>
-__global__ void __launch_bounds__(256) head1_fwd(const float* X, const float* w, const float* b, int R, int H, float* out) {
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const bool vec = (H % 4 == 0) && (MAXH % 4 == 0);
-    float wr[MAXH];
-#pragma unroll
-    for (int q = 0; q < MAXH; q++) {
-        const int c = lcol<MAXH>(lane, q);
-        wr[q] = c < H ? w[c] : 0.f;
-    }
-    const float bias = b[0];
-    for (int i = 0; i < H1_ROWS / 4; i++) {
-        const int row = blockIdx.x * H1_ROWS + i * 4 + wv;
-        if (row >= R) break;
-        const float* x = X + (int64_t)row * H;
-        float s = 0.f;
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < MAXH; q += 4) {
-                const int c = lcol<MAXH>(lane, q);
-                if (c < H) {
-                    float4 t = *reinterpret_cast<const float4*>(x + c);
-                    s += t.x * wr[q] + t.y * wr[q + 1] + t.z * wr[q + 2] + t.w * wr[q + 3];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < MAXH; q++) {
-                const int c = lcol<MAXH>(lane, q);
-                if (c < H) s += x[c] * wr[q];
-            }
-        }
-        s = wave_sum(s);
-        if (lane == 0) out[row] = s + bias;
-    }
-}
-
-// Backward of the rank-1 head: dA[i, :] = dv[i] * w; partials part[blk][0..H) = sum dv*X[i, :],
-// part[blk][H] = sum dv (bias) over the block's rows.  Same lane layout as head1_fwd.
-template <int MAXH>
-__global__ void __launch_bounds__(256) head1_bwd(const float* X, const float* w, const float* dv, int R, int H, float* dA,
-                                                float* part) {
-    __shared__ float red[4][64 * MAXH + 1];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const bool vec = (H % 4 == 0) && (MAXH % 4 == 0);
-    float wr[MAXH], acc[MAXH];
-    float accb = 0.f;
-#pragma unroll
-    for (int q = 0; q < MAXH; q++) {
-        const int c = lcol<MAXH>(lane, q);
-        wr[q] = c < H ? w[c] : 0.f;
-        acc[q] = 0.f;
-    }
-    const int r0 = blockIdx.x * LNB_ROWS;
-    for (int rr = wv; rr < LNB_ROWS; rr += 4) {
-        const int row = r0 + rr;
-        if (row >= R) break;
-        const float d = dv[row];
-        const float* x = X + (int64_t)row * H;
-        float* da = dA ? dA + (int64_t)row * H : nullptr;  // null: the LayerNorm backward recomputes dA
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < MAXH; q += 4) {
-                const int c = lcol<MAXH>(lane, q);
-                if (c < H) {
-                    float4 t = *reinterpret_cast<const float4*>(x + c);
-                    if (dA) *reinterpret_cast<float4*>(da + c) = make_float4(d * wr[q], d * wr[q + 1], d * wr[q + 2], d * wr[q + 3]);
-                    acc[q] += d * t.x;
-                    acc[q + 1] += d * t.y;
-                    acc[q + 2] += d * t.z;
-                    acc[q + 3] += d * t.w;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < MAXH; q++) {
-                const int c = lcol<MAXH>(lane, q);
-                if (c < H) {
-                    if (dA) da[c] = d * wr[q];
-                    acc[q] += d * x[c];
-                }
-            }
-        }
-        accb += d;
-    }
-#pragma unroll
-    for (int q = 0; q < MAXH; q++) red[wv][lcol<MAXH>(lane, q)] = acc[q];
-    if (lane == 0) red[wv][64 * MAXH] = accb;
-    __syncthreads();
-    float* out = part + (int64_t)blockIdx.x * (H + 1);
-    for (int c = threadIdx.x; c < H; c += 256) out[c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
-    if (threadIdx.x == 0) out[H] = red[0][64 * MAXH] + red[1][64 * MAXH] + red[2][64 * MAXH] + red[3][64 * MAXH];
-}
-RLGPU_NPER_DISPATCH(head1_fwd)
-RLGPU_NPER_DISPATCH(head1_bwd)
-
-// Per-block column partial sums of X [R, Cn] (Cn <= 1024): part[blk][Cn].
-constexpr int CS_ROWS = 256;
-__global__ void __launch_bounds__(256) colsum_partial(const float* X, int R, int Cn, float* part) {
-    int r0 = blockIdx.x * CS_ROWS;
-    for (int c = threadIdx.x; c < Cn; c += 256) {
-        float s = 0.f;
-        for (int r = r0; r < min(R, r0 + CS_ROWS); r++) s += X[(int64_t)r * Cn + c];
-        part[(int64_t)blockIdx.x * Cn + c] = s;
-    }
-}
-
-// The column sums of one tile of reduce_cols (block (x, y) of a G-group grid): the same loads in the same
-// order, so reduce_batch's column jobs give reduce_cols's bits.
+// One tile of a deterministic column reduction of per-block partials: tile (x, y) of a G-group grid sums the
+// partial rows b = y, y + G, ... of 64 columns -- 16 row groups of 64 threads, group gi taking every 16th of
+// those rows in order, combined in LDS in group order -- into out[y][c].  Eight partial rows are loaded before
+// they are added (in the order of a plain loop: the same bits), so a thread has eight loads in flight.
 DEV void reduce_cols_tile(const float* part, int nblk, int64_t stride, int n, int x, int y, int G, float* out,
                           int64_t out_stride, int accumulate, float (*red)[64]) {
     const int cl = threadIdx.x & 63, gi = threadIdx.x >> 6;
@@ -2341,9 +2202,10 @@ DEV void reduce_cols_tile(const float* part, int nblk, int64_t stride, int n, in
 // Every reduction of one backward pass in one launch per level (instead of one or two launches per
 // reduction).  Job k: dst[c] += sum over nblk partial rows (stride floats apart) of column c < n.
 //   vec = 1: split-K weight-gradient partials (few rows, many columns): 4 columns per thread, rows in
-//            order -- reduce_splits4's sums; vec = 2: one column per thread -- reduce_splits's.
-//   vec = 0: per-block column partials: reduce_cols's scheme, level 1 over G row groups into mid[y][c]
-//            (or straight into dst when G = 1), level 2 over mid's G rows into dst.
+//            order from a zero sum, then added to dst; vec = 2: the same sums, one column per thread.
+//   vec = 0: per-block column partials, two levels of reduce_cols_tile: level 1 (ceil(n / 64) x G tiles) over G
+//            row groups into mid[y][c] (or straight into dst when G = 1), level 2 (the same tile with G = 1 on
+//            mid's G rows) into dst.
 // Blocks of 1024 threads; b.tile0[k] = first block of job k at this level (a job with no tiles at a
 // level is skipped).  Same bits as the separate launches.
 constexpr int kRedJobs = 16;
@@ -2397,43 +2259,6 @@ __global__ void __launch_bounds__(1024) reduce_batch(RedBatch b) {
                          red);
     else
         reduce_cols_tile(J.mid, J.G, J.n, J.n, r, 0, 1, J.dst, 0, 1, red);
-}
-
-// Column reduction of per-block partials, deterministic, two levels:
-//   stage 1 (grid ceil(n/64) x G): block (x, y) sums partial rows b = y, y+G, ... of 64 columns
-//            (16 row groups of 64 threads, combined in LDS in a fixed order) -> out2[y][c]
-//   stage 2 (the same kernel with G = 1 on out2, accumulate = 1): grad[c] += sum_y out2[y][c]
-__global__ void __launch_bounds__(1024) reduce_cols(const float* part, int nblk, int64_t stride, int64_t off, int n,
-                                                   float* out, int64_t out_stride, int accumulate) {
-    __shared__ float red[16][64];
-    const int cl = threadIdx.x & 63, gi = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    const int G = gridDim.y, y = blockIdx.y;
-    float s = 0.f;
-    if (c < n) {
-        // eight partial rows loaded before they are added (in the same order as a plain loop: the
-        // same bits), so a thread has eight loads in flight instead of one
-        const int step = 16 * G;
-        for (int b = y + G * gi; b < nblk; b += 8 * step) {
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int bk = b + k * step;
-                v[k] = part[(int64_t)(bk < nblk ? bk : b) * stride + off + c];
-            }
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                if (b + k * step < nblk) s += v[k];
-        }
-    }
-    red[gi][cl] = s;
-    __syncthreads();
-    if (gi == 0 && c < n) {
-        float tot = 0.f;
-        for (int k = 0; k < 16; k++) tot += red[k][cl];
-        float* o = out + (int64_t)y * out_stride + c;
-        *o = accumulate ? *o + tot : tot;
-    }
 }
 
 }  // namespace mlp

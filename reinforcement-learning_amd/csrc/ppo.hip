@@ -4,6 +4,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rlgpu_ppo.h"
@@ -23,19 +24,26 @@ using rlgpu::ceil_div;
         else hipLaunchKernelGGL(KERN<false>, __VA_ARGS__);                                   \
     } while (0)
 
+// One side of a layer's pre-split weight: bf16 (x6, three) or fp16 (H3, two) planes of `rows` x `ld` elements,
+// rows padded to whole B tiles of the mode and ld to mlp::XKMAX, zero filled.  Offsets into Model::wsplit /
+// Model::wscale; -1 = none.
+struct Side {
+    int64_t planes = -1;
+    int rows = 0, ld = 0;
+    int64_t scale = -1;  // H3: per-row inverse scales of the planes
+    int64_t frag = -1;   // H3, mlp::RLN_J rows feeding a full-row kernel: the planes in fragment order (mlp::frag_weight_h3)
+    int64_t plane() const { return (int64_t)rows * ld; }  // elements per plane
+};
+
 struct Layer {
     int in, out;
     int64_t w, b, g, be;      // offsets into the flat fp32 buffers (g/be = -1 without LayerNorm)
     int in_pad;               // bf16 copy: weight rows padded to a multiple of 8 (16 bytes)
     int64_t hw, hb, hg, hbe;  // offsets into the padded bf16 inference copy
     int64_t fw = -1;          // offset into the fragment-major inference copy (infer::weight_to_frag)
-    // three-way bf16 split of the weight for the x6 training GEMMs (offsets into Model::wsplit):
-    // forward B = W [out_pad128][in_pad32], backward dA B = W^T [in_pad128][out_pad32]; -1 = none
-    int64_t sf = -1, sb = -1;
-    int sf_rows = 0, sf_ld = 0, sb_rows = 0, sb_ld = 0;
-    int64_t sfs = -1, sbs = -1;  // H3: per-row inverse scales of the planes (offsets into Model::wscale)
-    int64_t sq = -1;  // H3, hidden layers of mlp::RLN_J columns: the forward planes in fragment order (mlp::frag_weight_h3)
-    int64_t sqb = -1;  // H3, layers of mlp::RLN_J inputs above a hidden layer: the backward planes in fragment order
+    // the weight as B operand of the x6 / H3 training GEMMs (none for the rank-1 critic head, which has no GEMM):
+    // forward B = W [out_pad][in_pad], backward dA B = W^T [in_pad][out_pad]
+    Side fwd, bwd;
 };
 
 struct Model {
@@ -47,7 +55,7 @@ struct Model {
     int mode = 0;  // training GEMM arithmetic (rlgpu_ppo_config.train_gemm)
     // fp32 training workspace (per model, so the two models' passes can overlap on two streams)
     std::vector<float*> xhat, act, rstd;
-    float *y = nullptr, *dy = nullptr, *dA = nullptr, *dZ = nullptr, *wpart = nullptr, *cpart = nullptr, *mid = nullptr;  // y: model output
+    float *y = nullptr, *dy = nullptr, *dA = nullptr, *dZ = nullptr, *mid = nullptr;  // y: model output
     float* hpart = nullptr;  // rank-1 head dw / db partials, written by the last LayerNorm backward
     // per-layer partial buffers of the deferred reductions (so a backward pass reduces them all at its end):
     // split-K weight-gradient partials of layer l, LayerNorm-backward column partials of hidden layer l, and
@@ -73,6 +81,16 @@ constexpr int kMaxSplits = 256;
 // concurrent gemm_f32 workgroups on the device (CUs x RLGPU_GEMM_OCC), set at create: the split-K
 // weight gradients are sized to fill whole rounds of workgroups
 int g_cus = 256;  // compute units of the device, set at create
+
+// A three-way environment knob: 0 = never, 1 = always, unset (or anything else) = -1, the caller's default.
+// Callers keep the value in a function-local static, so each knob is read once per process.
+inline int tri_knob(const char* name) {
+    const char* e = getenv(name);
+    const int v = e ? atoi(e) : -1;
+    return v == 0 || v == 1 ? v : -1;
+}
+inline bool knob_or(int knob, bool dflt) { return knob < 0 ? dflt : knob == 1; }
+
 // Forward / input-gradient H3 GEMMs with output widths that are multiples of 256 on the 256 x 256 tile kernel
 // mlp::gemm_h3q, and weight gradients on mlp::gemm_h3qt (same bits as gemm_x6): by default for 1024 or
 // more output columns (the C5 leg's 2048-wide layers: 31.6 -> 27.6 ms per 50k minibatch against 128 x 256 tiles,
@@ -80,51 +98,44 @@ int g_cus = 256;  // compute units of the device, set at create
 // (K = 512, 16 stages per tile) its one workgroup per CU cannot hide the tile's prologue and epilogue and the
 // C2 minibatch takes 1.59 -> 1.70 ms.  RLGPU_H3_QUAD=0: never, 1: for every width that is a multiple of 256.
 inline bool h3_quad(int J) {
-    static const int mode = [] {
-        const char* e = getenv("RLGPU_H3_QUAD");
-        return e ? atoi(e) : -1;
-    }();
-    if (J % mlp::BQ != 0) return false;
-    return mode == 1 ? true : (mode == 0 ? false : J >= 1024);
+    static const int knob = tri_knob("RLGPU_H3_QUAD");
+    return J % mlp::BQ == 0 && knob_or(knob, J >= 1024);
 }
-// Hidden layers of forward_train on the full-row kernel mlp::gemm_h3_rowln (the H3 forward GEMM with its
+// Hidden layer L of forward_train on the full-row kernel mlp::gemm_h3_rowln (the H3 forward GEMM with its
 // LayerNorm + LeakyReLU in the same launch; same bits as gemm_x6 + ln_act_fwd_f32).  Eligible output width:
 // exactly 512 columns (mlp::RLN_J: the kernel's tile is the whole row, and its LayerNorm part is
 // ln_act_fwd_f32<8>'s column layout); every other width keeps the two-kernel path.  RLGPU_H3_ROWFUSE=0:
 // never, 1: every eligible layer; unset: on (C2 minibatch 1.57 -> 1.49 ms, learn phase 126.9 -> 120.2 ms per
 // iteration against the two-kernel path, profiles/r07a_rowfuse_bench_pairs.txt).
+// The one predicate behind both the launch (forward_train) and the fragment-order planes it reads
+// (split_weights); the launch also needs 16-byte loads of its A operand, else it falls back.
 constexpr bool kRowFuseDefault = true;
-inline bool h3_rowfuse(int J) {
-    static const int mode = [] {
-        const char* e = getenv("RLGPU_H3_ROWFUSE");
-        return e ? atoi(e) : -1;
-    }();
-    if (J != mlp::RLN_J) return false;
-    return mode == 1 ? true : (mode == 0 ? false : kRowFuseDefault);
+inline bool rowfuse_fwd(const Model& m, const Layer& L) {
+    static const int knob = tri_knob("RLGPU_H3_ROWFUSE");
+    return m.mode == RLGPU_GEMM_F16X3 && L.out == mlp::RLN_J && L.fwd.frag >= 0 && knob_or(knob, kRowFuseDefault);
 }
-// Input-gradient GEMMs of backward on the full-row kernel mlp::gemm_h3_row_lnbwd (the H3 dA GEMM of a layer with
+// The input-gradient GEMM of layer L on the full-row kernel mlp::gemm_h3_row_lnbwd (the H3 dA GEMM of a layer with
 // the LayerNorm + LeakyReLU backward of the hidden layer below it in the same launch; dA is never stored; same
-// bits as gemm_x6 + ln_act_bwd<8>).  Eligible: a layer of exactly 512 inputs (mlp::RLN_J) above a hidden layer;
-// everything else keeps the two-kernel path.  RLGPU_H3_ROWFUSE_BWD=0: never, 1: every eligible layer; unset: on
+// bits as gemm_x6 + ln_act_bwd<8>).  Eligible: a layer of exactly 512 inputs (mlp::RLN_J) above a hidden layer
+// (`below`; null for a model's first layer); everything else keeps the two-kernel path.
+// RLGPU_H3_ROWFUSE_BWD=0: never, 1: every eligible layer; unset: on
 // (C2 minibatch 1.49 -> 1.36 ms, learn phase 122.1 -> 110.8 ms per iteration against the two-kernel path,
 // profiles/r08a_rowfuse_bwd_bench_pairs.txt).  Independent of RLGPU_H3_ROWFUSE.
+// As above: the one predicate behind the launch (backward) and its planes (split_weights).
 constexpr bool kRowFuseBwdDefault = true;
-inline bool h3_rowfuse_bwd() {
-    static const int mode = [] {
-        const char* e = getenv("RLGPU_H3_ROWFUSE_BWD");
-        return e ? atoi(e) : -1;
-    }();
-    return mode == 1 ? true : (mode == 0 ? false : kRowFuseBwdDefault);
+inline bool rowfuse_bwd(const Model& m, const Layer& L, const Layer* below) {
+    static const int knob = tri_knob("RLGPU_H3_ROWFUSE_BWD");
+    return m.mode == RLGPU_GEMM_F16X3 && below && below->out == mlp::RLN_J && L.in == mlp::RLN_J && L.bwd.frag >= 0 &&
+           knob_or(knob, kRowFuseBwdDefault);
 }
-inline bool split_mode_(int mode) { return mode == RLGPU_GEMM_F32X6 || mode == RLGPU_GEMM_F16X3; }
 inline int gemm_slots(int mode) {
     // H3: 146 / 156 VGPRs (forward / weight-gradient instances), 40 KB LDS -> three workgroups per CU
     // (-Rpass-analysis=kernel-resource-usage: occupancy 3 waves / SIMD); x6: two
     if (mode == RLGPU_GEMM_F16X3) return g_cus * 3;
-    return g_cus * (split_mode_(mode) ? 2 : RLGPU_GEMM_OCC);
+    return g_cus * (split_mode(mode) ? 2 : RLGPU_GEMM_OCC);
 }
 // K granularity of a split-K chunk: a whole number of stages of either kernel
-inline int kgran(int mode) { return split_mode_(mode) ? mlp::XKMAX : mlp::BK; }
+inline int kgran(int mode) { return split_mode(mode) ? mlp::XKMAX : mlp::BK; }
 
 }  // namespace
 
@@ -229,168 +240,140 @@ struct Span {
 };
 }  // namespace ktime
 
-// C[I,J] (+ bias) = A . B with the layouts of mlp::gemm_f32.  *_tail_ok: the operand's rows are
-// zero-padded up to a multiple of 4 past the bound (so float4 loads may straddle it).
-template <int LA, int LB, bool AV, bool BV, bool PRE, bool H3>
-void x6_launch_v(dim3 grid, dim3 blk, hipStream_t s, const mlp::GemmArgs& g) {
-    hipLaunchKernelGGL((mlp::gemm_x6<LA, LB, AV, BV, PRE, H3>), grid, blk, 0, s, g);
-}
-template <int LA, int LB, bool H3>
-void x6_launch(bool av, bool bv, dim3 grid, dim3 blk, hipStream_t s, const mlp::GemmArgs& g) {
-    if (av && bv) x6_launch_v<LA, LB, true, true, false, H3>(grid, blk, s, g);
-    else if (av) x6_launch_v<LA, LB, true, false, false, H3>(grid, blk, s, g);
-    else if (bv) x6_launch_v<LA, LB, false, true, false, H3>(grid, blk, s, g);
-    else x6_launch_v<LA, LB, false, false, false, H3>(grid, blk, s, g);
+// An fp32 GEMM operand in memory: rows of ld floats, its H3 scale shards (64-shard max |x|; null outside H3), and
+// whether the rows are zero-padded up to a multiple of 4 past the bound (so 16-byte loads may straddle it).
+// Every A operand of the training passes is one: the gathered obs, act[l], dZ, the loss gradient.
+struct Operand {
+    const float* X;
+    int64_t ld;
+    const float* amax;
+    bool tail_ok;
+};
+// 16-byte loads of an operand: 16-byte aligned rows and a bound (K for k-contiguous rows, I / J otherwise) that
+// is a multiple of 4 or zero-padded past it (split-K chunk ends are multiples of BK)
+inline bool vec_ok(const Operand& x, int bound) {
+    return x.ld % 4 == 0 && (uintptr_t)x.X % 16 == 0 && (bound % 4 == 0 || x.tail_ok);
 }
 
-// amax_a / amax_b: the operands' 64-shard max |x| (RLGPU_GEMM_F16X3 only)
-void gemm_f32(int mode, int la, int lb, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
-              const float* bias, int I, int J, int K, int splits, hipStream_t s, bool a_tail_ok = false,
-              bool b_tail_ok = false, const float* amax_a = nullptr, const float* amax_b = nullptr) {
+// What every training GEMM launch shares: C[I, J] = A . B with A = a, B = fp32 (amax_b: its H3 shards) or pre-split
+// planes (bscale: their H3 per-row inverse scales), and the grid of tm x tn output tiles, one K split.  The
+// caller adds C / bias and its split-K or plane fields.  h3: the launch is on the fp16x3 arithmetic.
+mlp::GemmArgs gemm_args(bool h3, const Operand& a, const void* B, int64_t ldb, const float* amax_b, const float* bscale, int I,
+                        int J, int K, int tm, int tn) {
+    if (h3 && !(a.amax && (amax_b || bscale))) throw rlgpu::Error(RLGPU_ERR_STATE, "H3 GEMM without operand scales");
     mlp::GemmArgs g{};
-    g.amax_a = amax_a;
-    g.amax_b = amax_b;
-    if (mode == RLGPU_GEMM_F16X3 && !(amax_a && amax_b)) throw rlgpu::Error(RLGPU_ERR_STATE, "H3 GEMM without operand scales");
-    g.A = A;
-    g.B = B;
-    g.C = C;
-    g.bias = bias;
-    g.lda = lda;
+    g.A = a.X;
+    g.lda = a.ld;
+    g.amax_a = a.amax;
+    g.B = static_cast<const float*>(B);
     g.ldb = ldb;
-    g.ldc = ldc;
+    g.amax_b = amax_b;
+    g.bscale = bscale;
     g.I = I;
     g.J = J;
     g.K = K;
-    int chunk = (int)ceil_div(K, splits);
-    g.kchunk = (int)ceil_div(chunk, kgran(mode)) * kgran(mode);
-    int z = (int)ceil_div(K, g.kchunk);
-    g.c_split = (int64_t)I * ldc;
-    // float4 path: 16-byte aligned rows and a bound (K for k-contiguous, I / J otherwise) that is a
-    // multiple of 4 or zero-padded past it (split-K chunk ends are multiples of BK)
-    const int a_lim = la == mlp::A_IK ? K : I, b_lim = lb == mlp::B_JK ? K : J;
-    const bool av = (lda % 4 == 0) && ((uintptr_t)A % 16 == 0) && (a_lim % 4 == 0 || a_tail_ok);
-    const bool bv = (ldb % 4 == 0) && ((uintptr_t)B % 16 == 0) && (b_lim % 4 == 0 || b_tail_ok);
-    g.gx = (int)ceil_div(J, mlp::BN);
-    g.gy = (int)ceil_div(I, mlp::BM);
-    g.gz = z;
-    if (mode == RLGPU_GEMM_F16X3 && la == mlp::A_KI && lb == mlp::B_KJ && I % mlp::BQ == 0 && h3_quad(J)) {
-        // 256 x 256 tiles, the same split-K chunks (same bits as gemm_x6)
-        g.gx = J / mlp::BQ;
-        g.gy = I / mlp::BQ;
-        dim3 gridq(g.gx * g.gy * g.gz), blkq(512);
-        if (av && bv) hipLaunchKernelGGL((mlp::gemm_h3qt<true, true>), gridq, blkq, 0, s, g);
-        else if (av) hipLaunchKernelGGL((mlp::gemm_h3qt<true, false>), gridq, blkq, 0, s, g);
-        else if (bv) hipLaunchKernelGGL((mlp::gemm_h3qt<false, true>), gridq, blkq, 0, s, g);
-        else hipLaunchKernelGGL((mlp::gemm_h3qt<false, false>), gridq, blkq, 0, s, g);
-        RLGPU_CHECK_HIP(hipGetLastError());
-        return;
-    }
-    dim3 grid(g.gx * g.gy * g.gz), blk(256);
-#define RLGPU_GEMM_CASE(LA, LB)                                                                                  \
-    if (la == LA && lb == LB) {                                                                                  \
-        if (mode == RLGPU_GEMM_F32X6) {                                                                          \
-            x6_launch<LA, LB, false>(av, bv, grid, blk, s, g);                                                   \
-        } else if (mode == RLGPU_GEMM_F16X3) {                                                                   \
-            x6_launch<LA, LB, true>(av, bv, grid, blk, s, g);                                                    \
-        } else {                                                                                                 \
-            if (av && bv) hipLaunchKernelGGL((mlp::gemm_f32<LA, LB, true, true>), grid, blk, 0, s, g);           \
-            else if (av) hipLaunchKernelGGL((mlp::gemm_f32<LA, LB, true, false>), grid, blk, 0, s, g);          \
-            else if (bv) hipLaunchKernelGGL((mlp::gemm_f32<LA, LB, false, true>), grid, blk, 0, s, g);          \
-            else hipLaunchKernelGGL((mlp::gemm_f32<LA, LB, false, false>), grid, blk, 0, s, g);                 \
-        }                                                                                                        \
-        RLGPU_CHECK_HIP(hipGetLastError());                                                                      \
-        return;                                                                                                  \
-    }
-    RLGPU_GEMM_CASE(mlp::A_IK, mlp::B_JK)
-    RLGPU_GEMM_CASE(mlp::A_IK, mlp::B_KJ)
-    RLGPU_GEMM_CASE(mlp::A_KI, mlp::B_KJ)
-#undef RLGPU_GEMM_CASE
-    throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "gemm layout");
+    g.gx = (int)ceil_div(J, tn);
+    g.gy = (int)ceil_div(I, tm);
+    g.gz = 1;
+    return g;
+}
+// one workgroup per tile of g's grid
+template <class... P>
+void launch_gemm(void (*kernel)(mlp::GemmArgs, P...), int threads, hipStream_t s, const mlp::GemmArgs& g, const P&... more) {
+    hipLaunchKernelGGL(kernel, dim3(g.gx * g.gy * g.gz), dim3(threads), 0, s, g, more...);
+    RLGPU_CHECK_HIP(hipGetLastError());
+}
+// f(std::bool_constant<a>, std::bool_constant<b>): two run-time flags as template arguments of one launch expression
+template <class F>
+void with_flags(bool a, bool b, F&& f) {
+    if (a && b) f(std::true_type{}, std::true_type{});
+    else if (a) f(std::true_type{}, std::false_type{});
+    else if (b) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+}
+// the same for the operand layouts of mlp::gemm_f32
+template <class F>
+void with_layouts(int la, int lb, F&& f) {
+    using IK = std::integral_constant<int, mlp::A_IK>;
+    using KI = std::integral_constant<int, mlp::A_KI>;
+    using JK = std::integral_constant<int, mlp::B_JK>;
+    using KJ = std::integral_constant<int, mlp::B_KJ>;
+    if (la == mlp::A_IK && lb == mlp::B_JK) f(IK{}, JK{});
+    else if (la == mlp::A_IK && lb == mlp::B_KJ) f(IK{}, KJ{});
+    else if (la == mlp::A_KI && lb == mlp::B_KJ) f(KI{}, KJ{});
+    else throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "gemm layout");
 }
 
-// C[I,J] (+ bias) = A . B on the x6 GEMM with B given as pre-split planes (Layer::sf / sb layout)
-// H3 (bscale given): fp16 planes with per-row inverse scales bscale, A scaled by amax_a's shards
-void gemm_x6_pre(const float* A, int64_t lda, const uint16_t* Bp, int ldbp, int64_t bplane, float* C, int64_t ldc,
-                 const float* bias, int I, int J, int K, hipStream_t s, bool a_tail_ok = false,
-                 const float* amax_a = nullptr, const float* bscale = nullptr) {
-    ktime::Span span(ktime::FWD_GEMM, 2.0 * I * J * K, s);
-    mlp::GemmArgs g{};
-    g.amax_a = amax_a;
-    g.bscale = bscale;
-    const bool h3 = bscale != nullptr;
-    if (h3 && !amax_a) throw rlgpu::Error(RLGPU_ERR_STATE, "H3 GEMM without operand scales");
-    g.A = A;
-    g.B = reinterpret_cast<const float*>(Bp);
+// C[I,J] (+ bias) = A . B with the layouts of mlp::gemm_f32, both operands fp32 in memory, K in `splits` chunks
+// (partial k of I x ldc floats at C + k I ldc)
+void gemm_f32(int mode, int la, int lb, const Operand& a, const Operand& b, float* C, int64_t ldc, const float* bias, int I, int J,
+              int K, int splits, hipStream_t s) {
+    const bool h3 = mode == RLGPU_GEMM_F16X3;
+    const bool av = vec_ok(a, la == mlp::A_IK ? K : I), bv = vec_ok(b, lb == mlp::B_JK ? K : J);
+    // H3 weight gradients: 256 x 256 tiles, the same split-K chunks (same bits as gemm_x6)
+    const bool quad = h3 && la == mlp::A_KI && lb == mlp::B_KJ && I % mlp::BQ == 0 && h3_quad(J);
+    mlp::GemmArgs g = gemm_args(h3, a, b.X, b.ld, b.amax, nullptr, I, J, K, quad ? mlp::BQ : mlp::BM, quad ? mlp::BQ : mlp::BN);
     g.C = C;
     g.bias = bias;
-    g.lda = lda;
-    g.ldb = ldbp;
     g.ldc = ldc;
-    g.I = I;
-    g.J = J;
-    g.K = K;
-    g.kchunk = (int)ceil_div(K, mlp::XKMAX) * mlp::XKMAX;
-    g.c_split = 0;
-    g.bplane = bplane;
-    g.gx = (int)ceil_div(J, mlp::BN);
-    g.gy = (int)ceil_div(I, mlp::BM);
-    g.gz = 1;
-    const bool av = (lda % 4 == 0) && ((uintptr_t)A % 16 == 0) && (K % 4 == 0 || a_tail_ok);
-    if (h3 && av && h3_quad(J)) {  // 256 x 256 tiles (bit-identical to gemm_x6's H3 path)
-        g.gx = J / mlp::BQ;
-        g.gy = (int)ceil_div(I, mlp::BQ);
-        hipLaunchKernelGGL((mlp::gemm_h3q<true>), dim3(g.gx * g.gy), dim3(512), 0, s, g);
-        RLGPU_CHECK_HIP(hipGetLastError());
+    const int chunk = (int)ceil_div(K, splits);
+    g.kchunk = (int)ceil_div(chunk, kgran(mode)) * kgran(mode);
+    g.gz = (int)ceil_div(K, g.kchunk);
+    g.c_split = (int64_t)I * ldc;
+    if (quad) {
+        with_flags(av, bv, [&](auto AV, auto BV) { launch_gemm(mlp::gemm_h3qt<AV(), BV()>, 512, s, g); });
         return;
     }
-    dim3 grid(g.gx * g.gy), blk(256);
-    if (h3) {
-        if (av)
-            x6_launch_v<mlp::A_IK, mlp::B_JK, true, true, true, true>(grid, blk, s, g);
-        else
-            x6_launch_v<mlp::A_IK, mlp::B_JK, false, true, true, true>(grid, blk, s, g);
-    } else {
-        if (av)
-            x6_launch_v<mlp::A_IK, mlp::B_JK, true, true, true, false>(grid, blk, s, g);
-        else
-            x6_launch_v<mlp::A_IK, mlp::B_JK, false, true, true, false>(grid, blk, s, g);
-    }
-    RLGPU_CHECK_HIP(hipGetLastError());
+    with_layouts(la, lb, [&](auto LA, auto LB) {
+        with_flags(av, bv, [&](auto AV, auto BV) {
+            if (mode == RLGPU_GEMM_F32X6) launch_gemm(mlp::gemm_x6<LA(), LB(), AV(), BV(), false, false>, 256, s, g);
+            else if (h3) launch_gemm(mlp::gemm_x6<LA(), LB(), AV(), BV(), false, true>, 256, s, g);
+            else launch_gemm(mlp::gemm_f32<LA(), LB(), AV(), BV()>, 256, s, g);
+        });
+    });
+}
+
+// C[I,J] (+ bias) = A . B on the x6 GEMM with B given as pre-split planes (a Side's layout: [J_pad][ldbp] k contiguous,
+// bplane elements apart).  H3 (bscale given): fp16 planes with per-row inverse scales bscale, A scaled by its shards
+void gemm_x6_pre(const Operand& a, const uint16_t* Bp, int ldbp, int64_t bplane, const float* bscale, float* C, int64_t ldc,
+                 const float* bias, int I, int J, int K, hipStream_t s) {
+    ktime::Span span(ktime::FWD_GEMM, 2.0 * I * J * K, s);
+    const bool h3 = bscale != nullptr;
+    const bool av = vec_ok(a, K);
+    const bool quad = h3 && av && h3_quad(J);  // 256 x 256 tiles (bit-identical to gemm_x6's H3 path)
+    mlp::GemmArgs g = gemm_args(h3, a, Bp, ldbp, nullptr, bscale, I, J, K, quad ? mlp::BQ : mlp::BM, quad ? mlp::BQ : mlp::BN);
+    g.C = C;
+    g.bias = bias;
+    g.ldc = ldc;
+    g.kchunk = (int)ceil_div(K, mlp::XKMAX) * mlp::XKMAX;
+    g.bplane = bplane;
+    if (quad) return launch_gemm(mlp::gemm_h3q<true>, 512, s, g);
+    with_flags(av, h3, [&](auto AV, auto H3) { launch_gemm(mlp::gemm_x6<mlp::A_IK, mlp::B_JK, AV(), true, true, H3()>, 256, s, g); });
 }
 
 // refresh the split weight planes of model m from the current parameters (once per minibatch /
 // training forward: the weights change only at the optimizer step, but may be written directly)
 void split_weights(const float* P, Model& m, hipStream_t s) {
     if (!split_mode(m.mode)) return;
-    if (m.mode == RLGPU_GEMM_F16X3) {
-        for (auto& L : m.L) {
-            if (L.sf >= 0)
-                hipLaunchKernelGGL(mlp::split_weight_h3, dim3(L.sf_rows), dim3(256), 0, s, P + L.w, L.out, L.in, (int64_t)L.in, 0, L.sf_ld,
-                                   m.wsplit + L.sf, (int64_t)L.sf_rows * L.sf_ld, m.wscale + L.sfs);
-            if (L.sq >= 0 && h3_rowfuse(L.out))
-                hipLaunchKernelGGL(mlp::frag_weight_h3, dim3(L.sf_ld / 16 * (mlp::RLN_J / 32) * 2 * 64 / 256), dim3(256), 0, s,
-                                   m.wsplit + L.sf, (int64_t)L.sf_rows * L.sf_ld, L.sf_ld, m.wsplit + L.sq);
-            if (L.sb >= 0)
-                hipLaunchKernelGGL(mlp::split_weight_h3, dim3(L.sb_rows), dim3(256), 0, s, P + L.w, L.out, L.in, (int64_t)L.in, 1, L.sb_ld,
-                                   m.wsplit + L.sb, (int64_t)L.sb_rows * L.sb_ld, m.wscale + L.sbs);
-            // the backward planes are [in rows][out as k]: the forward planes' shape, the same reordering
-            if (L.sqb >= 0 && h3_rowfuse_bwd())
-                hipLaunchKernelGGL(mlp::frag_weight_h3, dim3(L.sb_ld / 16 * (mlp::RLN_J / 32) * 2 * 64 / 256), dim3(256), 0, s,
-                                   m.wsplit + L.sb, (int64_t)L.sb_rows * L.sb_ld, L.sb_ld, m.wsplit + L.sqb);
-        }
-        RLGPU_CHECK_HIP(hipGetLastError());
-        return;
-    }
-    for (auto& L : m.L) {
-        if (L.sf >= 0) {
-            int64_t e = (int64_t)L.sf_rows * L.sf_ld;
-            hipLaunchKernelGGL(mlp::split_weight, dim3(ceil_div(e, 256)), dim3(256), 0, s, P + L.w, L.out, L.in, 0, L.sf_rows,
-                               L.sf_ld, m.wsplit + L.sf);
-        }
-        if (L.sb >= 0) {
-            int64_t e = (int64_t)L.sb_rows * L.sb_ld;
-            hipLaunchKernelGGL(mlp::split_weight, dim3(ceil_div(e, 256)), dim3(256), 0, s, P + L.w, L.out, L.in, 1, L.sb_rows,
-                               L.sb_ld, m.wsplit + L.sb);
+    for (size_t l = 0; l < m.L.size(); l++) {
+        const Layer& L = m.L[l];
+        // the fragment-order copies exactly where the full-row kernels will read them (the backward planes are
+        // [in rows][out as k]: the forward planes' shape, the same reordering)
+        const bool frag[2] = {rowfuse_fwd(m, L), rowfuse_bwd(m, L, l > 0 ? &m.L[l - 1] : nullptr)};
+        for (int trans = 0; trans < 2; trans++) {
+            const Side& S = trans ? L.bwd : L.fwd;
+            if (S.planes < 0) continue;
+            uint16_t* planes = m.wsplit + S.planes;
+            if (m.mode != RLGPU_GEMM_F16X3) {
+                hipLaunchKernelGGL(mlp::split_weight, dim3(ceil_div(S.plane(), 256)), dim3(256), 0, s, P + L.w, L.out, L.in, trans,
+                                   S.rows, S.ld, planes);
+                continue;
+            }
+            hipLaunchKernelGGL(mlp::split_weight_h3, dim3(S.rows), dim3(256), 0, s, P + L.w, L.out, L.in, (int64_t)L.in, trans, S.ld,
+                               planes, S.plane(), m.wscale + S.scale);
+            if (frag[trans])
+                hipLaunchKernelGGL(mlp::frag_weight_h3, dim3(S.ld / 16 * (mlp::RLN_J / 32) * 2 * 64 / 256), dim3(256), 0, s, planes,
+                                   S.plane(), S.ld, m.wsplit + S.frag);
         }
     }
     RLGPU_CHECK_HIP(hipGetLastError());
@@ -465,54 +448,18 @@ struct Reducer {
     }
 };
 
-// dW (+)= dZ^T . X  over n rows (split-K over rows into `wpart`, fixed-order reduction into grad: now, or
-// through R at the end of the pass)
-void weight_grad(Model& m, const float* dZ, int out, const float* X, int64_t ldx, int in, int n, float* gW, hipStream_t s,
-                 bool x_tail_ok = false, const float* amax_dz = nullptr, const float* amax_x = nullptr, int64_t ldz = 0,
-                 Reducer* R = nullptr, float* wpart = nullptr) {
-    if (!wpart) wpart = m.wpart;
-    int splits = splits_for(m.mode, n, out, in);
-    int chunk = (int)ceil_div(ceil_div(n, splits), kgran(m.mode)) * kgran(m.mode);
-    int z = (int)ceil_div(n, chunk);
-    // ldz > out: dZ rows zero-padded to ldz floats (16-byte loads across the row end)
+// dW += dZ^T . X over n rows: split-K over the rows into the layer's partial buffer `wpart`, reduced in a fixed
+// order into gW through R at the end of the pass.  dz: [n][out] (rows zero-padded when tail_ok), x: [n][in]
+void weight_grad(Model& m, const Operand& dz, int out, const Operand& x, int in, int n, float* gW, hipStream_t s, Reducer& R,
+                 float* wpart) {
+    const int splits = splits_for(m.mode, n, out, in);
+    const int chunk = (int)ceil_div(ceil_div(n, splits), kgran(m.mode)) * kgran(m.mode);
     {
-    ktime::Span span(ktime::WGRAD_GEMM, 2.0 * out * in * (double)n, s);
-    gemm_f32(m.mode, mlp::A_KI, mlp::B_KJ, dZ, ldz ? ldz : out, X, ldx, wpart, in, nullptr, out, in, n, splits, s,
-             ldz > out, x_tail_ok, amax_dz, amax_x);
+        ktime::Span span(ktime::WGRAD_GEMM, 2.0 * out * in * (double)n, s);
+        gemm_f32(m.mode, mlp::A_KI, mlp::B_KJ, dz, x, wpart, in, nullptr, out, in, n, splits, s);
     }
-    int64_t e = (int64_t)out * in;
-    if (R) {
-        R->add(wpart, z, e, (int)e, gW, true, s);
-        return;
-    }
-    if (e % 4 == 0 && ((uintptr_t)gW & 15) == 0 && ((uintptr_t)wpart & 15) == 0)
-        hipLaunchKernelGGL(mlp::reduce_splits4, dim3(ceil_div(e / 4, 256)), dim3(256), 0, s, wpart, z, e, e, gW, 1);
-    else
-        hipLaunchKernelGGL(mlp::reduce_splits, dim3(ceil_div(e, 256)), dim3(256), 0, s, wpart, z, e, e, gW, 1);
-    RLGPU_CHECK_HIP(hipGetLastError());
-}
-
-// grad[0..n) += column sums of nblk partial rows (stride apart) -- two fixed-order levels
-void reduce_partials(Model& m, const float* part, int nblk, int64_t stride, int n, float* grad, hipStream_t s) {
-    const int G = nblk >= 256 ? 16 : 1;
-    float* mid = m.mid;  // [16][<= 3 * max(H, 1024)]
-    if (G > 1) {
-        hipLaunchKernelGGL(mlp::reduce_cols, dim3(ceil_div(n, 64), G), dim3(1024), 0, s, part, nblk, stride, (int64_t)0, n,
-                           mid, (int64_t)n, 0);
-        hipLaunchKernelGGL(mlp::reduce_cols, dim3(ceil_div(n, 64), 1), dim3(1024), 0, s, mid, G, (int64_t)n, (int64_t)0, n,
-                           grad, (int64_t)0, 1);
-    } else {
-        hipLaunchKernelGGL(mlp::reduce_cols, dim3(ceil_div(n, 64), 1), dim3(1024), 0, s, part, nblk, stride, (int64_t)0, n,
-                           grad, (int64_t)0, 1);
-    }
-    RLGPU_CHECK_HIP(hipGetLastError());
-}
-
-void colsum_into(Model& m, const float* X, int n, int C, float* g, hipStream_t s) {
-    int nb = (int)ceil_div(n, mlp::CS_ROWS);
-    hipLaunchKernelGGL(mlp::colsum_partial, dim3(nb), dim3(256), 0, s, X, n, C, m.cpart);
-    RLGPU_CHECK_HIP(hipGetLastError());
-    reduce_partials(m, m.cpart, nb, C, C, g, s);
+    const int64_t e = (int64_t)out * in;
+    R.add(wpart, (int)ceil_div(n, chunk), e, (int)e, gW, true, s);
 }
 
 // row stride of a multi-column loss gradient dout [n, out]: a multiple of 4 floats (the policy loss
@@ -525,207 +472,136 @@ inline const float* wscale_at(const Model& m, int64_t off) {
     return m.mode == RLGPU_GEMM_F16X3 ? m.wscale + off : nullptr;
 }
 
-// A training model's input: rows of ld floats, their H3 scale shards (null outside H3), and whether
-// the rows are zero-padded past the model input to a multiple of 4 (16-byte loads across the row end).
-struct Input {
-    const float* X;
-    int64_t ld;
-    const float* amax;
-    bool tail_ok;
-};
 // the gathered minibatch obs (rows of x_ld floats, zero-padded)
-inline Input obs_input(rlgpu_ppo* h) { return {h->x0, h->x_ld, h->x_amax, true}; }
+inline Operand obs_input(rlgpu_ppo* h) { return {h->x0, h->x_ld, h->x_amax, true}; }
 // what model mi reads: the obs, or the shared head's last activation (PPOLearner.cpp:403,474)
-inline Input model_input(rlgpu_ppo* h, int mi) {
+inline Operand model_input(rlgpu_ppo* h, int mi) {
     if (mi == 2 || !h->shared()) return obs_input(h);
     Model& sm = h->M[2];
     const int l = nhid(sm) - 1;
     return {sm.act[l], sm.L[l].out, amax_slot(sm, l), false};
 }
 
+// C[n, J] = A . W (+ bias) for layer L of model m: forward (J = L.out, K = L.in, with the bias) or -- bwd -- its
+// input gradient (J = L.in, K = L.out, A . W as [K][J]).  On the layer's pre-split planes when it has them
+// (gemm_x6_pre: the timed span, quad or 128 x 128 tiles), else on the fp32 weight (gemm_f32).
+void linear(const float* P, const Model& m, const Layer& L, bool bwd, const Operand& a, int n, float* C, hipStream_t s) {
+    const Side& S = bwd ? L.bwd : L.fwd;
+    const int J = bwd ? L.in : L.out, K = bwd ? L.out : L.in;
+    const float* bias = bwd ? nullptr : P + L.b;
+    if (S.planes >= 0)
+        gemm_x6_pre(a, m.wsplit + S.planes, S.ld, S.plane(), wscale_at(m, S.scale), C, J, bias, n, J, K, s);
+    else
+        gemm_f32(m.mode, mlp::A_IK, bwd ? mlp::B_KJ : mlp::B_JK, a, Operand{P + L.w, L.in, nullptr, false}, C, J, bias, n, J, K, 1, s);
+}
+
+// The GemmArgs of a full-row kernel (mlp::gemm_h3_rowln / gemm_h3_row_lnbwd) on side S: its fragment-order planes,
+// one 64-row x 512-column tile per workgroup; the caller adds C / bias where the kernel has them
+mlp::GemmArgs row_args(const Model& m, const Side& S, const Operand& a, int n, int K) {
+    return gemm_args(true, a, m.wsplit + S.frag, S.ld, nullptr, wscale_at(m, S.scale), n, mlp::RLN_J, K, mlp::RLN_BM, mlp::RLN_J);
+}
+
 // fp32 training forward of model mi on x; keeps activations; writes the output layer to `out` (the
 // shared head has none: its last activation stays in m.act).
-void forward_train(rlgpu_ppo* h, int mi, const Input& x, int n, float* out, hipStream_t s) {
+void forward_train(rlgpu_ppo* h, int mi, const Operand& x, int n, float* out, hipStream_t s) {
     Model& m = h->M[mi];
     const float* P = h->params;
     if (h->split_dirty[mi]) {
         split_weights(P, m, s);
         h->split_dirty[mi] = false;
     }
-    const int nh = nhid(m);
-    const float* in = x.X;
-    const float* in_amax = x.amax;
-    int64_t ld = x.ld;
-    bool tail_ok = x.tail_ok;
+    const int nh = nhid(m);  // >= 1 (rlgpu_ppo_create)
     const Layer* O = m.head_only ? nullptr : &m.L[nh];
-    const bool head1 = O && O->out == 1 && nh > 0;  // rank-1 head fused into the last LayerNorm forward
+    const bool head1 = O && O->out == 1;  // rank-1 head fused into the last LayerNorm forward
+    Operand in = x;
     for (int l = 0; l < nh; l++) {
         const Layer& L = m.L[l];
-        const float* gg = L.g >= 0 ? P + L.g : nullptr;
-        const float* bb = L.be >= 0 ? P + L.be : nullptr;
         const bool fuse = head1 && l == nh - 1;
-        const bool av = (ld % 4 == 0) && ((uintptr_t)in % 16 == 0) && (L.in % 4 == 0 || tail_ok);  // gemm_x6_pre's float4 test
-        if (m.mode == RLGPU_GEMM_F16X3 && L.sf >= 0 && L.sq >= 0 && av && h3_rowfuse(L.out)) {
-            if (!in_amax) throw rlgpu::Error(RLGPU_ERR_STATE, "H3 GEMM without operand scales");
+        // LayerNorm + LeakyReLU of z = m.xhat[l] into m.act[l] (and the rank-1 head's output)
+        const mlp::RowLnArgs ln{L.g >= 0 ? P + L.g : nullptr, L.be >= 0 ? P + L.be : nullptr, h->cfg.leaky_slope, h->cfg.layer_norm,
+                                m.act[l], reinterpret_cast<float2*>(m.rstd[l]), amax_slot(m, l), fuse ? P + O->w : nullptr,
+                                fuse ? P + O->b : nullptr, fuse ? out : nullptr};
+        if (rowfuse_fwd(m, L) && vec_ok(in, L.in)) {  // one launch; without 16-byte loads of `in`, the two below
             ktime::Span span(ktime::FWD_GEMM, 2.0 * n * L.out * L.in, s);
-            mlp::GemmArgs g{};
-            g.A = in;
-            g.B = reinterpret_cast<const float*>(m.wsplit + L.sq);
+            mlp::GemmArgs g = row_args(m, L.fwd, in, n, L.in);
             g.C = m.xhat[l];
             g.bias = P + L.b;
-            g.lda = ld;
-            g.ldb = L.sf_ld;
             g.ldc = L.out;
-            g.I = n;
-            g.J = L.out;
-            g.K = L.in;
-            g.amax_a = in_amax;
-            g.bscale = wscale_at(m, L.sfs);
-            const mlp::RowLnArgs ln{gg, bb, h->cfg.leaky_slope, h->cfg.layer_norm, m.act[l], reinterpret_cast<float2*>(m.rstd[l]),
-                                    amax_slot(m, l), fuse ? P + O->w : nullptr, fuse ? P + O->b : nullptr, fuse ? out : nullptr};
-            hipLaunchKernelGGL(mlp::gemm_h3_rowln, dim3(ceil_div(n, mlp::RLN_BM)), dim3(256), 0, s, g, ln);
+            launch_gemm(mlp::gemm_h3_rowln, 256, s, g, ln);
+        } else {
+            linear(P, m, L, false, in, n, m.xhat[l], s);
+            // bytes: z read, act written, (mean, rstd) written
+            ktime::Span span(ktime::LN_FWD, (double)n * (8.0 * L.out + 8.0), s);
+            int lnf_rows = 0;
+            const auto lnf = mlp::ln_act_fwd_f32_pick(L.out, &lnf_rows, fuse);
+            hipLaunchKernelGGL(lnf, dim3(ceil_div(n, lnf_rows)), dim3(256), 0, s, m.xhat[l], ln.gamma, ln.beta, n, L.out, ln.slope,
+                               ln.use_ln, ln.act, ln.stats, ln.amax, ln.head_w, ln.head_b, ln.head_out);
             RLGPU_CHECK_HIP(hipGetLastError());
-            in = m.act[l];
-            in_amax = amax_slot(m, l);
-            ld = L.out;
-            tail_ok = false;
-            continue;
         }
-        if (L.sf >= 0)
-            gemm_x6_pre(in, ld, m.wsplit + L.sf, L.sf_ld, (int64_t)L.sf_rows * L.sf_ld, m.xhat[l], L.out, P + L.b, n, L.out,
-                        L.in, s, tail_ok, in_amax, wscale_at(m, L.sfs));
-        else
-            gemm_f32(m.mode, mlp::A_IK, mlp::B_JK, in, ld, P + L.w, L.in, m.xhat[l], L.out, P + L.b, n, L.out, L.in, 1, s,
-                     tail_ok, false, in_amax);
-        // bytes: z read, act written, (mean, rstd) written
-        ktime::Span span(ktime::LN_FWD, (double)n * (8.0 * L.out + 8.0), s);
-        int lnf_rows = 0;
-        const auto lnf = mlp::ln_act_fwd_f32_pick(L.out, &lnf_rows, fuse);
-        hipLaunchKernelGGL(lnf, dim3(ceil_div(n, lnf_rows)), dim3(256), 0, s, m.xhat[l], gg, bb, n, L.out,
-                           h->cfg.leaky_slope, h->cfg.layer_norm, m.act[l], reinterpret_cast<float2*>(m.rstd[l]),
-                           amax_slot(m, l), fuse ? P + O->w : nullptr, fuse ? P + O->b : nullptr, fuse ? out : nullptr);
-        RLGPU_CHECK_HIP(hipGetLastError());
-        in = m.act[l];
-        in_amax = amax_slot(m, l);
-        ld = L.out;
-        tail_ok = false;
+        in = Operand{m.act[l], L.out, amax_slot(m, l), false};
     }
-    if (!O || head1) return;
-    // Not reached through rlgpu_ppo_create, which requires n_*_layers >= 1 (nh > 0, so head1 is set above); kept
-    // for a model without hidden layers.
-    if (O->out == 1) {  // rank-1 head (critic value) of a model without hidden layers: wave-per-row dot products
-        if (ld != O->in)
-            throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "a rank-1 model without hidden layers needs obs_size % 4 == 0");
-        hipLaunchKernelGGL(mlp::head1_fwd_any(O->in), dim3(ceil_div(n, mlp::H1_ROWS)), dim3(256), 0, s, in, P + O->w, P + O->b, n,
-                           O->in, out);
-        RLGPU_CHECK_HIP(hipGetLastError());
-        return;
-    }
-    if (O->sf >= 0)
-        gemm_x6_pre(in, ld, m.wsplit + O->sf, O->sf_ld, (int64_t)O->sf_rows * O->sf_ld, out, O->out, P + O->b, n, O->out, O->in, s,
-                    tail_ok, in_amax, wscale_at(m, O->sfs));
-    else
-        gemm_f32(m.mode, mlp::A_IK, mlp::B_JK, in, ld, P + O->w, O->in, out, O->out, P + O->b, n, O->out, O->in, 1, s, tail_ok,
-                 false, in_amax);
+    if (O && !head1) linear(P, m, *O, false, in, n, out, s);
 }
 
-// The input gradient of layer l (dA = A . W_l, A = the layer's dZ or the loss gradient: n rows of lda floats,
-// zero-padded to a multiple of 4 when a_tail_ok) and the LayerNorm backward of hidden layer l - 1 in one launch
-// of mlp::gemm_h3_row_lnbwd: writes that layer's dZ to dz_out (not A), its column partials to m.cpart_l[l - 1]
-// and max |dZ| to its slot; dA is not stored.  False (nothing launched) when the pair is not eligible.
-bool dA_ln_bwd_fused(rlgpu_ppo* h, Model& m, int l, const float* A, int64_t lda, bool a_tail_ok, const float* amax_a, int n,
-                     float* dz_out, hipStream_t s) {
-    if (m.mode != RLGPU_GEMM_F16X3 || l < 1 || !h3_rowfuse_bwd()) return false;
+// The input gradient of layer l >= 1 (dA = A . W_l, A = the layer's dZ or the loss gradient) and the LayerNorm
+// backward of hidden layer l - 1 in one launch of mlp::gemm_h3_row_lnbwd: writes that layer's dZ to dz_out (not A),
+// its column partials to m.cpart_l[l - 1] and max |dZ| to its slot; dA is not stored.  False (nothing launched)
+// when the pair is not eligible (rowfuse_bwd) or A cannot take 16-byte loads: the caller runs the two kernels.
+bool dA_ln_bwd_fused(rlgpu_ppo* h, Model& m, int l, const Operand& a, int n, float* dz_out, hipStream_t s) {
+    if (l < 1) return false;
     const Layer& L = m.L[l];
     const Layer& C = m.L[l - 1];  // the consumer: a hidden layer on ln_act_bwd<8>, never the rank-1 head's variant
-    if (L.sb < 0 || L.sqb < 0 || L.in != mlp::RLN_J || C.out != mlp::RLN_J) return false;
-    const bool av = (lda % 4 == 0) && ((uintptr_t)A % 16 == 0) && (L.out % 4 == 0 || a_tail_ok);  // gemm_x6_pre's float4 test
-    if (!av) return false;
-    if (!amax_a) throw rlgpu::Error(RLGPU_ERR_STATE, "H3 GEMM without operand scales");
+    if (!rowfuse_bwd(m, L, &C) || !vec_ok(a, L.out)) return false;
     const float* P = h->params;
     ktime::Span span(ktime::FWD_GEMM, 2.0 * n * L.in * L.out, s);
-    mlp::GemmArgs g{};
-    g.A = A;
-    g.B = reinterpret_cast<const float*>(m.wsplit + L.sqb);
-    g.lda = lda;
-    g.ldb = L.sb_ld;
-    g.I = n;
-    g.J = L.in;
-    g.K = L.out;
-    g.amax_a = amax_a;
-    g.bscale = wscale_at(m, L.sbs);
+    const mlp::GemmArgs g = row_args(m, L.bwd, a, n, L.out);
     const mlp::RowLnBwdArgs ln{C.g >= 0 ? P + C.g : nullptr, C.be >= 0 ? P + C.be : nullptr, h->cfg.leaky_slope, h->cfg.layer_norm,
                                m.xhat[l - 1], reinterpret_cast<const float2*>(m.rstd[l - 1]), dz_out, m.cpart_l[l - 1],
                                amax_slot(m, kAmaxDZ + l - 1)};
-    hipLaunchKernelGGL(mlp::gemm_h3_row_lnbwd, dim3(ceil_div(n, mlp::RLN_BM)), dim3(256), 0, s, g, ln);
-    RLGPU_CHECK_HIP(hipGetLastError());
+    launch_gemm(mlp::gemm_h3_row_lnbwd, 256, s, g, ln);
     return true;
 }
 
 // backward of model mi (input x) from dout into the grad buffer (accumulating).  dout: the loss
 // gradient [n, out] of the output layer, or -- the shared head -- the gradient of its last
-// activation [n, H].  dout_part: optional per-block column partials of dout (dout_nblk rows of `out`
-// floats, written by the loss kernel) for the output bias, instead of a separate column-sum pass.
+// activation [n, H].  dout_part: per-block column partials of a multi-column dout (dout_nblk rows of `out`
+// floats, written by the loss kernel) for the output bias.
 // H3: dout's max |x| is in slot kAmaxOut.  When m.dX is set (a model behind the shared head) the
 // gradient w.r.t. the model input is written there too.
-void backward(rlgpu_ppo* h, int mi, const Input& x, int n, const float* dout, hipStream_t s,
+void backward(rlgpu_ppo* h, int mi, const Operand& x, int n, const float* dout, hipStream_t s,
               const float* dout_part = nullptr, int dout_nblk = 0) {
     Model& m = h->M[mi];
     const float* P = h->params;
     float* G = h->grads;
-    const int nh = nhid(m);
+    const int nh = nhid(m);  // >= 1 (rlgpu_ppo_create): the output layer never reads the model input
+    // layer l's input, as its weight gradient reads it
+    const auto input_of = [&](int l) { return l > 0 ? Operand{m.act[l - 1], m.L[l].in, amax_slot(m, l - 1), false} : x; };
     const float* dA_top = m.dA;  // gradient of the last hidden layer's activation
     bool rank1 = false;          // rank-1 output layer folded into the last LayerNorm backward
     // the next layer's dZ when the launch above it already ran its LayerNorm backward (dA_ln_bwd_fused); those
     // launches alternate between m.dZ and m.dA, which no dA occupies on a fused layer, so none runs in place
     float* fused_dz = nullptr;
     // the pass's bias / LayerNorm / weight-gradient reductions, launched together at its end
-    Reducer red;
-    red.m = &m;
-    Reducer* R = &red;
+    Reducer R;
+    R.m = &m;
     const Layer* O = m.head_only ? nullptr : &m.L[nh];
     if (!O) {
         dA_top = dout;
-    } else if (O->out == 1 && nh == 0) {  // rank-1 head on the input: dA = dv w^T, dw / db partials in one pass
-        // not reached through rlgpu_ppo_create (n_*_layers >= 1), like forward_train's branch
-        if (x.ld != O->in)
-            throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "a rank-1 model without hidden layers needs obs_size % 4 == 0");
-        int nb = (int)ceil_div(n, mlp::LNB_ROWS);
-        hipLaunchKernelGGL(mlp::head1_bwd_any(O->in), dim3(nb), dim3(256), 0, s, x.X, P + O->w, dout, n, O->in,
-                           m.dX ? m.dX : m.dA, m.cpart);
-        RLGPU_CHECK_HIP(hipGetLastError());
-        reduce_partials(m, m.cpart, nb, O->in + 1, O->in + 1, G + O->w, s);  // [w | b] contiguous in the flat buffer
-        return;
     } else if (O->out == 1) {
         // rank-1 head after a LayerNorm: its backward recomputes dA = dv w^T and the activation, and
         // emits the head's dw / db partials (m.hpart) beside its own -- no separate head pass
         rank1 = true;
     } else {
-        if (m.mode == RLGPU_GEMM_F16X3 && !dout_part)
-            throw rlgpu::Error(RLGPU_ERR_STATE, "H3 backward: the loss kernel must provide dout's scale");
+        // the loss kernel provides the bias partials (and, H3, dout's scale): there is no column-sum pass
+        if (!dout_part) throw rlgpu::Error(RLGPU_ERR_STATE, "backward: a multi-column dout needs the loss kernel's bias partials");
         // dout rows of dld floats (the policy loss pads them with zeros to a multiple of 4)
         const int dld = dout_ld(O->out);
-        const Input a = nh > 0 ? Input{m.act[nh - 1], O->in, amax_slot(m, nh - 1), false} : x;
-        weight_grad(m, dout, O->out, a.X, a.ld, O->in, n, G + O->w, s, a.tail_ok, amax_slot(m, kAmaxOut), a.amax, dld, R,
-                    m.wpart_l[nh]);
-        if (dout_part)
-            R->add(dout_part, dout_nblk, O->out, O->out, G + O->b, false, s);
-        else if (dld == O->out)
-            colsum_into(m, dout, n, O->out, G + O->b, s);
-        else
-            throw rlgpu::Error(RLGPU_ERR_STATE, "backward: padded dout needs the loss kernel's bias partials");
-        // dA = dout . W_out (into the input gradient when the output layer reads the model input)
-        float* dA = nh > 0 ? m.dA : m.dX;
-        if (nh > 0 && dA_ln_bwd_fused(h, m, nh, dout, dld, dld > O->out, amax_slot(m, kAmaxOut), n, m.dZ, s)) {
-            fused_dz = m.dZ;
-        } else if (dA) {
-            if (O->sb >= 0)
-                gemm_x6_pre(dout, dld, m.wsplit + O->sb, O->sb_ld, (int64_t)O->sb_rows * O->sb_ld, dA, O->in, nullptr, n, O->in,
-                            O->out, s, dld > O->out, amax_slot(m, kAmaxOut), wscale_at(m, O->sbs));
-            else
-                gemm_f32(m.mode, mlp::A_IK, mlp::B_KJ, dout, dld, P + O->w, O->in, dA, O->in, nullptr, n, O->in, O->out, 1, s,
-                         dld > O->out, false, amax_slot(m, kAmaxOut), nullptr);
-        }
+        const Operand d{dout, dld, amax_slot(m, kAmaxOut), dld > O->out};
+        weight_grad(m, d, O->out, input_of(nh), O->in, n, G + O->w, s, R, m.wpart_l[nh]);
+        R.add(dout_part, dout_nblk, O->out, O->out, G + O->b, false, s);
+        // dA = dout . W_out
+        if (dA_ln_bwd_fused(h, m, nh, d, n, m.dZ, s)) fused_dz = m.dZ;
+        else linear(P, m, *O, true, d, n, m.dA, s);
     }
     const float* dA_in = dA_top;  // the gradient of the current layer's activation, unless fused_dz
     for (int l = nh - 1; l >= 0; l--) {
@@ -750,28 +626,22 @@ void backward(rlgpu_ppo* h, int mi, const Input& x, int n, const float* dout, hi
         // partials [blk][dbias | dgamma | dbeta] -> flat grads [b][g][be] (contiguous after L.b); the rank-1
         // head's [w | b] are contiguous too
         int ncol = h->cfg.layer_norm ? 3 * L.out : L.out;
-        if (r1) R->add(m.hpart, nb, O->in + 1, O->in + 1, G + O->w, false, s);
-        R->add(m.cpart_l[l], nb, 3 * (int64_t)L.out, ncol, G + L.b, false, s);
-        const Input a = l > 0 ? Input{m.act[l - 1], L.in, amax_slot(m, l - 1), false} : x;
-        weight_grad(m, dz, L.out, a.X, a.ld, L.in, n, G + L.w, s, a.tail_ok, amax_slot(m, kAmaxDZ + l), a.amax, 0, R,
-                    m.wpart_l[l]);
+        if (r1) R.add(m.hpart, nb, O->in + 1, O->in + 1, G + O->w, false, s);
+        R.add(m.cpart_l[l], nb, 3 * (int64_t)L.out, ncol, G + L.b, false, s);
+        const Operand d{dz, L.out, amax_slot(m, kAmaxDZ + l), false};
+        weight_grad(m, d, L.out, input_of(l), L.in, n, G + L.w, s, R, m.wpart_l[l]);
         float* other = dz == m.dZ ? m.dA : m.dZ;  // free: takes this layer's dA, or the next layer's dZ
         float* dA = l > 0 ? other : m.dX;         // the first layer's only when the input gradient is wanted
         fused_dz = nullptr;
         if (!dA) continue;
-        if (dA_ln_bwd_fused(h, m, l, dz, L.out, false, amax_slot(m, kAmaxDZ + l), n, other, s)) {
+        if (dA_ln_bwd_fused(h, m, l, d, n, other, s)) {
             fused_dz = other;
             continue;
         }
         dA_in = dA;
-        if (L.sb >= 0)
-            gemm_x6_pre(dz, L.out, m.wsplit + L.sb, L.sb_ld, (int64_t)L.sb_rows * L.sb_ld, dA, L.in, nullptr, n, L.in,
-                        L.out, s, false, amax_slot(m, kAmaxDZ + l), wscale_at(m, L.sbs));
-        else
-            gemm_f32(m.mode, mlp::A_IK, mlp::B_KJ, dz, L.out, P + L.w, L.in, dA, L.in, nullptr, n, L.in, L.out, 1, s, false,
-                     false, amax_slot(m, kAmaxDZ + l), nullptr);
+        linear(P, m, L, true, d, n, dA, s);
     }
-    red.flush(s);
+    R.flush(s);
 }
 
 void gather_obs(rlgpu_ppo* h, const float* obs, const int32_t* idx, int64_t start, int n, hipStream_t s) {
@@ -906,6 +776,25 @@ void infer_fused(rlgpu_ppo* h, int mi, bool ver, const float* X, int n, int mode
     RLGPU_CHECK_HIP(hipGetLastError());
 }
 
+// One side of a split weight -- `rows` B rows of k elements -- appended to m's plane and scale buffers: rows padded
+// to whole B tiles of the mode, k to mlp::XKMAX; frag (H3): the fragment-order copy of its mlp::RLN_J rows behind it
+Side add_side(Model& m, int rows, int k, bool frag) {
+    const bool h3 = m.mode == RLGPU_GEMM_F16X3;
+    const int rpad = h3 ? mlp::BNW : mlp::BN;
+    Side S;
+    S.rows = (int)ceil_div(rows, rpad) * rpad;
+    S.ld = (int)ceil_div(k, mlp::XKMAX) * mlp::XKMAX;
+    S.planes = m.nsplit;
+    m.nsplit += (h3 ? 2 : 3) * S.plane();  // planes per split weight
+    S.scale = m.nscale;
+    m.nscale += S.rows;
+    if (frag) {
+        S.frag = m.nsplit;
+        m.nsplit += 2 * (int64_t)mlp::RLN_J * S.ld;
+    }
+    return S;
+}
+
 // Model layout in the flat buffers.  out = 0: the shared head (hidden layers only, PPOLearner.cpp:56-64);
 // input_grad: the model reads the shared head's output, so its first layer also gets the transposed
 // weight planes for the input gradient.
@@ -952,31 +841,12 @@ void build_model(rlgpu_ppo* h, Model& m, int in, const int32_t* layers, int nl, 
         if (L.out > h->hmax) h->hmax = L.out;
         if (L.in > h->hmax && l > 0) h->hmax = L.in;
         if (split_mode(m.mode) && L.out > 1) {  // the rank-1 critic head has no GEMM
-            const int np = m.mode == RLGPU_GEMM_F16X3 ? 2 : 3;  // planes per split weight
-            const int rpad = m.mode == RLGPU_GEMM_F16X3 ? mlp::BNW : mlp::BN;  // rows: whole B tiles
-            L.sf_rows = (int)ceil_div(L.out, rpad) * rpad;
-            L.sf_ld = (int)ceil_div(L.in, mlp::XKMAX) * mlp::XKMAX;
-            L.sf = m.nsplit;
-            m.nsplit += np * (int64_t)L.sf_rows * L.sf_ld;
-            L.sfs = m.nscale;
-            m.nscale += L.sf_rows;
-            if (m.mode == RLGPU_GEMM_F16X3 && hidden && L.out == mlp::RLN_J) {
-                L.sq = m.nsplit;
-                m.nsplit += 2 * (int64_t)mlp::RLN_J * L.sf_ld;
-            }
-            if (l > 0 || input_grad) {  // dA of the first layer only behind the shared head
-                L.sb_rows = (int)ceil_div(L.in, rpad) * rpad;
-                L.sb_ld = (int)ceil_div(L.out, mlp::XKMAX) * mlp::XKMAX;
-                L.sb = m.nsplit;
-                m.nsplit += np * (int64_t)L.sb_rows * L.sb_ld;
-                L.sbs = m.nscale;
-                m.nscale += L.sb_rows;
-                // a hidden layer below consumes this layer's dA (the first layer's goes to the model input)
-                if (m.mode == RLGPU_GEMM_F16X3 && l > 0 && L.in == mlp::RLN_J) {
-                    L.sqb = m.nsplit;
-                    m.nsplit += 2 * (int64_t)mlp::RLN_J * L.sb_ld;
-                }
-            }
+            const bool h3 = m.mode == RLGPU_GEMM_F16X3;
+            // fragment-order copies: a hidden layer's own full row forward, and backward where a hidden layer below
+            // consumes this layer's dA (the first layer's goes to the model input)
+            L.fwd = add_side(m, L.out, L.in, h3 && hidden && L.out == mlp::RLN_J);
+            if (l > 0 || input_grad)  // dA of the first layer only behind the shared head
+                L.bwd = add_side(m, L.in, L.out, h3 && l > 0 && L.in == mlp::RLN_J);
         }
         m.L.push_back(L);
         prev = L.out;
@@ -1075,7 +945,6 @@ extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
             }
             int H = h->hmax;
             int omax = cfg->num_actions > 1 ? cfg->num_actions : 1;
-            int64_t wmax = 0, wpart_max = 0;
             {
                 int dev = 0, cus = 256;
                 if (hipGetDevice(&dev) == hipSuccess) {
@@ -1085,14 +954,9 @@ extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
                 }
                 g_cus = cus;
             }
-            for (int mi = 0; mi < h->nm; mi++)
-                for (auto& L : h->M[mi].L) {
-                    const Model& m = h->M[mi];
-                    wmax = std::max<int64_t>(wmax, (int64_t)L.in * L.out);
-                    // splits_for is non-decreasing in the row count, and z = ceil(n / chunk) <= splits
-                    wpart_max = std::max<int64_t>(wpart_max, (int64_t)splits_for(m.mode, (int)R, L.out, L.in) * L.in * L.out);
-                }
-            int64_t nb = ceil_div(R, std::min(std::min(mlp::LNB_ROWS_MIN, mlp::CS_ROWS), ppo::PL_ROWS));
+            // most blocks of any kernel that writes per-block partials: the LayerNorm backward variants and the policy
+            // loss (a 256-row column-sum pass once shared these buffers; 256 was never the minimum, so nb is what it was)
+            int64_t nb = ceil_div(R, std::min(mlp::LNB_ROWS_MIN, ppo::PL_ROWS));
             for (int mi = 0; mi < h->nm; mi++) {
                 Model& m = h->M[mi];
                 if (!m.head_only) {
@@ -1102,10 +966,9 @@ extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
                 if (sh && mi < 2) m.dX = h->alloc<float>(R * (int64_t)m.in);  // input gradient behind the shared head
                 m.dA = h->alloc<float>(R * H);
                 m.dZ = h->alloc<float>(R * H);
-                m.wpart = h->alloc<float>(wpart_max);
-                m.cpart = h->alloc<float>(nb * 3 * std::max(H, omax) + nb);
                 m.hpart = h->alloc<float>(nb * ((int64_t)H + 1));
-                // the deferred reductions' per-layer partials and level-1 rows (Reducer)
+                // the deferred reductions' per-layer partials and level-1 rows (Reducer); splits_for is
+                // non-decreasing in the row count, and a launch's ceil(n / chunk) partials are at most its splits
                 for (auto& L : m.L) {
                     m.wpart_l.push_back(h->alloc<float>((int64_t)splits_for(m.mode, (int)R, L.out, L.in) * L.in * L.out));
                     m.cpart_l.push_back(h->alloc<float>(nb * 3 * (int64_t)L.out));
@@ -1408,7 +1271,7 @@ extern "C" int rlgpu_ppo_minibatch(rlgpu_ppo* h, const float* d_obs, const uint8
         int A = h->cfg.num_actions;
         gather_obs(h, d_obs, d_index, start, n, s);  // one gathered, padded copy serves both models
         // the shared head's forward once per minibatch (PPOLearner.cpp:395-398); policy and critic read it
-        const Input obs_in = obs_input(h), xin = model_input(h, 0);
+        const Operand obs_in = obs_input(h), xin = model_input(h, 0);
         if (h->shared()) forward_train(h, 2, obs_in, n, nullptr, s);
         // the critic's pass runs on the auxiliary stream (disjoint parameters, gradients, workspace
         // and metric slots), overlapping the policy's; the caller's stream waits for both
@@ -1546,14 +1409,14 @@ extern "C" int rlgpu_gemm(int32_t mode, int32_t a_layout, int32_t b_layout, cons
                 else  // B [K][ldb]: W^T (out = K, in = J)
                     hipLaunchKernelGGL(mlp::split_weight_h3, dim3(rows), dim3(256), 0, s, d_B, K, J, ldb, 1, ld, planes, plane, inv);
                 RLGPU_CHECK_HIP(hipGetLastError());
-                gemm_x6_pre(d_A, lda, planes, ld, plane, d_C, ldc, d_bias, I, J, K, s, false, sh, inv);
+                gemm_x6_pre(Operand{d_A, lda, sh, false}, planes, ld, plane, inv, d_C, ldc, d_bias, I, J, K, s);
                 RLGPU_CHECK_HIP(hipFreeAsync(planes, s));
                 RLGPU_CHECK_HIP(hipFreeAsync(inv, s));
             } else {
                 const int64_t br = b_layout == 0 ? J : K, bc = b_layout == 0 ? K : J;
                 hipLaunchKernelGGL(mlp::amax_rows, dim3(256), dim3(256), 0, s, d_B, br, (int)bc, ldb, sh + 64);
-                gemm_f32(mode, a_layout, b_layout, d_A, lda, d_B, ldb, d_C, ldc, d_bias, I, J, K, splits, s, false, false, sh,
-                         sh + 64);
+                gemm_f32(mode, a_layout, b_layout, Operand{d_A, lda, sh, false}, Operand{d_B, ldb, sh + 64, false}, d_C, ldc, d_bias,
+                         I, J, K, splits, s);
             }
             RLGPU_CHECK_HIP(hipGetLastError());
             RLGPU_CHECK_HIP(hipFreeAsync(sh, s));
@@ -1572,11 +1435,12 @@ extern "C" int rlgpu_gemm(int32_t mode, int32_t a_layout, int32_t b_layout, cons
                 hipLaunchKernelGGL(mlp::split_weight, dim3(ceil_div(plane, 256)), dim3(256), 0, s, d_B, K, (int)ldb, 1, rows, ld,
                                    planes);
             RLGPU_CHECK_HIP(hipGetLastError());
-            gemm_x6_pre(d_A, lda, planes, ld, plane, d_C, ldc, d_bias, I, J, K, s);
+            gemm_x6_pre(Operand{d_A, lda, nullptr, false}, planes, ld, plane, nullptr, d_C, ldc, d_bias, I, J, K, s);
             RLGPU_CHECK_HIP(hipFreeAsync(planes, s));
             return;
         }
-        gemm_f32(mode, a_layout, b_layout, d_A, lda, d_B, ldb, d_C, ldc, d_bias, I, J, K, splits, s);
+        gemm_f32(mode, a_layout, b_layout, Operand{d_A, lda, nullptr, false}, Operand{d_B, ldb, nullptr, false}, d_C, ldc, d_bias, I,
+                 J, K, splits, s);
     });
 }
 
@@ -1588,7 +1452,8 @@ extern "C" int rlgpu_gemm_f32(int32_t a_layout, int32_t b_layout, const float* d
         RLGPU_REQUIRE(I > 0 && J > 0 && K > 0 && splits >= 1, "rlgpu_gemm_f32: bad sizes");
         RLGPU_REQUIRE((a_layout == 0 && (b_layout == 0 || b_layout == 1)) || (a_layout == 1 && b_layout == 1),
                       "rlgpu_gemm_f32: unsupported layout pair");
-        gemm_f32(RLGPU_GEMM_F32, a_layout, b_layout, d_A, lda, d_B, ldb, d_C, ldc, d_bias, I, J, K, splits, rlgpu::as_stream(stream));
+        gemm_f32(RLGPU_GEMM_F32, a_layout, b_layout, Operand{d_A, lda, nullptr, false}, Operand{d_B, ldb, nullptr, false}, d_C, ldc,
+                 d_bias, I, J, K, splits, rlgpu::as_stream(stream));
     });
 }
 

@@ -1,6 +1,7 @@
 """The full-row H3 forward GEMM with LayerNorm + LeakyReLU in the same launch (mlp::gemm_h3_rowln,
-RLGPU_H3_ROWFUSE) against the two-kernel path it replaces (gemm_x6 + ln_act_fwd_f32): same bits, and a
-kernel that keeps its registers and its two workgroups per CU."""
+RLGPU_H3_ROWFUSE) against the two-kernel path it replaces (gemm_x6 + ln_act_fwd_f32): same bits, the launches it
+is meant to replace and no others, and a kernel that keeps its registers and its two workgroups per CU."""
+import json
 import os
 import re
 import shutil
@@ -13,40 +14,50 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "reinforcement-learning_amd")
 
-# (rows, obs, policy layers, critic layers, layer_norm, leaky_slope).  The kernel's tile is 64 rows x 512 columns
-# (the only eligible width), its z stage 32 rows: 1 row, one below / above the tile height, several tiles with a
-# ragged last block; K = 167 (rows padded to 168 floats, the 16-byte loads straddle the row end), K = 168 and the
-# hidden K = 512; the critic's last layer carries the fused rank-1 head.  (510, 512): the first layer falls
-# back to the two-kernel path (ragged width), the second is fused behind it.
+# (rows, obs, policy layers, critic layers, layer_norm, leaky_slope, ln_fwd).  The kernel's tile is 64 rows x 512
+# columns (the only eligible width), its z stage 32 rows: 1 row, one below / above the tile height, several tiles
+# with a ragged last block; K = 167 (rows padded to 168 floats, the 16-byte loads straddle the row end), K = 168
+# and the hidden K = 512; the critic's last layer carries the fused rank-1 head.
+# ln_fwd: stand-alone LayerNorm forward launches of one minibatch with the knob at (0, 1).  The rule: a hidden
+# layer of exactly 512 outputs whose input rows take 16-byte loads (a 16-byte aligned base and leading dimension,
+# K a multiple of 4 or rows zero-padded to one) is fused; two models of two hidden layers have 4 launches.
+# (510, 512): the first layer is ragged, and the second reads its 510-float rows (no 16-byte loads), so both fall
+# back.  (256, 512): the first layer falls back on its width, the second is fused behind it.
 CASES = [
-    (1, 167, (512, 512), (512, 512), True, 0.01),
-    (63, 168, (512, 512), (512, 512), True, 0.01),
-    (65, 167, (512, 512), (512, 512), True, 0.01),
-    (1000, 167, (512, 512), (512, 512), True, 0.01),
-    (1000, 168, (512, 512), (512, 512), True, 0.01),
-    (1000, 167, (510, 512), (510, 512), True, 0.01),
-    (65, 167, (512, 512), (512, 512), False, 0.01),
-    (193, 167, (512, 512), (512, 512), True, 0.2),
+    (1, 167, (512, 512), (512, 512), True, 0.01, (4, 0)),
+    (63, 168, (512, 512), (512, 512), True, 0.01, (4, 0)),
+    (65, 167, (512, 512), (512, 512), True, 0.01, (4, 0)),
+    (1000, 167, (512, 512), (512, 512), True, 0.01, (4, 0)),
+    (1000, 168, (512, 512), (512, 512), True, 0.01, (4, 0)),
+    (1000, 167, (510, 512), (510, 512), True, 0.01, (4, 4)),
+    (65, 167, (256, 512), (256, 512), True, 0.01, (4, 2)),
+    (65, 167, (512, 512), (512, 512), False, 0.01, (4, 0)),
+    (193, 167, (512, 512), (512, 512), True, 0.2, (4, 0)),
 ]
 
 _CHILD = r"""
-import sys, numpy as np, torch
+import json, sys, numpy as np, torch
 sys.path[:0] = [sys.argv[2], sys.argv[2] + "/reinforcement-learning_amd", sys.argv[2] + "/tests"]
-from rlgpu.ppo import PPO
+from rlgpu.ppo import PPO, kernel_timing, kernel_timing_read
 from test_ppo import make_batch
 from test_ppo_rowfuse import CASES
 dev = torch.device("cuda:0")
-out = []
-for n, obs_size, pol, crit, ln, slope in CASES:
+out, counts = [], []
+for n, obs_size, pol, crit, ln, slope, _ in CASES:
     p = PPO(obs_size=obs_size, policy_layers=pol, critic_layers=crit, layer_norm=ln, leaky_slope=slope, max_rows=1024, seed=5)
     obs, masks, acts, old, adv, tgt = make_batch(np.random.default_rng(n + obs_size), n, obs_size=obs_size)
     d = [torch.from_numpy(v).to(dev) for v in (obs, masks, acts, old, adv, tgt)]
     if n > 1:
         p.adv_normalizer(d[4])
     p.zero_grad()
+    kernel_timing(True)
     p.minibatch(*d, None, 0, n, n)
+    torch.cuda.synchronize()
+    counts.append(kernel_timing_read()["LayerNorm forward"][2])
+    kernel_timing(False)
     out += [p.flat(grads=True).cpu().numpy(), p.forward(0, d[0]).cpu().numpy().ravel(), p.forward(1, d[0]).cpu().numpy().ravel()]
 np.save(sys.argv[1], np.concatenate(out))
+json.dump(counts, open(sys.argv[1] + ".json", "w"))
 """
 
 
@@ -56,14 +67,20 @@ def test_rowfuse_bit_identical(gpu, tmp_path):
     """RLGPU_H3_ROWFUSE=1 (every 512-column hidden layer on gemm_h3_rowln) gives the same minibatch gradients,
     policy forward and critic values, bit for bit, as RLGPU_H3_ROWFUSE=0 (gemm_x6 + ln_act_fwd_f32): the same
     products in the same order into one accumulator, the same epilogue value, and the LayerNorm forward's own
-    arithmetic on those bits.  The knob is read once per process: child processes."""
-    res = {}
+    arithmetic on those bits.  The stand-alone LayerNorm forward launches that remain in the minibatch (the
+    learn-phase timing spans count them) show that the fused launch ran where it should and nowhere else: the
+    two paths give the same bits, so nothing else here would notice a layer that silently stopped fusing.  The
+    knob is read once per process: child processes."""
+    res, cnt = {}, {}
     for v in ("0", "1"):
         f = str(tmp_path / f"r{v}.npy")
         r = subprocess.run(["timeout", "-k", "10", "90", sys.executable, "-c", _CHILD, f, ROOT],
                            env=dict(os.environ, RLGPU_H3_ROWFUSE=v), capture_output=True, text=True, cwd=ROOT)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
         res[v] = np.load(f)
+        cnt[v] = json.load(open(f + ".json"))
+    for v, col in (("0", 0), ("1", 1)):
+        assert cnt[v] == [c[6][col] for c in CASES], (v, cnt[v])
     assert res["0"].shape == res["1"].shape
     assert np.isfinite(res["0"]).all()
     np.testing.assert_array_equal(res["0"].view(np.uint32), res["1"].view(np.uint32))

@@ -416,6 +416,25 @@ def test_create_rejects_one_action():
         assert b"num_actions" not in L.rlgpu_last_error()
 
 
+@pytest.mark.parametrize("field", ["n_policy_layers", "n_critic_layers"])
+def test_create_rejects_model_without_hidden_layers(field):
+    """Every model has at least one hidden layer: rlgpu_ppo_create names a zero layer count, for the policy and for
+    the critic (the training passes have no path for an output layer that reads the model input), before it
+    allocates anything -- so this needs no GPU."""
+    import ctypes
+    from rlgpu.ppo import _Cfg, _bind
+    L = _bind()
+    L.rlgpu_last_error.restype = ctypes.c_char_p
+    cfg = _Cfg()
+    cfg.obs_size, cfg.num_actions, cfg.max_rows = 167, 90, 64
+    cfg.n_policy_layers = cfg.n_critic_layers = 1
+    cfg.policy_layers[0] = cfg.critic_layers[0] = 64
+    setattr(cfg, field, 0)
+    h = ctypes.c_void_p()
+    assert L.rlgpu_ppo_create(ctypes.byref(cfg), ctypes.byref(h)) != 0 and not h.value
+    assert b"1..8 hidden layers per model" in L.rlgpu_last_error()
+
+
 def test_scalar_floor_is_small():
     """No scalar is allowed more than 1e-4 of its scale, and the clip fraction less than half a row, at every n."""
     for c in list(CASES.values()) + [OPTIM]:
