@@ -169,6 +169,18 @@ DEV Tile xcd_tile(int gx, int gy, int gz) {
     return o;
 }
 
+// The 32 x 32 accumulator block of the 32x32xK MFMAs: lane l holds column l & 31; its element r (0..15) is row
+// (r & 3) + 8 (r >> 2) + 4 half, half = l >> 5 -- four consecutive rows out of every eight, the other
+// half-wave holding the four between.  base: the block's first row in the tile or matrix; it leads the sum
+// because the epilogues' index arithmetic is compiled to the same code only with this association.
+DEV int acc_row(int r, int half, int base = 0) { return base + (r & 3) + 8 * (r >> 2) + 4 * half; }
+// All-zero accumulators.  gemm_f32, gemm_x6 and h3_row_kloop keep their element loops: after either form the
+// registers hold the same zeros, but the instruction schedule of those three differs between the forms.
+template <int M, int N>
+DEV void zero_acc(f32x16 (&acc)[M][N]) {
+    __builtin_memset(acc, 0, sizeof(acc));
+}
+
 // fp32 GEMM on v_mfma_f32_32x32x2_f32: each MFMA j of a BK step takes k = j (lanes 0-31) and
 // k = 16 + j (lanes 32-63) so that k-contiguous tiles are read as 16-byte vectors.
 #ifndef RLGPU_GEMM_OCC
@@ -230,7 +242,7 @@ __global__ void __launch_bounds__(256, RLGPU_GEMM_OCC) gemm_f32(GemmArgs g) {
                 const float bj = g.bias ? g.bias[j0 + wn * 64 + tj * 32 + l32] : 0.f;
                 float* ct = cb + (int64_t)(ti * 32) * g.ldc + tj * 32;
 #pragma unroll
-                for (int r = 0; r < 16; r++) ct[(int64_t)((r & 3) + 8 * (r >> 2)) * g.ldc] = acc[ti][tj][r] + bj;
+                for (int r = 0; r < 16; r++) ct[(int64_t)acc_row(r, 0) * g.ldc] = acc[ti][tj][r] + bj;
             }
         return;
     }
@@ -243,7 +255,7 @@ __global__ void __launch_bounds__(256, RLGPU_GEMM_OCC) gemm_f32(GemmArgs g) {
             float bj = g.bias ? g.bias[j] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                int i = i0 + wm * 64 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                int i = acc_row(r, h, i0 + wm * 64 + ti * 32);
                 if (i < g.I) C[(int64_t)i * g.ldc + j] = acc[ti][tj][r] + bj;
             }
         }
@@ -261,10 +273,14 @@ __global__ void __launch_bounds__(256, RLGPU_GEMM_OCC) gemm_f32(GemmArgs g) {
 // (6 x 32 cycles per K = 16) replace eight f32 ones (8 x 64 cycles).  Same tiles, layouts, split-K
 // and epilogue as gemm_f32; operands are split once per LDS stage into three k-contiguous bf16
 // planes, so the MFMA loop reads b128 vectors whatever the global layout.
+constexpr int XK = 32;             // k depth of one LDS stage of every split-plane GEMM
+constexpr int XKG = XK / 8;        // its 16-byte chunks (8 k of one plane row)
 constexpr int XPAD = 8;            // bf16 pad per LDS row
-constexpr int XKMAX = 64;          // deepest stage of any variant: split-K chunks and weight-plane
-                                   // padding are multiples of it
+constexpr int XKMAX = 64;          // granularity of the k padding of the weight planes and of the split-K chunks
+                                   // (once the deepest stage of any variant; no stage is deeper than XK now, but
+                                   // the chunk boundaries decide the summation order, so the value stays)
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 
 DEV uint32_t pack_bf16x2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
 
@@ -346,30 +362,28 @@ DEV void h3_amax_commit(float* shards, uint32_t vmax) {
 }
 DEV uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
 
-// Per-thread share of one 128 x XK operand stage (XK = 32 or 64 k): NQ = XK / 16 groups of 8
-// consecutive k of one row, held in native 4-vectors (loop-carried prefetch registers stay where
-// the loads land, so the wait for them sits at the next stage's store, after this stage's MFMAs).
-//   KMAJ (k contiguous in memory): group e = t + 256 q -> row e / KG, k group e % KG (2 float4 loads)
+// Per-thread share of one 128 x XK operand stage: XK / 16 = 2 groups of 8 consecutive k of one row,
+// held in native 4-vectors (loop-carried prefetch registers stay where the loads land, so the wait
+// for them sits at the next stage's store, after this stage's MFMAs).
+//   KMAJ (k contiguous in memory): group e = t + 256 q -> row e / XKG, k group e % XKG (kc_load)
 //   !KMAJ (row index contiguous):  group e -> row e & 127, k group e >> 7 (8 scalar loads, each a
 //                                  256-byte contiguous wave access)
-template <bool KMAJ, int XK>
+template <bool KMAJ>
 DEV int xs_row(int q) {
-    constexpr int KG = XK / 8;
     const int e = threadIdx.x + 256 * q;
-    return KMAJ ? e / KG : e & 127;
+    return KMAJ ? e / XKG : e & 127;
 }
-template <bool KMAJ, int XK>
+template <bool KMAJ>
 DEV int xs_kg(int q) {
-    constexpr int KG = XK / 8;
     const int e = threadIdx.x + 256 * q;
-    return KMAJ ? e % KG : e >> 7;
+    return KMAJ ? e % XKG : e >> 7;
 }
-template <bool KMAJ, int XK>
+template <bool KMAJ>
 DEV RowPtrs xs_rows(const float* base, int64_t ld, int o0, int on) {
     RowPtrs r;
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        const int go = o0 + xs_row<KMAJ, XK>(q);
+        const int go = o0 + xs_row<KMAJ>(q);
         r.p[q] = (KMAJ && q < XK / 16 && go < on) ? base + (int64_t)go * ld : nullptr;
     }
     return r;
@@ -387,18 +401,47 @@ DEV f32x4_t load4v(const float* p, int c, int lim) {
     }
     return v;
 }
-template <bool KMAJ, bool VEC, int XK>
+// Unpadded planes (row pitch P == XK halves, 64 B) are XOR-swizzled instead of padded:
+// the 16-byte chunk c of row r sits at chunk c ^ ((r >> 2) & 3).  Then both the staging stores
+// (ds_write_b128: 8 lanes = 2 rows x 4 chunks, one 128-byte span) and the fragment reads
+// (ds_read_b128: 16 lanes = rows {0-3, 12-15, 20-27} + 32 u, one chunk) are conflict-free; the
+// padded pitch (80 B) left the stores 2-way conflicted.
+template <int P>
+DEV int xchunk(int row, int c) {  // physical chunk of logical chunk c
+    return P == XK ? (c ^ ((row >> 2) & 3)) : c;
+}
+// H3 staging of 8 consecutive k of one k-contiguous row (gemm_x6 through xs_*, gemm_h3q; h3_row_kloop
+// spells the same three lines out): two float4 loads (past ke or with no row: the zero row); scaled, split
+// into the (h, l) planes [2][R][P] at chunk kg of the row; the MFMA fragment (8 k of one row per lane) is
+// that chunk read back (kc_frag: all three kernels).
+template <bool VEC>
+DEV void kc_load(f32x4_t (&v)[2], const float* row, int kk, int ke) {
+    v[0] = load4v<VEC>(row, kk, ke);
+    v[1] = load4v<VEC>(row, kk + 4, ke);
+}
+template <int R, int P>
+DEV void kc_store(uint16_t (*lds)[R][P], const f32x4_t (&v)[2], float sc, int row, int kg) {
+    const int c = xchunk<P>(row, kg) * 8;
+    u32x4_t h, l;
+    split2h(v, sc, h, l);
+    *reinterpret_cast<u32x4_t*>(&lds[0][row][c]) = h;
+    *reinterpret_cast<u32x4_t*>(&lds[1][row][c]) = l;
+}
+template <int P>
+DEV h16x8 kc_frag(const uint16_t (*plane)[P], int row, int kc) {
+    return *(const h16x8*)&plane[row][xchunk<P>(row, kc) * 8];
+}
+template <bool KMAJ, bool VEC>
 DEV void xs_load(f32x4_t (&v)[XK / 16][2], const RowPtrs& rows, const float* base, int64_t ld, int o0, int on, int k0,
                  int ke) {
     const float* z = reinterpret_cast<const float*>(g_zero_row);
 #pragma unroll
     for (int q = 0; q < XK / 16; q++) {
-        const int kk = k0 + xs_kg<KMAJ, XK>(q) * 8;
+        const int kk = k0 + xs_kg<KMAJ>(q) * 8;
         if (KMAJ) {
-            v[q][0] = load4v<VEC>(rows.p[q], kk, ke);
-            v[q][1] = load4v<VEC>(rows.p[q], kk + 4, ke);
+            kc_load<VEC>(v[q], rows.p[q], kk, ke);
         } else {
-            const int o = o0 + xs_row<KMAJ, XK>(q);
+            const int o = o0 + xs_row<KMAJ>(q);
 #pragma unroll
             for (int c = 0; c < 8; c++) {
                 const bool ok = (kk + c < ke) && (o < on);
@@ -407,27 +450,15 @@ DEV void xs_load(f32x4_t (&v)[XK / 16][2], const RowPtrs& rows, const float* bas
         }
     }
 }
-// Unpadded 32-deep planes (row pitch P == XK == 32 halves, 64 B) are XOR-swizzled instead of padded:
-// the 16-byte chunk c of row r sits at chunk c ^ ((r >> 2) & 3).  Then both the staging stores
-// (ds_write_b128: 8 lanes = 2 rows x 4 chunks, one 128-byte span) and the fragment reads
-// (ds_read_b128: 16 lanes = rows {0-3, 12-15, 20-27} + 32 u, one chunk) are conflict-free; the
-// padded pitch (80 B) left the stores 2-way conflicted.
-template <int P, int XK>
-DEV int xchunk(int row, int c) {  // physical chunk of logical chunk c
-    static_assert(P != XK || XK == 32, "swizzled planes are 32 deep");
-    return P == XK ? (c ^ ((row >> 2) & 3)) : c;
-}
-template <bool KMAJ, int XK, bool H3, int P = XK + XPAD>
+template <bool KMAJ, bool H3, int P = XK + XPAD>
 DEV void xs_store(uint16_t (*lds)[BM][P], const f32x4_t (&v)[XK / 16][2], float sc) {
 #pragma unroll
     for (int q = 0; q < XK / 16; q++) {
-        const int row = xs_row<KMAJ, XK>(q), c = xchunk<P, XK>(row, xs_kg<KMAJ, XK>(q)) * 8;
+        const int row = xs_row<KMAJ>(q), kg = xs_kg<KMAJ>(q);
         if (H3) {
-            u32x4_t h, l;
-            split2h(v[q], sc, h, l);
-            *reinterpret_cast<u32x4_t*>(&lds[0][row][c]) = h;
-            *reinterpret_cast<u32x4_t*>(&lds[1][row][c]) = l;
+            kc_store(lds, v[q], sc, row, kg);
         } else {
+            const int c = xchunk<P>(row, kg) * 8;
             u32x4_t h, m, l;
             split3(v[q], h, m, l);
             *reinterpret_cast<u32x4_t*>(&lds[0][row][c]) = h;
@@ -438,32 +469,30 @@ DEV void xs_store(uint16_t (*lds)[BM][P], const f32x4_t (&v)[XK / 16][2], float 
 }
 
 // B operand given pre-split (BPRE): three bf16 planes [3][rows][ldbp] (k contiguous; rows padded to a
-// multiple of 128 and ldbp a multiple of 64, zero filled), plane stride g.bplane elements.  A
+// multiple of 128 and ldbp a multiple of XKMAX, zero filled), plane stride g.bplane elements.  A
 // weight matrix is reused by every row tile of a minibatch, so it is split once per minibatch
 // (split_weight) instead of once per tile and stage.  Per thread and stage: XK / 16 16-byte chunks
-// per plane (row e / KG, chunk e % KG of 8 bf16).
-template <int XK, int NP>
+// per plane (row e / XKG, chunk e % XKG of 8 bf16).
+template <int NP>
 DEV void xp_load(u32x4_t (&v)[NP][XK / 16], const uint16_t* B, int64_t ldb, int64_t plane, int j0, int k0, int ke) {
-    constexpr int KG = XK / 8;
 #pragma unroll
     for (int q = 0; q < XK / 16; q++) {
         const int e = threadIdx.x + 256 * q;
-        const int64_t off = (int64_t)(j0 + e / KG) * ldb + k0 + (e % KG) * 8;
-        const bool ok = k0 + (e % KG) * 8 < ke;
+        const int64_t off = (int64_t)(j0 + e / XKG) * ldb + k0 + (e % XKG) * 8;
+        const bool ok = k0 + (e % XKG) * 8 < ke;
 #pragma unroll
         for (int p = 0; p < NP; p++)
             v[p][q] = *reinterpret_cast<const u32x4_t*>(ok ? B + p * plane + off : reinterpret_cast<const uint16_t*>(g_zero_row));
     }
 }
-template <int XK, int NP, int P = XK + XPAD>
+template <int NP, int P = XK + XPAD>
 DEV void xp_store(uint16_t (*lds)[BM][P], const u32x4_t (&v)[NP][XK / 16]) {
-    constexpr int KG = XK / 8;
 #pragma unroll
     for (int q = 0; q < XK / 16; q++) {
         const int e = threadIdx.x + 256 * q;
-        const int c = xchunk<P, XK>(e / KG, e % KG) * 8;
+        const int c = xchunk<P>(e / XKG, e % XKG) * 8;
 #pragma unroll
-        for (int p = 0; p < NP; p++) *reinterpret_cast<u32x4_t*>(&lds[p][e / KG][c]) = v[p][q];
+        for (int p = 0; p < NP; p++) *reinterpret_cast<u32x4_t*>(&lds[p][e / XKG][c]) = v[p][q];
     }
 }
 
@@ -533,9 +562,89 @@ __global__ void __launch_bounds__(256) amax_rows(const float* X, int64_t rows, i
     h3_amax_commit(shards, m);
 }
 
-// gemm_x6's pipeline: 32-deep stages, one LDS buffer, the next stage prefetched into registers while this
-// stage's MFMAs run; two (x6) or three (H3: 146 VGPRs, 40 KB LDS) workgroups per CU.
-template <int XK>
+// ---- k-major staging of a row-index-contiguous operand (H3): A_KI (dZ^T) and B_KJ (activations) of the
+// weight gradients, in gemm_x6 (NT = 256 threads, COLS = 128) and gemm_h3qt (512, 256).  Global rows are k,
+// contiguous in the output index o, so each thread loads 4 float4s along o (group e = t + NT q: k row
+// e / (COLS / 4), float4 e % (COLS / 4); whole coalesced rows, no scalar gathers) and stores each plane
+// k-major: element (k, o) at k * kt_pitch(COLS) + o of the plane.  The MFMA fragments (8 consecutive k of one
+// o per lane) are read back transposed with ds_read_b64_tr_b16 (tr_frag): per 16-lane group a 4 (k) x 16 (o)
+// block, lane 4q+p addressing row q, columns 4p..4p+3; two reads give k .. k+7.  The pitch COLS + 32 halves
+// puts the 4 rows of a 32-lane half at bank offsets 0 / 16 / 32 / 48: conflict-free.
+constexpr int kt_pitch(int cols) { return cols + 32; }
+static_assert(XK * kt_pitch(BM) == BM * (XK + XPAD), "gemm_x6's k-major plane must fit its row-major plane storage");
+template <int NT, int COLS, bool VEC>
+DEV void kt_load(f32x4_t (&v)[2][2], const float* base, int64_t ld, int o0, int on, int k0, int ke) {
+    static_assert(XK * COLS == 16 * NT, "4 float4 per thread");
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int e = threadIdx.x + NT * q;
+        const int k = k0 + e / (COLS / 4), o = o0 + (e % (COLS / 4)) * 4;
+        const float* row = k < ke ? base + (int64_t)k * ld : nullptr;
+        v[q >> 1][q & 1] = load4v<VEC>(row, o, on);
+    }
+}
+template <int NT, int COLS>
+DEV void kt_store(uint16_t* ph, uint16_t* pl, const f32x4_t (&v)[2][2], float sc) {  // ph / pl: the h / l planes
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int e = threadIdx.x + NT * q;
+        const int off = (e / (COLS / 4)) * kt_pitch(COLS) + (e % (COLS / 4)) * 4;
+        const f32x4_t x = v[q >> 1][q & 1];
+        uint32_t h2[2], l2[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            const float x0 = x[2 * c] * sc, x1 = x[2 * c + 1] * sc;
+            const uint16_t h0 = f2hf(x0), h1 = f2hf(x1);
+            h2[c] = pack_h2(h0, h1);
+            l2[c] = pack_h2(f2hf(x0 - hf2f(h0)), f2hf(x1 - hf2f(h1)));
+        }
+        *reinterpret_cast<uint2*>(ph + off) = make_uint2(h2[0], h2[1]);
+        *reinterpret_cast<uint2*>(pl + off) = make_uint2(l2[0], l2[1]);
+    }
+}
+// the 32x32x16 operand fragment of output rows ob .. ob+31 at k = kof0 + 8 (lane >> 5) + 0..7, from a k-major
+// plane of row pitch P halves
+typedef short v4i16 __attribute__((ext_vector_type(4)));
+template <int P>
+DEV h16x8 tr_frag(const uint16_t* plane, int ob, int kof0, int lane) {
+    const int g = lane >> 4, i = lane & 15;
+    const int o = ob + 16 * (g & 1) + 4 * (i & 3);
+    const int k = kof0 + 8 * (g >> 1) + (i >> 2);
+    typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
+    const v4i16 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(plane + k * P + o));
+    const v4i16 y = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(plane + (k + 4) * P + o));
+    typedef short v8i16 __attribute__((ext_vector_type(8)));
+    const v8i16 r = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
+    return __builtin_bit_cast(h16x8, r);
+}
+
+// The H3 products of one 16-deep k step of a wave's 64 x (32 NJ) tile, from its fragments a / b [plane][block].
+// Every H3 kernel (gemm_x6, gemm_h3q, gemm_h3qt, h3_row_kloop) takes its k steps in ascending order through this
+// one function, so for the same operands and K chunk their accumulators hold the same bits.
+// One accumulator: the corrections l.h, h.l, then the leading product h.h, enter the running f32 sum (the rounding
+// count of an f32 FMA chain; a separate correction accumulator would cost 64 registers that the stage uses instead)
+template <int NJ>
+DEV void h3_mfma_step(const h16x8 (&a)[2][2], const h16x8 (&b)[2][NJ], f32x16 (&acc)[2][NJ]) {
+#pragma unroll
+    for (int ti = 0; ti < 2; ti++)
+#pragma unroll
+        for (int tj = 0; tj < NJ; tj++) {
+            f32x16 c = acc[ti][tj];
+            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][ti], b[0][tj], c, 0, 0, 0);  // l h
+            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[1][tj], c, 0, 0, 0);  // h l
+            acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[0][tj], c, 0, 0, 0);  // h h
+        }
+}
+// The H3 epilogue value of an accumulator element v: the operand scales undone (powers of two: exact; csc the
+// pre-split B's per-row inverse scale or 1, p the sum of the per-tensor scale exponents), then the bias.
+// gemm_x6 is the statement of this arithmetic: it passes v = acc + cor, its H3 correction accumulator being all
+// zeros, and a bias of 0.f where there is none.  x + 0.f is not the identity (it turns -0 into +0) and the
+// compiler keeps it, so the full-row kernels, which have no such accumulator and in the backward no bias, pass
+// acc + 0.f and 0.f to state gemm_x6's arithmetic literally.  gemm_h3q / gemm_h3qt pass acc itself (a 1.f scale
+// folds away); that differs from gemm_x6 only for an accumulator of -0, and the quad-tile bit-identity tests pin it.
+DEV float h3_out(float v, float csc, int p, float bias) { return ldexpf(v * csc, -p) + bias; }
+
+// One stage of gemm_x6's MFMAs: ra / rb this lane's row of the wave's first A / B block.
 DEV void x6_mfma_stage(const uint16_t (*As)[BM][XK + XPAD], const uint16_t (*Bs)[BN][XK + XPAD], int ra, int rb, int lane,
                        f32x16 (&acc)[2][2], f32x16 (&cor)[2][2]) {
 #pragma unroll
@@ -564,81 +673,11 @@ DEV void x6_mfma_stage(const uint16_t (*As)[BM][XK + XPAD], const uint16_t (*Bs)
             }
     }
 }
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-
-// ---- k-major ("T") staging of a row-index-contiguous operand (H3, 32-deep stages): A_KI (dZ^T)
-// and B_KJ (activations) of the weight gradients.  Global rows are k, contiguous in the output
-// index o, so each thread loads float4s along o (coalesced 512-byte rows per half wave, no scalar
-// gathers) and stores each plane k-major: element (k, o) at k * TPITCH + o of the plane (the
-// plane's [BM][XK + XPAD] storage, same size).  The MFMA fragments (8 consecutive k of one o per
-// lane) are read back transposed with ds_read_b64_tr_b16: per 16-lane group a 4 (k) x 16 (o)
-// block, lane 4q+p addressing row q, columns 4p..4p+3; two reads give k .. k+7.  TPITCH = 160
-// halves puts the 4 rows of a 32-lane half at bank offsets 0 / 16 / 32 / 48: conflict-free.
-constexpr int TPITCH = 160;
-static_assert(32 * TPITCH == BM * (32 + XPAD), "k-major plane must fit the row-major plane storage");
-typedef short v4i16 __attribute__((ext_vector_type(4)));
-template <bool VEC>
-DEV void xt_load(f32x4_t (&v)[2][2], const float* base, int64_t ld, int o0, int on, int k0, int ke) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int e = threadIdx.x + 256 * q;
-        const int k = k0 + (e >> 5), o = o0 + (e & 31) * 4;
-        const float* row = k < ke ? base + (int64_t)k * ld : nullptr;
-        v[q >> 1][q & 1] = load4v<VEC>(row, o, on);
-    }
-}
-DEV void xt_store(uint16_t (*lds)[BM][32 + XPAD], const f32x4_t (&v)[2][2], float sc) {
-    uint16_t* ph = &lds[0][0][0];
-    uint16_t* pl = &lds[1][0][0];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int e = threadIdx.x + 256 * q;
-        const int off = (e >> 5) * TPITCH + (e & 31) * 4;
-        const f32x4_t x = v[q >> 1][q & 1];
-        uint32_t h2[2], l2[2];
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const float x0 = x[2 * c] * sc, x1 = x[2 * c + 1] * sc;
-            const uint16_t h0 = f2hf(x0), h1 = f2hf(x1);
-            h2[c] = pack_h2(h0, h1);
-            l2[c] = pack_h2(f2hf(x0 - hf2f(h0)), f2hf(x1 - hf2f(h1)));
-        }
-        *reinterpret_cast<uint2*>(ph + off) = make_uint2(h2[0], h2[1]);
-        *reinterpret_cast<uint2*>(pl + off) = make_uint2(l2[0], l2[1]);
-    }
-}
-// the 32x32x16 operand fragment of output rows ob .. ob+31 at k = kof0 + 8 (lane >> 5) + 0..7
-DEV h16x8 tr_frag(const uint16_t* plane, int ob, int kof0, int lane) {
-    const int g = lane >> 4, i = lane & 15;
-    const int o = ob + 16 * (g & 1) + 4 * (i & 3);
-    const int k = kof0 + 8 * (g >> 1) + (i >> 2);
-    typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
-    const v4i16 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(plane + k * TPITCH + o));
-    const v4i16 y = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(plane + (k + 4) * TPITCH + o));
-    typedef short v8i16 __attribute__((ext_vector_type(8)));
-    const v8i16 r = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-    return __builtin_bit_cast(h16x8, r);
-}
-
-// The H3 products of one 16-deep k step of a wave's 64 x (32 NJ) tile, from its fragments a / b [plane][block]:
-// one accumulator: the corrections, then the leading product, enter the running f32 sum (the rounding count of
-// an f32 FMA chain; a separate correction accumulator would cost 64 registers that the deeper stage uses instead)
-template <int NJ>
-DEV void h3_mfma_step(const h16x8 (&a)[2][2], const h16x8 (&b)[2][NJ], f32x16 (&acc)[2][NJ]) {
-#pragma unroll
-    for (int ti = 0; ti < 2; ti++)
-#pragma unroll
-        for (int tj = 0; tj < NJ; tj++) {
-            f32x16 c = acc[ti][tj];
-            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][ti], b[0][tj], c, 0, 0, 0);  // l h
-            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[1][tj], c, 0, 0, 0);  // h l
-            acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[0][tj], c, 0, 0, 0);  // h h
-        }
-}
-template <int XK, bool TA = false, bool TB = false, int P = XK + XPAD>
+// The same for H3; TA / TB: that operand's planes are k-major (the wave's 32-row block base is ra & ~31)
+template <bool TA = false, bool TB = false, int P = XK + XPAD>
 DEV void h3_mfma_stage(const uint16_t (*As)[BM][P], const uint16_t (*Bs)[BN][P], int ra, int rb, int lane,
-                       f32x16 (&acc)[2][2], f32x16 (&cor)[2][2]) {
+                       f32x16 (&acc)[2][2]) {
+    constexpr int TP = kt_pitch(BM);
 #pragma unroll
     for (int ks = 0; ks < XK / 16; ks++) {
         const int kc = 2 * ks + (lane >> 5);  // logical 16-byte chunk of this lane's 8 k
@@ -647,27 +686,28 @@ DEV void h3_mfma_stage(const uint16_t (*As)[BM][P], const uint16_t (*Bs)[BN][P],
         for (int p = 0; p < 2; p++)
 #pragma unroll
             for (int u = 0; u < 2; u++) {
-                // ra / rb: this lane's row; (ra & ~31) the wave's 32-row block base
-                a[p][u] = TA ? tr_frag(&As[p][0][0], (ra & ~31) + 32 * u, ks * 16, lane)
-                             : *(const h16x8*)&As[p][ra + 32 * u][xchunk<P, XK>(ra + 32 * u, kc) * 8];
-                b[p][u] = TB ? tr_frag(&Bs[p][0][0], (rb & ~31) + 32 * u, ks * 16, lane)
-                             : *(const h16x8*)&Bs[p][rb + 32 * u][xchunk<P, XK>(rb + 32 * u, kc) * 8];
+                a[p][u] = TA ? tr_frag<TP>(&As[p][0][0], (ra & ~31) + 32 * u, ks * 16, lane) : kc_frag(As[p], ra + 32 * u, kc);
+                b[p][u] = TB ? tr_frag<TP>(&Bs[p][0][0], (rb & ~31) + 32 * u, ks * 16, lane) : kc_frag(Bs[p], rb + 32 * u, kc);
             }
         h3_mfma_step<2>(a, b, acc);
     }
 }
 
+// gemm_x6 (three bf16 planes) and its H3 form (two fp16 planes): 128 x 128 tiles, XK-deep stages in one LDS
+// buffer, the next stage prefetched into registers while this stage's MFMAs run; two (x6) or three (H3: 146
+// VGPRs, 40 KB LDS) workgroups per CU.  The H3 products are h3_mfma_step's and the H3 epilogue value h3_out's:
+// the other H3 kernels are measured against this one.
 template <int LA, int LB, bool AV, bool BV, bool BPRE, bool H3 = false>
 __global__ void __launch_bounds__(256, 2) gemm_x6(GemmArgs g) {
-    constexpr int XK = 32, NB = 1, NQ = XK / 16, NP = H3 ? 2 : 3;
+    constexpr int NQ = XK / 16, NP = H3 ? 2 : 3;
     constexpr bool AK = LA == A_IK, BKM = LB == B_JK;
-    // H3 with 32-deep stages: row-index-contiguous operands staged k-major (xt_load / tr_frag)
-    constexpr bool TA = H3 && !AK && XK == 32, TB = H3 && !BPRE && !BKM && XK == 32;
+    // H3: row-index-contiguous operands are staged k-major (kt_load / kt_store / tr_frag)
+    constexpr bool TA = H3 && !AK, TB = H3 && !BPRE && !BKM;
     // H3 with both operands k-contiguous, default variant: unpadded XOR-swizzled planes (xchunk)
     constexpr bool SWZ = H3 && !TA && !TB;
     constexpr int P = SWZ ? XK : XK + XPAD;
-    __shared__ uint16_t As[NB][NP][BM][P];
-    __shared__ uint16_t Bs[NB][NP][BN][P];
+    __shared__ uint16_t As[NP][BM][P];
+    __shared__ uint16_t Bs[NP][BN][P];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int wm = w >> 1, wn = w & 1;
     const Tile tl = xcd_tile(g.gx, g.gy, g.gz);
@@ -691,54 +731,54 @@ __global__ void __launch_bounds__(256, 2) gemm_x6(GemmArgs g) {
         if (!BPRE) pb = h3_pow(shard_max_bits(g.amax_b));
     }
     const float sa = pow2f(pa), sb = pow2f(pb);
-    const RowPtrs arow = xs_rows<AK, XK>(g.A, g.lda, i0, g.I);
-    const RowPtrs brow = xs_rows<BKM, XK>(g.B, g.ldb, j0, g.J);
+    const RowPtrs arow = xs_rows<AK>(g.A, g.lda, i0, g.I);
+    const RowPtrs brow = xs_rows<BKM>(g.B, g.ldb, j0, g.J);
     auto load_stage = [&](int k0) {
         if constexpr (TA)
-            xt_load<AV>(va, g.A, g.lda, i0, g.I, k0, ke);
+            kt_load<256, BM, AV>(va, g.A, g.lda, i0, g.I, k0, ke);
         else
-            xs_load<AK, AV, XK>(va, arow, g.A, g.lda, i0, g.I, k0, ke);
+            xs_load<AK, AV>(va, arow, g.A, g.lda, i0, g.I, k0, ke);
         if (BPRE)
-            xp_load<XK, NP>(vp, Bp, g.ldb, g.bplane, j0, k0, ke);
+            xp_load<NP>(vp, Bp, g.ldb, g.bplane, j0, k0, ke);
         else if constexpr (TB)
-            xt_load<BV>(vb, g.B, g.ldb, j0, g.J, k0, ke);
+            kt_load<256, BN, BV>(vb, g.B, g.ldb, j0, g.J, k0, ke);
         else
-            xs_load<BKM, BV, XK>(vb, brow, g.B, g.ldb, j0, g.J, k0, ke);
+            xs_load<BKM, BV>(vb, brow, g.B, g.ldb, j0, g.J, k0, ke);
     };
     const int ra = wm * 64 + (lane & 31), rb = wn * 64 + (lane & 31);
-    auto store_stage = [&](int buf) {
+    auto store_stage = [&]() {
         if constexpr (TA)
-            xt_store(As[buf], va, sa);
+            kt_store<256, BM>(&As[0][0][0], &As[1][0][0], va, sa);
         else
-            xs_store<AK, XK, H3, P>(As[buf], va, sa);
+            xs_store<AK, H3, P>(As, va, sa);
         if (BPRE)
-            xp_store<XK, NP, P>(Bs[buf], vp);
+            xp_store<NP, P>(Bs, vp);
         else if constexpr (TB)
-            xt_store(Bs[buf], vb, sb);
+            kt_store<256, BN>(&Bs[0][0][0], &Bs[1][0][0], vb, sb);
         else
-            xs_store<BKM, XK, H3, P>(Bs[buf], vb, sb);
+            xs_store<BKM, H3, P>(Bs, vb, sb);
     };
-    auto mfma_stage = [&](int buf) {
+    auto mfma_stage = [&]() {
         if constexpr (H3)
-            h3_mfma_stage<XK, TA, TB, P>(As[buf], Bs[buf], ra, rb, lane, acc, cor);
+            h3_mfma_stage<TA, TB, P>(As, Bs, ra, rb, lane, acc);
         else
-            x6_mfma_stage<XK>(As[buf], Bs[buf], ra, rb, lane, acc, cor);
+            x6_mfma_stage(As, Bs, ra, rb, lane, acc, cor);
     };
     load_stage(kb);
     for (int k0 = kb; k0 < ke; k0 += XK) {
-        store_stage(0);
+        store_stage();
         __syncthreads();
         // prefetch the next stage into registers while the MFMAs run; unconditional (past ke it
         // reads the zero row) so the loop-carried registers are the load destinations
         load_stage(k0 + XK);
         __builtin_amdgcn_sched_barrier(0);  // keep the split of the prefetched stage after the MFMAs
-        mfma_stage(0);
+        mfma_stage();
         __syncthreads();
     }
+    // H3 (h3_out): pa + pb undoes the operand scales; the pre-split B's per-row inverse scale is read for the
+    // tile's columns (rows past J carry 1).  cor stays all zeros in H3, whose corrections enter acc.
     float* C = g.C + (int64_t)tl.z * g.c_split;
     const int h = lane >> 5, l32 = lane & 31;
-    // H3: undo the operand scales (powers of two: exact); the pre-split B's per-row inverse scale
-    // is read for the tile's columns (rows past J carry 1)
     const int pab = pa + pb;
     float csc[2];
 #pragma unroll
@@ -754,7 +794,7 @@ __global__ void __launch_bounds__(256, 2) gemm_x6(GemmArgs g) {
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
                     const float v = acc[ti][tj][r] + cor[ti][tj][r];
-                    ct[(int64_t)((r & 3) + 8 * (r >> 2)) * g.ldc] = (H3 ? ldexpf(v * csc[tj], -pab) : v) + bj;
+                    ct[(int64_t)acc_row(r, 0) * g.ldc] = H3 ? h3_out(v, csc[tj], pab, bj) : v + bj;
                 }
             }
         return;
@@ -768,42 +808,26 @@ __global__ void __launch_bounds__(256, 2) gemm_x6(GemmArgs g) {
             float bj = g.bias ? g.bias[j] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                int i = i0 + wm * 64 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                int i = acc_row(r, h, i0 + wm * 64 + ti * 32);
                 const float v = acc[ti][tj][r] + cor[ti][tj][r];
-                if (i < g.I) C[(int64_t)i * g.ldc + j] = (H3 ? ldexpf(v * csc[tj], -pab) : v) + bj;
+                if (i < g.I) C[(int64_t)i * g.ldc + j] = H3 ? h3_out(v, csc[tj], pab, bj) : v + bj;
             }
         }
 }
 
 // weight planes are padded to whole 256-row blocks (the 256 x 256 tiles of gemm_h3q / gemm_h3qt)
 constexpr int BNW = 2 * BN;
-// tr_frag over a k-major plane of row pitch P halves (P = COLS + 32: conflict-free, see TPITCH)
-template <int P>
-DEV h16x8 trp_frag(const uint16_t* plane, int ob, int kof0, int lane) {
-    const int g = lane >> 4, i = lane & 15;
-    const int o = ob + 16 * (g & 1) + 4 * (i & 3);
-    const int k = kof0 + 8 * (g >> 1) + (i >> 2);
-    typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
-    const v4i16 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(plane + k * P + o));
-    const v4i16 y = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(plane + (k + 4) * P + o));
-    typedef short v8i16 __attribute__((ext_vector_type(8)));
-    const v8i16 r = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-    return __builtin_bit_cast(h16x8, r);
-}
 
 // ---- H3 GEMM with 256 x 256 tiles (gemm_h3q): the forward and input-gradient GEMMs (A_IK fp32 x the
 // pre-split fp16 B planes, J a multiple of 256).  The 128 x 128 tile reads 32 KB from L2 per 128 x 128 x 32
 // stage; at ~70 GB/s of L2 per CU (MI355X_MICROARCH.md, "Indexed rows") three such workgroups per CU need
 // more feed cycles than their MFMAs take, so the stage skeleton, not the matrix pipe, sets gemm_x6's time.
 // A 256 x 256 tile halves the L2 bytes per product.  8 waves (512 threads, one workgroup per CU, two waves
-// per SIMD), each 64 x 128 (2 x 4 MFMA blocks); double-buffered LDS (2 x 64 KB) with one barrier per stage:
-// this stage's MFMAs run on one buffer while the next stage (in registers since the previous iteration)
-// is split into the other and the stage after is loaded.  Per 16-deep k step and block the products enter
-// the one accumulator as l.h, h.l, h.h -- gemm_x6's H3 order -- so the results are bit-identical to it.
+// per SIMD), each 64 x 128 (2 x 4 MFMA blocks); double-buffered LDS (2 x 64 KB), see the K loop below.  A is
+// staged as in gemm_x6's swizzled variant (kc_load / kc_store / kc_frag); products by h3_mfma_step, one K chunk.
 constexpr int BQ = 256;
 template <bool AV>
 __global__ void __launch_bounds__(512, 1) gemm_h3q(GemmArgs g) {
-    constexpr int XK = 32, KG = XK / 8;
     __shared__ uint16_t As[2][2][BQ][XK];  // [buffer][plane][row][k], 16-byte chunks XOR-swizzled (xchunk)
     __shared__ uint16_t Bs[2][2][BQ][XK];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -812,21 +836,16 @@ __global__ void __launch_bounds__(512, 1) gemm_h3q(GemmArgs g) {
     const int i0 = tl.y * BQ, j0 = tl.x * BQ;
     const int ke = g.K;
     f32x16 acc[2][4];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
-    // this thread's share of a stage: A groups e = t + 512 q (row e / KG, k group e % KG), 8 floats each;
+    zero_acc(acc);
+    // this thread's share of a stage: A groups e = t + 512 q (row e / XKG, k group e % XKG), 8 floats each;
     // B chunks of the same (row, k group) in both planes
     const float* arow[2];
 #pragma unroll
     for (int q = 0; q < 2; q++) {
-        const int gi = i0 + (t + 512 * q) / KG;
+        const int gi = i0 + (t + 512 * q) / XKG;
         arow[q] = gi < g.I ? g.A + (int64_t)gi * g.lda : nullptr;
     }
-    const int kg = t % KG;
+    const int kg = t % XKG;
     f32x4_t va[2][2];
     u32x4_t vp[2][2];
     const uint16_t* Bp = reinterpret_cast<const uint16_t*>(g.B);
@@ -837,9 +856,8 @@ __global__ void __launch_bounds__(512, 1) gemm_h3q(GemmArgs g) {
         const bool ok = kk < ke;
 #pragma unroll
         for (int q = 0; q < 2; q++) {
-            va[q][0] = load4v<AV>(arow[q], kk, ke);
-            va[q][1] = load4v<AV>(arow[q], kk + 4, ke);
-            const int64_t off = (int64_t)(j0 + (t + 512 * q) / KG) * g.ldb + kk;
+            kc_load<AV>(va[q], arow[q], kk, ke);
+            const int64_t off = (int64_t)(j0 + (t + 512 * q) / XKG) * g.ldb + kk;
 #pragma unroll
             for (int p = 0; p < 2; p++)
                 vp[p][q] = *reinterpret_cast<const u32x4_t*>(ok ? Bp + p * g.bplane + off
@@ -849,11 +867,8 @@ __global__ void __launch_bounds__(512, 1) gemm_h3q(GemmArgs g) {
     auto store_stage = [&](int buf) {
 #pragma unroll
         for (int q = 0; q < 2; q++) {
-            const int row = (t + 512 * q) / KG, c = xchunk<XK, XK>(row, kg) * 8;
-            u32x4_t h, l;
-            split2h(va[q], sa, h, l);
-            *reinterpret_cast<u32x4_t*>(&As[buf][0][row][c]) = h;
-            *reinterpret_cast<u32x4_t*>(&As[buf][1][row][c]) = l;
+            const int row = (t + 512 * q) / XKG, c = xchunk<XK>(row, kg) * 8;
+            kc_store(As[buf], va[q], sa, row, kg);
 #pragma unroll
             for (int p = 0; p < 2; p++) *reinterpret_cast<u32x4_t*>(&Bs[buf][p][row][c]) = vp[p][q];
         }
@@ -867,23 +882,15 @@ __global__ void __launch_bounds__(512, 1) gemm_h3q(GemmArgs g) {
 #pragma unroll
             for (int p = 0; p < 2; p++) {
 #pragma unroll
-                for (int u = 0; u < 2; u++)
-                    a[p][u] = *(const h16x8*)&As[buf][p][ra + 32 * u][xchunk<XK, XK>(ra + 32 * u, kc) * 8];
+                for (int u = 0; u < 2; u++) a[p][u] = kc_frag(As[buf][p], ra + 32 * u, kc);
 #pragma unroll
-                for (int u = 0; u < 4; u++)
-                    b[p][u] = *(const h16x8*)&Bs[buf][p][rb + 32 * u][xchunk<XK, XK>(rb + 32 * u, kc) * 8];
+                for (int u = 0; u < 4; u++) b[p][u] = kc_frag(Bs[buf][p], rb + 32 * u, kc);
             }
-#pragma unroll
-            for (int ti = 0; ti < 2; ti++)
-#pragma unroll
-                for (int tj = 0; tj < 4; tj++) {
-                    f32x16 c = acc[ti][tj];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][ti], b[0][tj], c, 0, 0, 0);  // l h
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[1][tj], c, 0, 0, 0);  // h l
-                    acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[0][tj], c, 0, 0, 0);  // h h
-                }
+            h3_mfma_step<4>(a, b, acc);
         }
     };
+    // The two-buffer K loop, one barrier per stage: this stage's MFMAs run on one buffer while the next stage (in
+    // registers since the previous iteration) is split into the other and the stage after is loaded.
     load_stage(0);
     store_stage(0);
     __syncthreads();
@@ -906,47 +913,18 @@ __global__ void __launch_bounds__(512, 1) gemm_h3q(GemmArgs g) {
         for (int ti = 0; ti < 2; ti++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int i = i0 + wm * 64 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (i < g.I) g.C[(int64_t)i * g.ldc + j] = ldexpf(acc[ti][tj][r] * bsc, -pa) + bj;
+                const int i = acc_row(r, h, i0 + wm * 64 + ti * 32);
+                if (i < g.I) g.C[(int64_t)i * g.ldc + j] = h3_out(acc[ti][tj][r], bsc, pa, bj);
             }
     }
 }
 
 // ---- gemm_h3q's weight-gradient form (gemm_h3qt): A_KI (dZ^T) x B_KJ (activations), both row-index
-// contiguous, staged k-major (float4 loads along the output index, planes [k][256 + 32],
-// fragments read back with ds_read_b64_tr_b16); split-K over grid z like the other kernels.  Same products in
-// the same order per split as gemm_x6: bit-identical partials.
-template <bool VEC>
-DEV void q_kload(f32x4_t (&v)[4], const float* base, int64_t ld, int o0, int on, int k0, int ke) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {  // element group e = t + 512 q: k row e / 64, float4 e % 64 of the 256 columns
-        const int e = (int)threadIdx.x + 512 * q;
-        const int k = k0 + e / 64, o = o0 + (e % 64) * 4;
-        const float* row = k < ke ? base + (int64_t)k * ld : nullptr;
-        v[q] = load4v<VEC>(row, o, on);
-    }
-}
-DEV void q_kstore(uint16_t* ph, uint16_t* pl, const f32x4_t (&v)[4], float sc) {
-    constexpr int P = BQ + 32;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int e = (int)threadIdx.x + 512 * q;
-        const int off = (e / 64) * P + (e % 64) * 4;
-        uint32_t h2[2], l2[2];
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const float x0 = v[q][2 * c] * sc, x1 = v[q][2 * c + 1] * sc;
-            const uint16_t h0 = f2hf(x0), h1 = f2hf(x1);
-            h2[c] = pack_h2(h0, h1);
-            l2[c] = pack_h2(f2hf(x0 - hf2f(h0)), f2hf(x1 - hf2f(h1)));
-        }
-        *reinterpret_cast<uint2*>(ph + off) = make_uint2(h2[0], h2[1]);
-        *reinterpret_cast<uint2*>(pl + off) = make_uint2(l2[0], l2[1]);
-    }
-}
+// contiguous, staged k-major (kt_load / kt_store / tr_frag, planes [k][256 + 32]); split-K over grid z like
+// gemm_x6, whose partials it reproduces per split (h3_mfma_step).
 template <bool AV, bool BV>
 __global__ void __launch_bounds__(512, 1) gemm_h3qt(GemmArgs g) {
-    constexpr int XK = 32, P = BQ + 32;
+    constexpr int P = kt_pitch(BQ);
     __shared__ uint16_t As[2][2][XK * P];  // [buffer][plane][k][o]
     __shared__ uint16_t Bs[2][2][XK * P];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -956,22 +934,17 @@ __global__ void __launch_bounds__(512, 1) gemm_h3qt(GemmArgs g) {
     const int kb = tl.z * g.kchunk;
     const int ke = min(g.K, kb + g.kchunk);
     f32x16 acc[2][4];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
-    f32x4_t va[4], vb[4];
+    zero_acc(acc);
+    f32x4_t va[2][2], vb[2][2];
     const int pa = h3_pow(shard_max_bits(g.amax_a)), pb = h3_pow(shard_max_bits(g.amax_b));
     const float sa = pow2f(pa), sb = pow2f(pb);
     auto load_stage = [&](int k0) {
-        q_kload<AV>(va, g.A, g.lda, i0, g.I, k0, ke);
-        q_kload<BV>(vb, g.B, g.ldb, j0, g.J, k0, ke);
+        kt_load<512, BQ, AV>(va, g.A, g.lda, i0, g.I, k0, ke);
+        kt_load<512, BQ, BV>(vb, g.B, g.ldb, j0, g.J, k0, ke);
     };
     auto store_stage = [&](int buf) {
-        q_kstore(&As[buf][0][0], &As[buf][1][0], va, sa);
-        q_kstore(&Bs[buf][0][0], &Bs[buf][1][0], vb, sb);
+        kt_store<512, BQ>(&As[buf][0][0], &As[buf][1][0], va, sa);
+        kt_store<512, BQ>(&Bs[buf][0][0], &Bs[buf][1][0], vb, sb);
     };
     auto mfma_stage = [&](int buf) {
 #pragma unroll
@@ -980,22 +953,14 @@ __global__ void __launch_bounds__(512, 1) gemm_h3qt(GemmArgs g) {
 #pragma unroll
             for (int p = 0; p < 2; p++) {
 #pragma unroll
-                for (int u = 0; u < 2; u++) a[p][u] = trp_frag<P>(&As[buf][p][0], wm * 64 + 32 * u, ks * 16, lane);
+                for (int u = 0; u < 2; u++) a[p][u] = tr_frag<P>(&As[buf][p][0], wm * 64 + 32 * u, ks * 16, lane);
 #pragma unroll
-                for (int u = 0; u < 4; u++) b[p][u] = trp_frag<P>(&Bs[buf][p][0], wn * 128 + 32 * u, ks * 16, lane);
+                for (int u = 0; u < 4; u++) b[p][u] = tr_frag<P>(&Bs[buf][p][0], wn * 128 + 32 * u, ks * 16, lane);
             }
-#pragma unroll
-            for (int ti = 0; ti < 2; ti++)
-#pragma unroll
-                for (int tj = 0; tj < 4; tj++) {
-                    f32x16 c = acc[ti][tj];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][ti], b[0][tj], c, 0, 0, 0);  // l h
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[1][tj], c, 0, 0, 0);  // h l
-                    acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ti], b[0][tj], c, 0, 0, 0);  // h h
-                }
+            h3_mfma_step<4>(a, b, acc);
         }
     };
-    load_stage(kb);
+    load_stage(kb);  // gemm_h3q's two-buffer K loop over this split's chunk
     store_stage(0);
     __syncthreads();
     load_stage(kb + XK);  // unconditional: past ke it reads the zero row
@@ -1019,11 +984,12 @@ __global__ void __launch_bounds__(512, 1) gemm_h3qt(GemmArgs g) {
         for (int ti = 0; ti < 2; ti++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int i = i0 + wm * 64 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (i < g.I) C[(int64_t)i * g.ldc + j] = ldexpf(acc[ti][tj][r] * 1.f, -pab) + bj;
+                const int i = acc_row(r, h, i0 + wm * 64 + ti * 32);
+                if (i < g.I) C[(int64_t)i * g.ldc + j] = h3_out(acc[ti][tj][r], 1.f, pab, bj);
             }
     }
 }
+
 
 // ---- bf16 inference GEMM: C[i,j] = bf16( sum_k A[i,k] W[j,k] + bias[j] ) on
 // v_mfma_f32_32x32x16_bf16 (fp32 accumulate).  A [I][lda] and W [J][ldb] bf16, k contiguous,
@@ -1088,9 +1054,7 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16(HGemmArgs g) {
         brow[q] = j0 + rr < g.J ? g.B + (int64_t)(j0 + rr) * g.ldb : nullptr;
     }
     f32x16 acc[2][2];
-    for (int a = 0; a < 2; a++)
-        for (int b = 0; b < 2; b++)
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
+    zero_acc(acc);
     u32x4 ra[HQ], rb[HQ];
     htile_load(ra, arow, 0, g.K);
     htile_load(rb, brow, 0, g.K);
@@ -1125,7 +1089,7 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16(HGemmArgs g) {
             float bj = g.bias ? h2f<F16>(g.bias[j]) : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                int i = i0 + wm * 64 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                int i = acc_row(r, lane >> 5, i0 + wm * 64 + ti * 32);
                 if (i < g.I) g.C[(int64_t)i * g.ldc + j] = f2h<F16>(acc[ti][tj][r] + bj);
             }
         }
@@ -1385,8 +1349,8 @@ __global__ void __launch_bounds__(256) ln_act_fwd_f32(const float* Z, const floa
 // in fragment order (frag_weight_h3's copy of the split planes: each load instruction of a wave is one
 // contiguous 1 KB), one 16-deep k step ahead of the MFMAs that use them.  A: 32-deep stages, split into two
 // XOR-swizzled fp16 planes in a double-buffered LDS stage (one barrier per stage), the next stage prefetched
-// into registers.  Per 16-k step the products enter the one accumulator as l.h, h.l, h.h (h3_mfma_step), one K
-// chunk, and the epilogue value is gemm_x6's ldexpf(v * csc, -pa) + bias.  The finished z rows are staged in
+// into registers.  The products are h3_mfma_step's, one K chunk, and the epilogue value is h3_out's with
+// gemm_x6's arguments.  The finished z rows are staged in
 // LDS, 32 rows at a time (pitch 520 floats: the two half-waves of an accumulator store land on disjoint
 // banks), and each wave takes whole rows from there in lcol layout: it writes z (the backward recomputes xhat
 // from it) and runs lnf_rows, ln_act_fwd_f32's arithmetic.  Same bits as the two-kernel path.  65 KB LDS and
@@ -1421,9 +1385,8 @@ struct RowLnArgs {
 // the A stages in smem are free.
 // g.B: the fragment-order planes; g.ldb: their k extent (a multiple of 32, at least K rounded up to 32)
 DEV int h3_row_kloop(const GemmArgs& g, unsigned char* smem, f32x16 (&acc)[2][4]) {
-    constexpr int XK = 32, KG = XK / 8;
     constexpr int KSTEP = (RLN_J / 32) * 2 * 64 * 8;  // halves per k step of the fragment-order planes
-    auto As = reinterpret_cast<uint16_t (*)[2][RLN_BM][XK]>(smem);  // [buffer][plane][row][k]
+    auto As = reinterpret_cast<uint16_t (*)[2][RLN_BM][XK]>(smem);  // [buffer][plane][row][k], swizzled (xchunk)
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int i0 = blockIdx.x * RLN_BM;
     const int ke = g.K;
@@ -1433,12 +1396,13 @@ DEV int h3_row_kloop(const GemmArgs& g, unsigned char* smem, f32x16 (&acc)[2][4]
         for (int b = 0; b < 4; b++)
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
-    // this thread's share of an A stage: row t / KG, k group t % KG (8 floats)
-    const int srow = t / KG, kg = t % KG;
+    // this thread's share of an A stage: row t / XKG, k group t % XKG (8 floats)
+    const int srow = t / XKG, kg = t % XKG;
     const float* arow = i0 + srow < g.I ? g.A + (int64_t)(i0 + srow) * g.lda : nullptr;
     f32x4_t va[2];
     const int pa = h3_pow(shard_max_bits(g.amax_a));
     const float sa = pow2f(pa);
+    // kc_load / kc_store written out (through the helpers this kernel's schedule and register count move)
     auto load_a = [&](int k0) {  // past K it reads the zero row
         va[0] = load4v<true>(arow, k0 + kg * 8, ke);
         va[1] = load4v<true>(arow, k0 + kg * 8 + 4, ke);
@@ -1446,7 +1410,7 @@ DEV int h3_row_kloop(const GemmArgs& g, unsigned char* smem, f32x16 (&acc)[2][4]
     auto store_a = [&](int buf) {
         u32x4_t h, l;
         split2h(va, sa, h, l);
-        const int c = xchunk<XK, XK>(srow, kg) * 8;
+        const int c = xchunk<XK>(srow, kg) * 8;
         *reinterpret_cast<u32x4_t*>(&As[buf][0][srow][c]) = h;
         *reinterpret_cast<u32x4_t*>(&As[buf][1][srow][c]) = l;
     };
@@ -1467,7 +1431,7 @@ DEV int h3_row_kloop(const GemmArgs& g, unsigned char* smem, f32x16 (&acc)[2][4]
 #pragma unroll
         for (int p = 0; p < 2; p++)
 #pragma unroll
-            for (int u = 0; u < 2; u++) a[p][u] = *(const h16x8*)&As[buf][p][l32 + 32 * u][xchunk<XK, XK>(l32 + 32 * u, kc) * 8];
+            for (int u = 0; u < 2; u++) a[p][u] = kc_frag(As[buf][p], l32 + 32 * u, kc);
         h3_mfma_step<4>(a, b, acc);
     };
     h16x8 b0[2][4], b1[2][4];
@@ -1504,7 +1468,7 @@ __global__ void __launch_bounds__(256, 2) gemm_h3_rowln(GemmArgs g, RowLnArgs ln
     const int l32 = lane & 31, hh = lane >> 5;
     f32x16 acc[2][4];
     const int pa = h3_row_kloop(g, smem, acc);
-    // epilogue: z = ldexpf(v * csc, -pa) + bias into the LDS stage, then LayerNorm + LeakyReLU per row
+    // epilogue: z (h3_out) into the LDS stage, then LayerNorm + LeakyReLU per row
     float csc[4], bj[4];
 #pragma unroll
     for (int tj = 0; tj < 4; tj++) {
@@ -1522,8 +1486,9 @@ __global__ void __launch_bounds__(256, 2) gemm_h3_rowln(GemmArgs g, RowLnArgs ln
         for (int tj = 0; tj < 4; tj++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const float v = acc[ti][tj][r] + 0.f;  // gemm_x6's sum with its (zero) correction accumulator
-                zs[((r & 3) + 8 * (r >> 2) + 4 * hh) * RLN_ZP + w * 128 + tj * 32 + l32] = ldexpf(v * csc[tj], -pa) + bj[tj];
+                const float v = acc[ti][tj][r] + 0.f;  // gemm_x6's sum with its zero correction accumulator (h3_out)
+                // row acc_row(r, hh), written out (the call moves this kernel's schedule)
+                zs[((r & 3) + 8 * (r >> 2) + 4 * hh) * RLN_ZP + w * 128 + tj * 32 + l32] = h3_out(v, csc[tj], pa, bj[tj]);
             }
         __syncthreads();
         for (int b0 = 0; b0 < 32 / 4; b0 += RF) {  // this wave's 8 rows of the half, RF at a time
@@ -1802,7 +1767,7 @@ __global__ void __launch_bounds__(256) ln_act_bwd(const float* dA, const float* 
 // ---- Full-row H3 input-gradient GEMM with the LayerNorm + LeakyReLU backward of the layer below in the same
 // launch (gemm_h3_row_lnbwd): a gemm_x6<A_IK, B_JK, pre-split B, H3> dA GEMM of 512 output columns + the
 // ln_act_bwd<8> that reads it.  gemm_h3_rowln's tile, prologue and K loop (h3_row_kloop) on the fragment-order
-// copy of the layer's backward planes; the epilogue value is gemm_x6's ldexpf(v * csc, -pa) + 0 (no bias).
+// copy of the layer's backward planes; the epilogue value is h3_out's with gemm_x6's arguments (no bias: 0.f).
 // The finished dA rows are staged in LDS, 32 rows at a time, and never reach memory: each wave takes whole
 // rows from the stage in lcol layout, loads the matching z row and (mean, rstd), and runs lnb_row.  The 32-row
 // half is one ln_act_bwd<8> block: wave w takes the rows w, w + 4, ... of the half in ascending order, the four
@@ -1849,8 +1814,8 @@ __global__ void __launch_bounds__(256, 2) gemm_h3_row_lnbwd(GemmArgs g, RowLnBwd
         for (int tj = 0; tj < 4; tj++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const float v = acc[ti][tj][r] + 0.f;  // gemm_x6's sum with its (zero) correction accumulator
-                zs[((r & 3) + 8 * (r >> 2) + 4 * hh) * RLN_ZP + w * 128 + tj * 32 + l32] = ldexpf(v * csc[tj], -pa) + 0.f;
+                const float v = acc[ti][tj][r] + 0.f;  // as in gemm_h3_rowln
+                zs[((r & 3) + 8 * (r >> 2) + 4 * hh) * RLN_ZP + w * 128 + tj * 32 + l32] = h3_out(v, csc[tj], pa, 0.f);
             }
         __syncthreads();
         float lg[MAXH], lb[MAXH], pg[MAXH], pb[MAXH], pz[MAXH], ph[MAXH];
