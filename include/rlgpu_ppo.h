@@ -133,7 +133,8 @@ int rlgpu_kernel_timing_read(double* ms, double* work, int64_t* count, int32_t n
  * model 2 is the shared head alone (out_size = its last width).
  * The 16-bit inference (this, rlgpu_ppo_infer_actions*, rlgpu_ppo_infer_critic) runs as one fused
  * kernel per call when every layer fits it (inputs / hidden widths <= 512, outputs <= 128); the
- * environment variable RLGPU_FUSED_INFER=0 selects the layer-by-layer kernels, same results. */
+ * environment variable RLGPU_FUSED_INFER=0 (read on every call) selects the layer-by-layer kernels, same
+ * results. */
 int rlgpu_ppo_forward(rlgpu_ppo* h, int32_t model, int32_t precision, const float* d_in, int32_t n,
                       float* d_out, void* stream);
 
@@ -164,7 +165,7 @@ int rlgpu_ppo_infer_actions_rows(rlgpu_ppo* h, const float* d_obs, const uint8_t
                                  int32_t* d_actions, float* d_logp, void* stream);
 /* 1 when model `model` (0 policy, 1 critic) runs on the fused inference kernel, else 0. */
 int rlgpu_ppo_fused_infer(rlgpu_ppo* h, int32_t model);
-/* InferCriticBatched: bf16 critic forward over n rows (any n; chunked by max_rows). */
+/* InferCriticBatched: bf16 critic forward over n rows (any n; off the fused kernel in chunks of max_rows). */
 int rlgpu_ppo_infer_critic(rlgpu_ppo* h, const float* d_obs, int64_t n, float* d_values, void* stream);
 
 /* Mean and unbiased std of d_x[n] into d_out[2] (batch advantage normalisation,

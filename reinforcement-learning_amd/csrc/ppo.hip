@@ -72,6 +72,11 @@ struct Model {
     float* amax = nullptr;
     float* dX = nullptr;  // gradient w.r.t. the model input (policy / critic behind a shared head)
 };
+// One Linear layer of a model's 16-bit inference forward (rlgpu_ppo::chain)
+struct Link {
+    const Layer* L;
+    bool hidden;  // [Linear -> LayerNorm -> LeakyReLU]; false: the output Linear
+};
 // hidden [Linear -> LayerNorm -> LeakyReLU] layers of a model (all of the shared head's)
 inline int nhid(const Model& m) { return (int)m.L.size() - (m.head_only ? 0 : 1); }
 constexpr int kAmaxDZ = RLGPU_MAX_LAYERS, kAmaxOut = 2 * RLGPU_MAX_LAYERS, kAmaxSlots = 2 * RLGPU_MAX_LAYERS + 1;
@@ -171,6 +176,12 @@ struct rlgpu_ppo {
     int xh_ld = 0;
     uint16_t *zh = nullptr, *ah[2] = {nullptr, nullptr}, *logits_h = nullptr;
     float* logits_f = nullptr;  // fp32 inference (RLGPU_INFER_F32): the policy's logits [max_rows][A]
+    // The Linear layers a 16-bit forward of model mi runs through: the shared head's first (for the policy / critic), then
+    // the model's -- Model::Forward chained as InferPolicyProbsFromModels / InferCritic do (PPOLearner.cpp:90-91,188-191).
+    // The shared head's f32 output re-enters the policy as bf16 (Models.cpp:64), which is exact, so the chain is one 16-bit
+    // network.  Built once, at the end of rlgpu_ppo_create (build_chains): the Layer vectors do not move afterwards.
+    std::vector<Link> chain[3];
+    bool fused_fit[3] = {false, false, false};  // chain[mi]'s widths fit the fused inference kernel
     std::vector<void*> allocs;
 
     template <class T>
@@ -653,39 +664,18 @@ void gather_obs(rlgpu_ppo* h, const float* obs, const int32_t* idx, int64_t star
     RLGPU_CHECK_HIP(hipGetLastError());
 }
 
-// The Linear layers a 16-bit forward of model mi runs through: the shared head's first (for the
-// policy / critic), then the model's -- Model::Forward chained as InferPolicyProbsFromModels /
-// InferCritic do (PPOLearner.cpp:90-91,188-191).  The shared head's f32 output re-enters the policy
-// as bf16 (Models.cpp:64), which is exact, so the chain is one 16-bit network.
-struct Link {
-    const Layer* L;
-    bool hidden;  // [Linear -> LayerNorm -> LeakyReLU]; false: the output Linear
-};
-std::vector<Link> chain(const rlgpu_ppo* h, int mi) {
-    std::vector<Link> c;
-    if (mi != 2 && h->shared())
-        for (auto& L : h->M[2].L) c.push_back({&L, true});
-    const Model& m = h->M[mi];
-    for (size_t l = 0; l < m.L.size(); l++) c.push_back({&m.L[l], m.head_only || l + 1 < m.L.size()});
-    return c;
-}
-
-// bf16 inference forward of n rows through chain(mi); returns the 16-bit result [n, out] (h->logits_h
-// after an output Linear, else the last activation buffer).  Model::Forward with halfPrec
+// bf16 inference forward of n <= max_rows rows through h->chain[mi]; returns the 16-bit result [n, out]
+// (h->logits_h after an output Linear, else the last activation buffer).  Model::Forward with halfPrec
 // (Models.cpp:42-68): every module runs on the bf16 copy, activations rounded to bf16.
 const uint16_t* forward_half(rlgpu_ppo* h, int mi, const float* X, int n, hipStream_t s, const uint16_t* weights = nullptr) {
     const uint16_t* P = weights ? weights : h->half;
-    const auto c = chain(h, mi);
-    {
-        int64_t e = (int64_t)n * h->xh_ld;
-        RLGPU_H16_LAUNCH(f16(h), mlp::rows_to_bf16, dim3(ceil_div(e, 256)), dim3(256), 0, s, X, h->cfg.obs_size, n, h->xh,
-                         h->xh_ld);
-        RLGPU_CHECK_HIP(hipGetLastError());
-    }
+    const int64_t e = (int64_t)n * h->xh_ld;
+    RLGPU_H16_LAUNCH(f16(h), mlp::rows_to_bf16, dim3(ceil_div(e, 256)), dim3(256), 0, s, X, h->cfg.obs_size, n, h->xh, h->xh_ld);
+    RLGPU_CHECK_HIP(hipGetLastError());
     const uint16_t* in = h->xh;
     int64_t ld = h->xh_ld;
     int cur = 0;
-    for (const Link& k : c) {
+    for (const Link& k : h->chain[mi]) {
         const Layer& L = *k.L;
         mlp::HGemmArgs g;
         g.A = in;
@@ -715,32 +705,72 @@ const uint16_t* forward_half(rlgpu_ppo* h, int mi, const float* X, int n, hipStr
     return in;
 }
 
-// Fused inference (infer::mlp_infer): one launch per forward when every layer fits the kernel's
-// LDS tile (inputs / hidden widths <= 512, outputs <= 128); RLGPU_FUSED_INFER=0 selects the
-// layer-by-layer path (forward_half), which computes the same bits.
-unsigned long long* g_infer_trace = nullptr;  // rlgpu_debug_infer_trace
-int64_t g_infer_trace_cap = 0;             // its capacity (uint64 entries)
-bool fused_ok(const rlgpu_ppo* h, int mi) {
-    if (infer_f32(h)) return false;  // fp32 inference runs the training forward (forward_f32)
-    const char* e = getenv("RLGPU_FUSED_INFER");
-    if (e && atoi(e) == 0) return false;
-    const auto c = chain(h, mi);
-    if ((int)c.size() > infer::kMaxLinear || c.back().hidden) return false;  // the kernel ends on an output Linear
-    for (size_t l = 0; l < c.size(); l++) {
-        if (c[l].L->in > infer::IMAX) return false;
-        if (c[l].L->out > (l + 1 < c.size() ? infer::IMAX : infer::IOUT)) return false;
-    }
-    return true;
+// fp32 forward of model 0 or 1 (through the shared head, if any) on n <= max_rows rows of X into out:
+// the training forward's arithmetic (rlgpu_ppo_forward precision 0, and the fp32 inference)
+void forward_f32(rlgpu_ppo* h, int model, const float* X, int n, float* out, hipStream_t s) {
+    gather_obs(h, X, nullptr, 0, n, s);
+    if (h->shared()) forward_train(h, 2, obs_input(h), n, nullptr, s);
+    forward_train(h, model, model_input(h, model), n, out, s);
 }
 
-// one fused forward over n rows of X with the 16-bit copy P: mode 0 writes f32 outputs to out_f,
-// mode 1 samples actions (masks, act, logp; row_sel / sel as ppo::sample_actions)
-void infer_fused(rlgpu_ppo* h, int mi, bool ver, const float* X, int n, int mode, float* out_f,
-                 const uint8_t* masks, int det, uint64_t step, int32_t* act, float* logp, const uint8_t* row_sel, int sel,
-                 hipStream_t s, int64_t row0 = 0) {
-    const auto c = chain(h, mi);
+// ---- inference, one path behind every entry point.  A forward runs as the fp32 training forward (RLGPU_INFER_F32), as
+// one launch of the fused kernel infer::mlp_infer when every layer fits its LDS tile (inputs / hidden widths <= 512,
+// outputs <= 128), or on the layer-by-layer kernels (forward_half), which compute the fused kernel's bits.
+unsigned long long* g_infer_trace = nullptr;  // rlgpu_debug_infer_trace
+int64_t g_infer_trace_cap = 0;             // its capacity (uint64 entries)
+
+// end of rlgpu_ppo_create: the chains, and whether their widths fit the fused kernel, which ends on an output Linear
+void build_chains(rlgpu_ppo* h) {
+    for (int mi = 0; mi < 3; mi++) {
+        auto& c = h->chain[mi];
+        if (mi != 2 && h->shared())
+            for (auto& L : h->M[2].L) c.push_back({&L, true});
+        const Model& m = h->M[mi];
+        for (size_t l = 0; l < m.L.size(); l++) c.push_back({&m.L[l], m.head_only || l + 1 < m.L.size()});
+        bool fit = !c.empty() && (int)c.size() <= infer::kMaxLinear && !c.back().hidden;
+        for (size_t l = 0; fit && l < c.size(); l++)
+            fit = c[l].L->in <= infer::IMAX && c[l].L->out <= (l + 1 < c.size() ? infer::IMAX : infer::IOUT);
+        h->fused_fit[mi] = fit;
+    }
+}
+// Model mi runs on the fused kernel.  RLGPU_FUSED_INFER=0 selects the layer-by-layer path; it is read on every
+// call, not once per handle: tests/test_ppo.py::test_fused_inference_matches_layer_path flips it on a live handle.
+bool fused_ok(const rlgpu_ppo* h, int mi) {
+    if (infer_f32(h) || !h->fused_fit[mi]) return false;  // fp32 inference runs the training forward (forward_f32)
+    const char* e = getenv("RLGPU_FUSED_INFER");
+    return !(e && atoi(e) == 0);
+}
+
+// A block of rows of one inference call: X [n, obs_size], masks [n, num_actions] (null for a forward that draws
+// nothing), and row0, the block's first row in the sampler's row numbering (cfg.sample_row_offset included).
+struct Rows {
+    const float* X;
+    int64_t n, row0;
+    const uint8_t* masks;
+    // rows [b, b + m) of the block: the one place that knows the row strides
+    Rows sub(const rlgpu_ppo_config& c, int64_t b, int64_t m) const {
+        return {X + b * c.obs_size, m, row0 + b, masks ? masks + b * c.num_actions : nullptr};
+    }
+};
+// What a sampling pass does with a block's logits: argmax (det) or the draw of (seed, row, step) into act, its log
+// prob into logp (may be null), for the rows with (row_sel[i] != 0) == (sel != 0) (row_sel null: every row).
+struct Draw {
+    int det;
+    uint64_t step;
+    int32_t* act;
+    float* logp;
+    const uint8_t* row_sel = nullptr;
+    int sel = 0;
+    Draw sub(int64_t b) const { return {det, step, act + b, logp ? logp + b : nullptr, row_sel ? row_sel + b : nullptr, sel}; }
+};
+
+// one fused forward of model mi over a block with the 16-bit copy of the current parameters or (ver) of the old
+// version's: writes f32 outputs to out_f (d null, the kernel's mode 0) or samples actions (d, mode 1)
+void infer_fused(rlgpu_ppo* h, int mi, bool ver, const Rows& r, float* out_f, const Draw* d, hipStream_t s) {
+    const auto& c = h->chain[mi];
+    const int n = (int)r.n;
     infer::InferArgs a{};
-    a.X = X;
+    a.X = r.X;
     a.n = n;
     a.in = h->cfg.obs_size;
     a.P = ver ? h->half_ver : h->half;
@@ -757,23 +787,72 @@ void infer_fused(rlgpu_ppo* h, int mi, bool ver, const float* X, int n, int mode
     }
     a.slope = h->cfg.leaky_slope;
     a.use_ln = h->cfg.layer_norm;
-    a.mode = mode;
-    a.out_f = out_f;
-    a.masks = masks;
-    a.det = det;
     a.seed = h->cfg.seed;
-    a.step = step;
-    a.row0 = row0;
-    a.act = act;
-    a.logp = logp;
-    a.row_sel = row_sel;
-    a.sel = sel;
+    a.out_f = out_f;
+    if (d) {
+        a.mode = 1;
+        a.masks = r.masks;
+        a.row0 = r.row0;
+        a.det = d->det;
+        a.step = d->step;
+        a.act = d->act;
+        a.logp = d->logp;
+        a.row_sel = d->row_sel;
+        a.sel = d->sel;
+    }
     a.trace = g_infer_trace;
     if (a.trace && ceil_div(n, infer::IR) * 16 > g_infer_trace_cap)
         throw rlgpu::Error(RLGPU_ERR_INVALID_ARG, "rlgpu_debug_infer_trace: buffer of " + std::to_string(g_infer_trace_cap) +
                                                       " entries, this launch needs " + std::to_string(ceil_div(n, infer::IR) * 16));
     RLGPU_H16_LAUNCH(f16(h), infer::mlp_infer, dim3(ceil_div(n, infer::IR)), dim3(infer::IT), 0, s, a);
     RLGPU_CHECK_HIP(hipGetLastError());
+}
+
+// The inference forward of model mi over a block (n <= max_rows off the fused kernel) into f32 out [n, out]: fp32
+// (useHalfPrecision = false) or 16-bit.  half: 16-bit on an fp32 handle too (rlgpu_ppo_forward's precision 1).
+void infer_values(rlgpu_ppo* h, int mi, const Rows& r, float* out, hipStream_t s, bool half = false) {
+    if (infer_f32(h) && !half) return forward_f32(h, mi, r.X, (int)r.n, out, s);
+    if (fused_ok(h, mi)) return infer_fused(h, mi, false, r, out, nullptr, s);
+    const uint16_t* y = forward_half(h, mi, r.X, (int)r.n, s);
+    const int64_t e = r.n * h->M[mi].out;
+    RLGPU_H16_LAUNCH(f16(h), ppo::bf16_to_f32, dim3(ceil_div(e, 256)), dim3(256), 0, s, y, out, e);
+    RLGPU_CHECK_HIP(hipGetLastError());
+}
+
+// one policy forward over a block (n <= max_rows off the fused kernel) and its draw, with the current parameters
+// or (ver) the old version's: the fused kernel, or fp32 logits / forward_half and the sampler
+void sample_pass(rlgpu_ppo* h, bool ver, const Rows& r, const Draw& d, hipStream_t s) {
+    if (fused_ok(h, 0)) return infer_fused(h, 0, ver, r, nullptr, &d, s);
+    const int n = (int)r.n;
+    const auto sample = [&](auto kern, const auto* logits) {
+        hipLaunchKernelGGL(kern, dim3(ceil_div(n, 4)), dim3(256), 0, s, logits, r.masks, n, h->cfg.num_actions, d.det,
+                           h->cfg.seed, d.step, r.row0, d.act, d.logp, d.row_sel, d.sel);
+        RLGPU_CHECK_HIP(hipGetLastError());
+    };
+    if (infer_f32(h)) {  // useHalfPrecision = false: fp32 logits, the same sampler
+        forward_f32(h, 0, r.X, n, h->logits_f, s);
+        return sample(ppo::sample_actions<false, float>, h->logits_f);
+    }
+    const uint16_t* y = forward_half(h, 0, r.X, n, s, ver ? h->half_ver : h->half);
+    sample(f16(h) ? ppo::sample_actions<true> : ppo::sample_actions<false>, y);
+}
+
+// The action entry points after their argument checks: the block in chunks of `chunk` rows; with old_rows, per chunk
+// the current policy's rows and then the old version's, log probs only from the current pass.  Chunking: the layered
+// and fp32 paths work in the per-handle row buffers, so a launch of theirs takes at most max_rows rows; the fused
+// kernel keeps none and takes any count.  rlgpu_ppo_infer_actions and _mixed chunk by max_rows on every path (the fused
+// one too), rlgpu_ppo_infer_actions_rows -- fused only -- never chunks (INT64_MAX), and the critic chunks by max_rows
+// off the fused kernel and by 2^30 rows on it.
+void infer_policy(rlgpu_ppo* h, const Rows& rows, const Draw& draw, const uint8_t* old_rows, int64_t chunk, hipStream_t s) {
+    for (int64_t b = 0; b < rows.n; b += chunk) {
+        const Rows r = rows.sub(h->cfg, b, std::min(chunk, rows.n - b));
+        Draw d = draw.sub(b);
+        d.row_sel = old_rows ? old_rows + b : nullptr;
+        for (d.sel = 0; d.sel < (old_rows ? 2 : 1); d.sel++) {
+            if (d.sel) d.logp = nullptr;
+            sample_pass(h, d.sel != 0, r, d, s);
+        }
+    }
 }
 
 // One side of a split weight -- `rows` B rows of k elements -- appended to m's plane and scale buffers: rows padded
@@ -1000,6 +1079,7 @@ extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
             h->ah[1] = h->alloc<uint16_t>(R * H);
             h->logits_h = h->alloc<uint16_t>(R * omax);
             if (cfg->infer_fp16 == RLGPU_INFER_F32) h->logits_f = h->alloc<float>(R * omax);
+            build_chains(h);
             *out = h;
         } catch (...) {
             for (void* p : h->allocs) (void)hipFree(p);
@@ -1071,14 +1151,6 @@ extern "C" int rlgpu_ppo_refresh_half(rlgpu_ppo* h, void* stream) {
     });
 }
 
-// fp32 forward of model 0 or 1 (through the shared head, if any) on n <= max_rows rows of X into out:
-// the training forward's arithmetic (rlgpu_ppo_forward precision 0, and the fp32 inference)
-void forward_f32(rlgpu_ppo* h, int model, const float* X, int n, float* out, hipStream_t s) {
-    gather_obs(h, X, nullptr, 0, n, s);
-    if (h->shared()) forward_train(h, 2, obs_input(h), n, nullptr, s);
-    forward_train(h, model, model_input(h, model), n, out, s);
-}
-
 extern "C" int rlgpu_ppo_forward(rlgpu_ppo* h, int32_t model, int32_t precision, const float* d_in, int32_t n, float* d_out,
                                  void* stream) {
     return rlgpu::guarded([&] {
@@ -1087,22 +1159,13 @@ extern "C" int rlgpu_ppo_forward(rlgpu_ppo* h, int32_t model, int32_t precision,
         RLGPU_REQUIRE(n >= 0 && n <= h->cfg.max_rows, "n must be in [0, max_rows]");
         if (n == 0) return;
         hipStream_t s = rlgpu::as_stream(stream);
-        const int64_t e = (int64_t)n * h->M[model].out;
-        if (precision == 0) {
-            if (model == 2) {  // the shared head's last activation
-                gather_obs(h, d_in, nullptr, 0, n, s);
-                forward_train(h, 2, obs_input(h), n, nullptr, s);
-                RLGPU_CHECK_HIP(hipMemcpyAsync(d_out, model_input(h, 0).X, e * sizeof(float), hipMemcpyDeviceToDevice, s));
-            } else {
-                forward_f32(h, model, d_in, n, d_out, s);
-            }
-        } else if (fused_ok(h, model)) {
-            infer_fused(h, model, false, d_in, n, 0, d_out, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, s);
-        } else {
-            const uint16_t* y = forward_half(h, model, d_in, n, s);
-            RLGPU_H16_LAUNCH(f16(h), ppo::bf16_to_f32, dim3(ceil_div(e, 256)), dim3(256), 0, s, y, d_out, e);
-            RLGPU_CHECK_HIP(hipGetLastError());
-        }
+        if (precision != 0) return infer_values(h, model, Rows{d_in, n, 0, nullptr}, d_out, s, true);
+        if (model != 2) return forward_f32(h, model, d_in, n, d_out, s);
+        // the shared head's last activation
+        gather_obs(h, d_in, nullptr, 0, n, s);
+        forward_train(h, 2, obs_input(h), n, nullptr, s);
+        RLGPU_CHECK_HIP(hipMemcpyAsync(d_out, model_input(h, 0).X, (int64_t)n * h->M[2].out * sizeof(float),
+                                       hipMemcpyDeviceToDevice, s));
     });
 }
 
@@ -1112,31 +1175,8 @@ extern "C" int rlgpu_ppo_infer_actions(rlgpu_ppo* h, const float* d_obs, const u
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(h && d_obs && d_masks && d_actions, "null argument");
         RLGPU_REQUIRE(n >= 0, "n must be >= 0");
-        hipStream_t s = rlgpu::as_stream(stream);
-        int R = h->cfg.max_rows;
-        for (int64_t b = 0; b < n; b += R) {
-            int m = (int)std::min<int64_t>(R, n - b);
-            if (infer_f32(h)) {  // useHalfPrecision = false: fp32 logits, the same sampler
-                forward_f32(h, 0, d_obs + b * h->cfg.obs_size, m, h->logits_f, s);
-                hipLaunchKernelGGL((ppo::sample_actions<false, float>), dim3(ceil_div(m, 4)), dim3(256), 0, s, h->logits_f,
-                                   d_masks + b * h->cfg.num_actions, m, h->cfg.num_actions, deterministic, h->cfg.seed,
-                                   rng_step, b + h->cfg.sample_row_offset, d_actions + b, d_logp ? d_logp + b : nullptr,
-                                   nullptr, 0);
-                RLGPU_CHECK_HIP(hipGetLastError());
-                continue;
-            }
-            if (fused_ok(h, 0)) {
-                infer_fused(h, 0, false, d_obs + b * h->cfg.obs_size, m, 1, nullptr, d_masks + b * h->cfg.num_actions,
-                            deterministic, rng_step, d_actions + b, d_logp ? d_logp + b : nullptr, nullptr, 0, s,
-                            b + h->cfg.sample_row_offset);
-                continue;
-            }
-            forward_half(h, 0, d_obs + b * h->cfg.obs_size, m, s);
-            RLGPU_H16_LAUNCH(f16(h), ppo::sample_actions, dim3(ceil_div(m, 4)), dim3(256), 0, s, h->logits_h,
-                               d_masks + b * h->cfg.num_actions, m, h->cfg.num_actions, deterministic, h->cfg.seed,
-                               rng_step, b + h->cfg.sample_row_offset, d_actions + b, d_logp ? d_logp + b : nullptr);
-            RLGPU_CHECK_HIP(hipGetLastError());
-        }
+        infer_policy(h, Rows{d_obs, n, h->cfg.sample_row_offset, d_masks}, Draw{deterministic, rng_step, d_actions, d_logp},
+                     nullptr, h->cfg.max_rows, rlgpu::as_stream(stream));
     });
 }
 
@@ -1169,26 +1209,8 @@ extern "C" int rlgpu_ppo_infer_actions_mixed(rlgpu_ppo* h, const float* d_obs, c
             throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "rlgpu_ppo_infer_actions_mixed: fp32 inference (RLGPU_INFER_F32) "
                                                       "keeps no old-version copy (self-play needs 16-bit inference)");
         RLGPU_REQUIRE(n >= 0, "n must be >= 0");
-        hipStream_t s = rlgpu::as_stream(stream);
-        int R = h->cfg.max_rows;
-        for (int64_t b = 0; b < n; b += R) {
-            int m = (int)std::min<int64_t>(R, n - b);
-            for (int old = 0; old < 2; old++) {  // current policy rows, then the old version's rows
-                if (fused_ok(h, 0)) {
-                    infer_fused(h, 0, old != 0, d_obs + b * h->cfg.obs_size, m, 1, nullptr,
-                                d_masks + b * h->cfg.num_actions, deterministic, rng_step, d_actions + b,
-                                (d_logp && !old) ? d_logp + b : nullptr, d_old_rows + b, old, s,
-                                b + h->cfg.sample_row_offset);
-                    continue;
-                }
-                forward_half(h, 0, d_obs + b * h->cfg.obs_size, m, s, old ? h->half_ver : h->half);
-                RLGPU_H16_LAUNCH(f16(h), ppo::sample_actions, dim3(ceil_div(m, 4)), dim3(256), 0, s, h->logits_h,
-                                   d_masks + b * h->cfg.num_actions, m, h->cfg.num_actions, deterministic, h->cfg.seed,
-                                   rng_step, b + h->cfg.sample_row_offset, d_actions + b,
-                                   (d_logp && !old) ? d_logp + b : nullptr, d_old_rows + b, old);
-                RLGPU_CHECK_HIP(hipGetLastError());
-            }
-        }
+        infer_policy(h, Rows{d_obs, n, h->cfg.sample_row_offset, d_masks}, Draw{deterministic, rng_step, d_actions, d_logp},
+                     d_old_rows, h->cfg.max_rows, rlgpu::as_stream(stream));
     });
 }
 
@@ -1202,44 +1224,20 @@ extern "C" int rlgpu_ppo_infer_actions_rows(rlgpu_ppo* h, const float* d_obs, co
         if (!fused_ok(h, 0))
             throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "rlgpu_ppo_infer_actions_rows: the policy is not on the fused kernel "
                                                       "(widths, RLGPU_FUSED_INFER = 0 or fp32 inference)");
-        hipStream_t s = rlgpu::as_stream(stream);
-        // the fused kernel keeps no per-row buffers: one launch per pass over all n rows (no max_rows chunks)
-        const int64_t r0 = row0 + h->cfg.sample_row_offset;
-        if (!d_old_rows) {
-            infer_fused(h, 0, false, d_obs, n, 1, nullptr, d_masks, deterministic, rng_step, d_actions, d_logp, nullptr, 0, s,
-                        r0);
-            return;
-        }
-        for (int old = 0; old < 2; old++)  // current policy rows, then the old version's rows
-            infer_fused(h, 0, old != 0, d_obs, n, 1, nullptr, d_masks, deterministic, rng_step, d_actions,
-                        (d_logp && !old) ? d_logp : nullptr, d_old_rows, old, s, r0);
+        const Rows rows{d_obs, n, row0 + h->cfg.sample_row_offset, d_masks};
+        infer_policy(h, rows, Draw{deterministic, rng_step, d_actions, d_logp}, d_old_rows, INT64_MAX, rlgpu::as_stream(stream));
     });
 }
 
-extern "C" int rlgpu_ppo_fused_infer(rlgpu_ppo* h, int32_t model) { return h && fused_ok(h, model) ? 1 : 0; }
+extern "C" int rlgpu_ppo_fused_infer(rlgpu_ppo* h, int32_t model) { return h && model >= 0 && model < 3 && fused_ok(h, model); }
 
 extern "C" int rlgpu_ppo_infer_critic(rlgpu_ppo* h, const float* d_obs, int64_t n, float* d_values, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(h && d_obs && d_values, "null argument");
         hipStream_t s = rlgpu::as_stream(stream);
-        // the fused kernel keeps no per-row buffers: one launch over up to 2^30 rows (no max_rows chunks)
-        const int64_t R = fused_ok(h, 1) ? (int64_t)1 << 30 : h->cfg.max_rows;
-        for (int64_t b = 0; b < n; b += R) {
-            int m = (int)std::min<int64_t>(R, n - b);
-            if (infer_f32(h)) {  // useHalfPrecision = false
-                forward_f32(h, 1, d_obs + b * h->cfg.obs_size, m, d_values + b, s);
-                continue;
-            }
-            if (fused_ok(h, 1)) {
-                infer_fused(h, 1, false, d_obs + b * h->cfg.obs_size, m, 0, d_values + b, nullptr, 0, 0, nullptr, nullptr,
-                            nullptr, 0, s);
-                continue;
-            }
-            forward_half(h, 1, d_obs + b * h->cfg.obs_size, m, s);
-            RLGPU_H16_LAUNCH(f16(h), ppo::bf16_to_f32, dim3(ceil_div(m, 256)), dim3(256), 0, s, h->logits_h, d_values + b,
-                               (int64_t)m);
-            RLGPU_CHECK_HIP(hipGetLastError());
-        }
+        const Rows rows{d_obs, n, 0, nullptr};
+        const int64_t R = fused_ok(h, 1) ? (int64_t)1 << 30 : h->cfg.max_rows;  // see infer_policy on chunking
+        for (int64_t b = 0; b < n; b += R) infer_values(h, 1, rows.sub(h->cfg, b, std::min(R, n - b)), d_values + b, s);
     });
 }
 

@@ -399,7 +399,7 @@ int Learner::CollectGroups() const {
 void Learner::CollectGrouped(int G) {
     const int T = exp_.T, P = exp_.P, W = exp_.W;
     const rlgpu_rollout_view& v = exp_.v;
-    const uint8_t* old = oldTeam_ >= 0 ? oldRows_[oldTeam_] : nullptr;
+    const uint8_t* old = OldRows();
     const int Na = cfg_.num_arenas / G, Pg = 4 * Na;
     if ((int)gs_.size() != G) {
         for (auto s : gs_) (void)hipStreamDestroy(s);
@@ -412,11 +412,7 @@ void Learner::CollectGrouped(int G) {
         }
         if (!gsStart_) hipCheck(hipEventCreateWithFlags(&gsStart_, hipEventDisableTiming), "group event");
     }
-    if (envTiming_ && ev_.size() < (size_t)2 * T * G) {
-        for (auto e : ev_) (void)hipEventDestroy(e);
-        ev_.assign((size_t)2 * T * G, nullptr);
-        for (auto& e : ev_) hipCheck(hipEventCreate(&e), "event");
-    }
+    if (envTiming_) EnsureEvents((size_t)2 * T * G);
     hipCheck(hipEventRecord(gsStart_, s_), "group start");
     for (int g = 0; g < G; g++) hipCheck(hipStreamWaitEvent(gs_[g], gsStart_, 0), "group wait");
     rlgpu_ppo* ph = ppo_->handle();
@@ -454,32 +450,41 @@ void Learner::Collect() {
         return;
     }
     collectGroupsUsed_ = 1;
-    const int T = exp_.T, P = exp_.P;
+    const int T = exp_.T, P = exp_.P, W = exp_.W;
     const rlgpu_rollout_view& v = exp_.v;
-    const uint8_t* old = oldTeam_ >= 0 ? oldRows_[oldTeam_] : nullptr;
-    if (envTiming_ && ev_.size() < (size_t)2 * T) {
-        for (auto e : ev_) (void)hipEventDestroy(e);
-        ev_.assign(2 * T, nullptr);
-        for (auto& e : ev_) hipCheck(hipEventCreate(&e), "event");
-    }
-    const int W = exp_.W;
-    const rlgpu_envset_buffers& st = env_->state();
+    if (envTiming_) EnsureEvents((size_t)2 * T);
     for (int t = 0; t < T; t++) {
         const size_t r = (size_t)t * P;
-        ppo_->InferActions(v.obs + r * W, v.masks + r * ACT, P, cfg_.deterministic != 0, (uint64_t)stats.rng_step,
-                           v.actions + r, v.logp + r, old);
-        stats.rng_step++;
-        // the fused step appends straight into the rollout; stacked obs are assembled from the env's
-        // own obs / pre-reset rows after it
-        rlgpu_step_outputs o{K_ > 1 ? nullptr : v.obs + (r + P) * OBS, v.masks + (r + P) * ACT, v.rewards + r,
-                             v.terms + r, K_ > 1 ? nullptr : v.trunc_obs + r * OBS};
-        if (envTiming_) hipCheck(hipEventRecord(ev_[2 * t], s_), "event");
-        StepEnv(v.actions + r, o);
-        if (envTiming_) hipCheck(hipEventRecord(ev_[2 * t + 1], s_), "event");
-        if (K_ > 1)
-            lk::stack_frames(st.obs, st.trunc_obs, v.terms + r, hist_, K_, P, OBS, v.obs + (r + P) * W, v.trunc_obs + r * W,
-                             s_);
+        ActAndStep(r, r + P, v.trunc_obs + r * OBS, v.trunc_obs + r * W, envTiming_ ? &ev_[2 * t] : nullptr);
     }
+}
+
+// One collection step of every player on s_: the actions of the obs / masks at rollout row `row` (rng_step
+// advances), then the env step, which appends the next obs / masks at row `next`.  Unstacked, the fused step
+// appends straight into the rollout and writes the pre-reset rows to `trunc` (may be null); with stacked frames
+// the obs and the truncation rows (`truncStacked`, [P][W]) are assembled from the env's own obs / pre-reset rows
+// after it.  timing: two events recorded around the env step, or null.
+void Learner::ActAndStep(size_t row, size_t next, float* trunc, float* truncStacked, hipEvent_t* timing) {
+    const int P = exp_.P, W = exp_.W;
+    const rlgpu_rollout_view& v = exp_.v;
+    const rlgpu_envset_buffers& st = env_->state();
+    ppo_->InferActions(v.obs + row * W, v.masks + row * ACT, P, cfg_.deterministic != 0, (uint64_t)stats.rng_step,
+                       v.actions + row, v.logp + row, OldRows());
+    stats.rng_step++;
+    rlgpu_step_outputs o{K_ > 1 ? nullptr : v.obs + next * OBS, v.masks + next * ACT, v.rewards + row, v.terms + row,
+                         K_ > 1 ? nullptr : trunc};
+    if (timing) hipCheck(hipEventRecord(timing[0], s_), "event");
+    StepEnv(v.actions + row, o);
+    if (timing) hipCheck(hipEventRecord(timing[1], s_), "event");
+    if (K_ > 1) lk::stack_frames(st.obs, st.trunc_obs, v.terms + row, hist_, K_, P, OBS, v.obs + next * W, truncStacked, s_);
+}
+
+// at least `count` timing events in ev_ (recreated when it grows)
+void Learner::EnsureEvents(size_t count) {
+    if (ev_.size() >= count) return;
+    for (auto e : ev_) (void)hipEventDestroy(e);
+    ev_.assign(count, nullptr);
+    for (auto& e : ev_) hipCheck(hipEventCreate(&e), "event");
 }
 
 // One env step with the experience append.  Without a hook: the fused kernel (step, reset of terminated
@@ -764,6 +769,8 @@ void Learner::FinishIteration() {
 }
 
 // ---- RLGPU_EXP_TRAJECTORIES: the reference's trajectory loop (Learner.cpp:643-861)
+lk::TrajRecs TrajectoryStore::Records() const { return {rp.p, rstart.p, rlen.p, rcode.p, rtidx.p, roff.p}; }
+
 void Learner::CollectTrajectories() {
     TrajectoryStore& J = traj;
     const int P = exp_.P, W = exp_.W, Tm = J.Tmax;
@@ -774,7 +781,6 @@ void Learner::CollectTrajectories() {
     const uint8_t* track = oldTeam_ >= 0 ? oldRows_[1 - oldTeam_] : nullptr;
     if (J.lastOldTeam >= 0) lk::traj_restart(oldRows_[J.lastOldTeam], P, (int)(J.step % Tm), J.start, J.len, s_);
     J.lastOldTeam = oldTeam_;
-    const uint8_t* old = oldTeam_ >= 0 ? oldRows_[oldTeam_] : nullptr;
     hipCheck(hipMemsetAsync(J.counters, 0, lk::kTcCount * sizeof(int64_t), s_), "traj counters");
     J.firstStep = J.step;
     J.steps = 0;
@@ -788,17 +794,10 @@ void Learner::CollectTrajectories() {
         }
         J.truncObs.Reserve((J.ntrunc + P) * (int64_t)W, s_, true);
         const int r = (int)(J.step % Tm), rn = (int)((J.step + 1) % Tm);
-        const size_t row = (size_t)r * P, rown = (size_t)rn * P;
-        ppo_->InferActions(v.obs + row * W, v.masks + row * ACT, P, cfg_.deterministic != 0, (uint64_t)stats.rng_step,
-                           v.actions + row, v.logp + row, old);
-        stats.rng_step++;
-        rlgpu_step_outputs o{K_ > 1 ? nullptr : v.obs + rown * OBS, v.masks + rown * ACT, v.rewards + row, v.terms + row,
-                             nullptr};
-        StepEnv(v.actions + row, o);
-        if (K_ > 1)
-            lk::stack_frames(st.obs, st.trunc_obs, v.terms + row, hist_, K_, P, OBS, v.obs + rown * W, J.truncStage, s_);
-        lk::TrajRecs R{J.rp.p, J.rstart.p, J.rlen.p, J.rcode.p, J.rtidx.p, J.roff.p};
-        lk::traj_step(v.terms + row, r, Tm, track, P, J.start, J.len, R, J.counters, J.trnew, s_);
+        const size_t row = (size_t)r * P;
+        // the pre-reset rows stay in the env's buffer (or, stacked, go to the stage) for traj_trunc_copy below
+        ActAndStep(row, (size_t)rn * P, nullptr, J.truncStage, nullptr);
+        lk::traj_step(v.terms + row, r, Tm, track, P, J.start, J.len, J.Records(), J.counters, J.trnew, s_);
         lk::traj_trunc_copy(K_ > 1 ? J.truncStage : st.trunc_obs, W, J.counters, J.trnew, J.truncObs.p, s_);
         J.step++;
         J.steps++;
@@ -832,9 +831,8 @@ void Learner::ConsumeTrajectories() {
         return;
     }
     // combinedTraj -> tensors (Learner.cpp:863-912): the complete trajectories in the order they ended
-    lk::TrajRecs R{J.rp.p, J.rstart.p, J.rlen.p, J.rcode.p, J.rtidx.p, J.roff.p};
-    lk::traj_gather(R, K, J.Tmax, P, W, ACT, v.obs, v.masks, v.actions, v.logp, v.rewards, v.terms, J.cObs.p, J.cMasks.p,
-                    J.cActs.p, J.cLogp.p, J.cRews.p, J.cTerms.p, s_);
+    lk::traj_gather(J.Records(), K, J.Tmax, P, W, ACT, v.obs, v.masks, v.actions, v.logp, v.rewards, v.terms, J.cObs.p,
+                    J.cMasks.p, J.cActs.p, J.cLogp.p, J.cRews.p, J.cTerms.p, s_);
     ppo_->InferCritic(J.cObs.p, M, J.cVals.p);  // InferCriticBatched (Learner.cpp:936)
     if (ntr > 0) ppo_->InferCritic(J.truncObs.p, ntr, J.truncVals.p);  // nextTruncStates (:939-941)
     const float std_ = (float)returnStat.GetSTD();
@@ -1000,12 +998,13 @@ extern "C" int rlgpu_learner_batch(rlgpu_learner* h, rlgpu_batch_view* out) {
         b.trunc_obs = J.truncObs.p;
         b.trunc_vals = J.truncVals.p;
         b.num_truncs = J.ntrunc;
-        b.seg_player = J.rp.p;
-        b.seg_start = J.rstart.p;
-        b.seg_len = J.rlen.p;
-        b.seg_code = J.rcode.p;
-        b.seg_tidx = J.rtidx.p;
-        b.seg_off = J.roff.p;
+        const lk::TrajRecs R = J.Records();
+        b.seg_player = R.p;
+        b.seg_start = R.start;
+        b.seg_len = R.len;
+        b.seg_code = R.code;
+        b.seg_tidx = R.tidx;
+        b.seg_off = R.off;
         b.num_segments = J.nrec;
         b.store_rows = J.Tmax;
         b.steps = J.steps;

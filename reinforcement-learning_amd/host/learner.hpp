@@ -58,6 +58,10 @@ private:
 
 }  // namespace RLGC
 
+namespace lk {
+struct TrajRecs;  // csrc/learner_kernels.hpp
+}
+
 namespace GGL {
 
 using RLGC::RlgpuCheck;
@@ -120,6 +124,7 @@ struct TrajectoryStore {
     DevArray<int8_t> cTerms;
     float* truncStage = nullptr;  // [P][W] stacked pre-reset rows (frame stacking)
     int64_t nrec = 0, ntrunc = 0, nrows = 0;
+    lk::TrajRecs Records() const;  // this iteration's records (rp .. roff) as the kernels take them
 };
 
 // PPOLearner (PPOLearner.h:41-59) over rlgpu_ppo.
@@ -190,6 +195,8 @@ public:
 
 private:
     void StepEnv(const int32_t* d_actions, const rlgpu_step_outputs& o);
+    void ActAndStep(size_t row, size_t next, float* trunc, float* truncStacked, hipEvent_t* timing);
+    void EnsureEvents(size_t count);
     void AllReduceGrads(int epoch, int batch);
     void BatchAdvantageStats(const float* d_adv, const int32_t* d_idx, int64_t n);
     void CollectTrajectories();
@@ -222,6 +229,8 @@ private:
     void CollectGrouped(int G);
     // device scratch
     uint8_t* oldRows_[2] = {nullptr, nullptr};
+    // the rows that act with the old version this iteration (self-play), or null
+    const uint8_t* OldRows() const { return oldTeam_ >= 0 ? oldRows_[oldTeam_] : nullptr; }
     int32_t* trainRows_ = nullptr;
     int32_t* perm_ = nullptr;     // the shuffle, its row-selected form and the gathered batch advantages:
     int32_t* permRows_ = nullptr; // permCap_ rows each (T * P; grown to the combined batch in the

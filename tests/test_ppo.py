@@ -274,6 +274,55 @@ def test_fused_inference_matches_layer_path(gpu, monkeypatch, layers, ln, fp16, 
 
 
 @pytest.mark.gpu
+def test_infer_actions_rows_matches_whole_call(gpu, monkeypatch):
+    """rlgpu_ppo_infer_actions_rows (the collection in arena groups; not bound in rlgpu.ppo) over the row blocks
+    [0, 77) and [77, 200) of a 200-row step -- off the fused kernel's 64-row tile -- draws the actions and log
+    probs of one rlgpu_ppo_infer_actions call over the 200 rows (d_old_rows NULL), and with the matching slices
+    of old_rows those of one rlgpu_ppo_infer_actions_mixed call, bit for bit: the sampler's rows are global
+    (row0).  Off the fused kernel (RLGPU_FUSED_INFER=0) it is refused with RLGPU_ERR_UNSUPPORTED."""
+    import ctypes
+    import torch
+    from rlgpu import _lib
+    from rlgpu.ppo import PPO
+    n, cut = 200, 77
+    p = PPO(policy_layers=(40, 72), max_rows=n, seed=23)
+    L = _lib.lib()
+    vp, i32, i64, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
+    L.rlgpu_ppo_infer_actions_rows.argtypes = [vp, vp, vp, i32, i64, i32, u64, vp, vp, vp, vp]
+    rng = np.random.default_rng(n)
+    obs, masks, *_ = make_batch(rng, n)
+    o, m = torch.from_numpy(obs).to(gpu), torch.from_numpy(masks).to(gpu)
+    old_rows = torch.from_numpy((rng.random(n) < 0.5).astype(np.uint8)).to(gpu)
+    p.set_version(p.model_slice(0) * 0.5)
+
+    def rows(b, e, old, a, lp):
+        return L.rlgpu_ppo_infer_actions_rows(p._h, _lib.ptr(o[b:e]), _lib.ptr(m[b:e]), e - b, b, 0, 7,
+                                              _lib.ptr(old[b:e]) if old is not None else None, _lib.ptr(a[b:e]),
+                                              _lib.ptr(lp[b:e]), _lib.stream_ptr())
+
+    def blank():  # the old version's rows get no log prob: both sides start from the same NaN
+        return torch.full((n,), -1, dtype=torch.int32, device=gpu), torch.full((n,), float("nan"), device=gpu)
+
+    assert old_rows.any() and not old_rows.all()
+    for old in (None, old_rows):
+        wa, wlp = blank()
+        if old is None:
+            p.infer_actions(o, m, step=7, actions=wa, logp=wlp)
+        else:
+            p.infer_actions_mixed(o, m, old, step=7, actions=wa, logp=wlp)
+        a, lp = blank()
+        for b, e in ((0, cut), (cut, n)):
+            _lib.check(rows(b, e, old, a, lp), "rlgpu_ppo_infer_actions_rows")
+        assert (wa >= 0).all() and not torch.isnan(wlp[old_rows == 0]).any()
+        assert torch.equal(a, wa), (a != wa).sum().item()
+        assert torch.equal(lp.view(torch.int32), wlp.view(torch.int32))
+    monkeypatch.setenv("RLGPU_FUSED_INFER", "0")
+    a, lp = torch.empty(n, dtype=torch.int32, device=gpu), torch.empty(n, device=gpu)
+    assert rows(0, cut, None, a, lp) == -5  # RLGPU_ERR_UNSUPPORTED
+    assert "not on the fused kernel" in _lib.last_error()
+
+
+@pytest.mark.gpu
 def test_mean_std(gpu):
     import torch
     from rlgpu.ppo import PPO

@@ -1,5 +1,8 @@
 """Inference microbenchmark: rlgpu_ppo_infer_actions on one collection step (16,384 agents) and
-rlgpu_ppo_infer_critic over a C2 rollout (129 x 16,384 rows), bf16 MFMA path."""
+rlgpu_ppo_infer_critic over a C2 rollout (129 x 16,384 rows), bf16 MFMA path.
+
+    python tools/infer_bench.py [infer_fp16]     0 bf16 (default), 1 fp16, 2 the fp32 training forward
+"""
 import os
 import sys
 
@@ -10,7 +13,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "reinforcement-learning_amd")]
 from rlgpu.ppo import PPO  # noqa: E402
 
 dev = torch.device("cuda:0")
-ppo = PPO(167, 90, (512, 512), (512, 512), max_rows=65536, seed=1, device=dev)
+ppo = PPO(167, 90, (512, 512), (512, 512), max_rows=65536, seed=1, device=dev,
+          infer_fp16=int(sys.argv[1]) if len(sys.argv) > 1 else 0)
 P = 16384
 obs = torch.randn(P, 167, device=dev)
 masks = torch.ones(P, 90, dtype=torch.uint8, device=dev)
