@@ -108,6 +108,9 @@ typedef struct {
                                       bit for bit; measured slower so far); 0 / 1 = one launch per step; G > 1
                                       when the policy runs on the fused inference kernel, without host plugins or
                                       frame stacking, and 4 G | num_arenas */
+    float policy_temperature;      /* rlgpu_ppo_config.policy_temperature (PPOLearnerConfig::policyTemperature):
+                                      collection, old versions and Learn alike; 0 = 1 */
+    int32_t mask_entropy;          /* rlgpu_ppo_config.mask_entropy (PPOLearnerConfig::maskEntropy) */
 } rlgpu_learner_config;
 
 enum { RLGPU_ACT_LEAKY_RELU = 0, RLGPU_ACT_RELU = 1 };
@@ -120,6 +123,8 @@ enum { RLGPU_EXP_ROLLOUT = 0, RLGPU_EXP_TRAJECTORIES = 1 };
  * topology -- shared head [384, 384], policy / critic [384] x 3 as its log prints it
  * (run_out.log:25-28) -- is what host/example_main.cpp (rlgpu_train) selects. */
 int rlgpu_learner_default_config(rlgpu_learner_config* cfg);
+/* sizeof(rlgpu_learner_config), for language bindings to check their mirror of the struct against. */
+int32_t rlgpu_learner_config_size(void);
 
 /* Collectives for world > 1, called synchronously from the learner's host thread (the learner's
  * stream is synchronised before each call).  Return 0 on success. */

@@ -72,6 +72,15 @@ typedef struct {
     /* global row number of this handle's row 0 for the sampler's Philox counter (row, step): rank r of a
      * data-parallel job passes r x its rows, so the ranks draw what one device holding every row draws */
     int64_t sample_row_offset;
+    /* PPOLearnerConfig::policyTemperature: every sampling entry point (the old-version pass included,
+     * PPOLearner.cpp:187) and the minibatch loss run the softmax on logit / policy_temperature + (-1e10)*!mask
+     * (an fp32 division, PPOLearner.cpp:97-102,411-415).  Finite and > 0; 0 (a zero-initialised config) means 1. */
+    float policy_temperature;
+    /* PPOLearnerConfig::maskEntropy (0 / 1): the minibatch loss and its entropy metric divide each row's entropy
+     * by log(the row's legal actions) instead of log(num_actions) (PPOLearner.cpp:426-438).  No guard, as in the
+     * reference: a row with exactly one legal action divides by log 1 = 0 (inf / NaN in the loss and the
+     * gradients); the Rocket League masks never produce such a row. */
+    int32_t mask_entropy;
 } rlgpu_ppo_config;
 
 /* fp32 GEMM arithmetic of the training path (libtorch fp32 Linear forward / backward in the
@@ -102,6 +111,8 @@ enum {
 
 int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out);
 int rlgpu_ppo_destroy(rlgpu_ppo* h);
+/* sizeof(rlgpu_ppo_config), for language bindings to check their mirror of the struct against. */
+int32_t rlgpu_ppo_config_size(void);
 
 /* Flat fp32 buffers of all models, contiguous (policy first, then critic, then the shared head). */
 int rlgpu_ppo_buffers(rlgpu_ppo* h, float** d_params, float** d_grads, int64_t* num_params);
@@ -138,7 +149,8 @@ int rlgpu_kernel_timing_read(double* ms, double* work, int64_t* count, int32_t n
 int rlgpu_ppo_forward(rlgpu_ppo* h, int32_t model, int32_t precision, const float* d_in, int32_t n,
                       float* d_out, void* stream);
 
-/* InferActions: bf16 policy forward, logits + (-1e10)*!mask, softmax, clamp [1e-11, 1],
+/* InferActions: bf16 policy forward, logits / cfg.policy_temperature + (-1e10)*!mask (the logits as fp32, an
+ * IEEE fp32 division, the mask term added after it), softmax, clamp [1e-11, 1],
  * then argmax (deterministic) or a multinomial draw by inverse CDF on a Philox uniform
  * (key = cfg.seed, counter = (row, rng_step)).  d_actions int32 [n], d_logp [n] (may be NULL). */
 int rlgpu_ppo_infer_actions(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int32_t n,
@@ -176,7 +188,11 @@ int rlgpu_mean_std(const float* d_x, int64_t n, float* d_out, void* stream);
  * (with a shared head: its forward once, policy and critic on its output, and its backward from the
  * sum of their input gradients -- PPOLearner.cpp:396-398,478-498)
  * gathered from d_obs [*, obs_size], d_masks [*, A], d_actions int32, d_old_logp, d_adv,
- * d_target.  Advantages are normalised with d_adv_stats = (mean, std) as (a - mean)/(std+1e-8).
+ * d_target.  The policy's probabilities are softmax(logits / cfg.policy_temperature + (-1e10)*!mask) clamped
+ * to [1e-11, 1], and the logit gradient carries the factor 1 / policy_temperature.  The entropy is the mean over
+ * rows of -(p log p).sum / log(num_actions), or with cfg.mask_entropy / log(the row's legal actions) (a row with
+ * one legal action divides by 0, as in the reference).
+ * Advantages are normalised with d_adv_stats = (mean, std) as (a - mean)/(std+1e-8).
  * loss = (policyLoss - entropy*entropy_scale)*n/batch_size + MSE(V, target)*n/batch_size;
  * gradients are ACCUMULATED into the grad buffer; metrics summed into d_metrics. */
 int rlgpu_ppo_minibatch(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, const int32_t* d_actions,

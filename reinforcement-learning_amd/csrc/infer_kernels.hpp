@@ -78,6 +78,7 @@ struct InferArgs {
     float* out_f;
     const uint8_t* masks;          // mode 1: [n][out]
     int det;
+    float temp;                    // mode 1: policyTemperature, the sampler divides the logits by it
     uint64_t seed, step;
     int64_t row0;                  // global row number of X's row 0 (the sampler's Philox counter)
     int32_t* act;
@@ -417,7 +418,7 @@ __global__ void __launch_bounds__(IT, 1) mlp_infer(InferArgs a) {
             ok = Sel[r] != 0;
         };
         const auto mark = [&](int k) { INFER_MARK(k == 0 ? 7 : 11); };  // trace slots 7 / 11 are free here
-        ppo::sample_rows_looped<IRW, F16>(rowfn, N, a.det, a.seed, a.step, a.row0, lane, a.act, a.logp, mark);
+        ppo::sample_rows_looped<IRW, F16>(rowfn, N, a.temp, a.det, a.seed, a.step, a.row0, lane, a.act, a.logp, mark);
     }
     INFER_MARK(15);
 }

@@ -788,6 +788,7 @@ void infer_fused(rlgpu_ppo* h, int mi, bool ver, const Rows& r, float* out_f, co
     a.slope = h->cfg.leaky_slope;
     a.use_ln = h->cfg.layer_norm;
     a.seed = h->cfg.seed;
+    a.temp = h->cfg.policy_temperature;
     a.out_f = out_f;
     if (d) {
         a.mode = 1;
@@ -825,8 +826,8 @@ void sample_pass(rlgpu_ppo* h, bool ver, const Rows& r, const Draw& d, hipStream
     if (fused_ok(h, 0)) return infer_fused(h, 0, ver, r, nullptr, &d, s);
     const int n = (int)r.n;
     const auto sample = [&](auto kern, const auto* logits) {
-        hipLaunchKernelGGL(kern, dim3(ceil_div(n, 4)), dim3(256), 0, s, logits, r.masks, n, h->cfg.num_actions, d.det,
-                           h->cfg.seed, d.step, r.row0, d.act, d.logp, d.row_sel, d.sel);
+        hipLaunchKernelGGL(kern, dim3(ceil_div(n, 4)), dim3(256), 0, s, logits, r.masks, n, h->cfg.num_actions,
+                           h->cfg.policy_temperature, d.det, h->cfg.seed, d.step, r.row0, d.act, d.logp, d.row_sel, d.sel);
         RLGPU_CHECK_HIP(hipGetLastError());
     };
     if (infer_f32(h)) {  // useHalfPrecision = false: fp32 logits, the same sampler
@@ -967,12 +968,18 @@ void refresh_half(rlgpu_ppo* h, hipStream_t s) {
 
 }  // namespace
 
+extern "C" int32_t rlgpu_ppo_config_size(void) { return (int32_t)sizeof(rlgpu_ppo_config); }
+
 extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(cfg && out, "rlgpu_ppo_create: null argument");
         // one action has no distribution to learn: the entropy is normalised by log(num_actions), which is 0
         RLGPU_REQUIRE(cfg->obs_size > 0 && cfg->num_actions >= 2 && cfg->num_actions <= ppo::kMaxA,
                       "num_actions must be in [2, 128]");
+        // policyTemperature: 0 (a zero-initialised config) means 1; the sampler and the loss divide by it
+        RLGPU_REQUIRE(std::isfinite(cfg->policy_temperature) && cfg->policy_temperature >= 0.f,
+                      "policy_temperature must be finite and > 0 (0 = the default, 1)");
+        RLGPU_REQUIRE(cfg->mask_entropy == 0 || cfg->mask_entropy == 1, "mask_entropy must be 0 or 1");
         RLGPU_REQUIRE(cfg->n_policy_layers >= 1 && cfg->n_policy_layers <= RLGPU_MAX_LAYERS && cfg->n_critic_layers >= 1 &&
                           cfg->n_critic_layers <= RLGPU_MAX_LAYERS,
                       "1..8 hidden layers per model");
@@ -987,6 +994,7 @@ extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
         auto* h = new rlgpu_ppo();
         try {
             h->cfg = *cfg;
+            if (h->cfg.policy_temperature == 0.f) h->cfg.policy_temperature = 1.f;
             const bool sh = cfg->n_shared_layers > 0;
             h->nm = sh ? 3 : 2;
             // PPOLearner::MakeModels (PPOLearner.cpp:42-74): behind a shared head the policy / critic
@@ -1287,9 +1295,13 @@ extern "C" int rlgpu_ppo_minibatch(rlgpu_ppo* h, const float* d_obs, const uint8
         // policy on the caller's stream
         forward_train(h, 0, xin, n, pm.y, s);
         const int pl_blocks = (int)ceil_div(n, ppo::PL_ROWS);
-        hipLaunchKernelGGL(ppo::policy_loss_any(A), dim3(pl_blocks), dim3(256), 0, s, pm.y, d_masks, d_actions, d_old_logp, d_adv,
+        // the kernel that knows policy_temperature / mask_entropy only when one of them is set: the defaults run the
+        // kernel without them (see policy_loss on why x / 1 alone does not keep the bits)
+        const bool pl_opt = h->cfg.policy_temperature != 1.f || h->cfg.mask_entropy != 0;
+        hipLaunchKernelGGL(ppo::policy_loss_any(A, pl_opt), dim3(pl_blocks), dim3(256), 0, s, pm.y, d_masks, d_actions, d_old_logp, d_adv,
                            d_index, start, n, A, d_adv_stats, bsr, h->cfg.clip_range, h->cfg.entropy_scale,
-                           1.f / std::log((float)A), pm.dy, dout_ld(A), d_metrics, pm.lpart, amax_slot(pm, kAmaxOut));
+                           1.f / std::log((float)A), h->cfg.policy_temperature, h->cfg.mask_entropy, pm.dy, dout_ld(A), d_metrics,
+                           pm.lpart, amax_slot(pm, kAmaxOut));
         RLGPU_CHECK_HIP(hipGetLastError());
         backward(h, 0, xin, n, pm.dy, s, pm.lpart, pl_blocks);
         RLGPU_CHECK_HIP(hipStreamWaitEvent(s, h->ev_join, 0));

@@ -53,7 +53,9 @@ __device__ __forceinline__ void masked_softmax(float z0, float z1, bool v0, bool
 }
 
 // InferActions: logits bf16 [n, A] -> action (int32), log prob (PPOLearner.cpp:78-184).  The probs are the
-// masked softmax clamped to [1e-11, 1]; deterministic: argmax (lowest index on ties); otherwise the
+// softmax of logit / temp + (-1e10) * !mask (temp = policyTemperature, wave-uniform; an IEEE fp32 division of
+// the fp32-converted logit, the mask term added after it, :97-102; skipped by a uniform branch at temp = 1, where
+// x / 1 = x) clamped to [1e-11, 1]; deterministic: argmax (lowest index on ties); otherwise the
 // reference's CPU sampler (PPOLearner.cpp:157-178): r uniform in [0, 1), the first action whose running sum
 // of the clamped probs, accumulated in column order, reaches r (r <= running), the last column when none
 // does, and log(max(1e-12, p)) of the pick.  The uniform is a Philox draw of (seed, row0 + row, step) --
@@ -77,9 +79,9 @@ __device__ __forceinline__ float logit_f(float x) { return x; }
 
 template <int RG, bool F16, typename LT = uint16_t>
 __device__ __forceinline__ void sample_rows(const LT* const (&lg)[RG], const uint8_t* const (&mk)[RG],
-                                            float* const (&pr)[RG], int A, int deterministic, uint64_t seed,
-                                            uint64_t step, int64_t row0, const int (&row)[RG], const bool (&ok)[RG],
-                                            int lane, int32_t* act, float* logp) {
+                                            float* const (&pr)[RG], int A, float temp, int deterministic,
+                                            uint64_t seed, uint64_t step, int64_t row0, const int (&row)[RG],
+                                            const bool (&ok)[RG], int lane, int32_t* act, float* logp) {
 #pragma clang fp contract(off)
     const int a0 = 2 * lane, a1 = 2 * lane + 1;
     const bool in0 = a0 < A, in1 = a1 < A;
@@ -88,8 +90,12 @@ __device__ __forceinline__ void sample_rows(const LT* const (&lg)[RG], const uin
     const int c0 = min(a0, A - 1), c1 = min(a1, A - 1);  // loads stay unconditional (no branches between them)
 #pragma unroll
     for (int g = 0; g < RG; g++) {
-        const float l0 = logit_f<F16>(lg[g][c0]), l1 = logit_f<F16>(lg[g][c1]);
+        float l0 = logit_f<F16>(lg[g][c0]), l1 = logit_f<F16>(lg[g][c1]);
         const uint8_t m0 = mk[g][c0], m1 = mk[g][c1];
+        if (temp != 1.f) {  // wave-uniform; x / 1 = x exactly, the branch only spares T = 1 the division's time
+            l0 = l0 / temp;
+            l1 = l1 / temp;
+        }
         z0[g] = in0 ? l0 + (m0 ? 0.f : kDisabledLogit) : 0.f;
         z1[g] = in1 ? l1 + (m1 ? 0.f : kDisabledLogit) : 0.f;
         // softmax over all A columns (masked ones carry -1e10, exactly as the reference)
@@ -200,8 +206,8 @@ struct NoMark {
     __device__ void operator()(int) const {}
 };
 template <int RG, bool F16, typename RowFn, typename Mark = NoMark>
-__device__ __forceinline__ void sample_rows_looped(RowFn rowfn, int A, int deterministic, uint64_t seed, uint64_t step,
-                                                   int64_t row0, int lane, int32_t* act, float* logp,
+__device__ __forceinline__ void sample_rows_looped(RowFn rowfn, int A, float temp, int deterministic, uint64_t seed,
+                                                   uint64_t step, int64_t row0, int lane, int32_t* act, float* logp,
                                                    Mark mark = Mark{}) {
 #pragma clang fp contract(off)
     const int a0 = 2 * lane, a1 = 2 * lane + 1;
@@ -216,8 +222,12 @@ __device__ __forceinline__ void sample_rows_looped(RowFn rowfn, int A, int deter
         int rw;
         bool ok;
         rowfn(g, lg, mk, pr, rw, ok);
-        const float l0 = mlp::h2f<F16>(lg[c0]), l1 = mlp::h2f<F16>(lg[c1]);
+        float l0 = mlp::h2f<F16>(lg[c0]), l1 = mlp::h2f<F16>(lg[c1]);
         const uint8_t m0 = mk[c0], m1 = mk[c1];
+        if (temp != 1.f) {  // wave-uniform, as in sample_rows
+            l0 = l0 / temp;
+            l1 = l1 / temp;
+        }
         float z0 = in0 ? l0 + (m0 ? 0.f : kDisabledLogit) : 0.f;
         float z1 = in1 ? l1 + (m1 ? 0.f : kDisabledLogit) : 0.f;
         const float m = mlp::wave_max_x(fmaxf(in0 ? z0 : -INFINITY, in1 ? z1 : -INFINITY));
@@ -296,7 +306,7 @@ __device__ __forceinline__ void sample_rows_looped(RowFn rowfn, int A, int deter
 }
 
 template <bool F16, typename LT = uint16_t>
-__global__ void __launch_bounds__(256) sample_actions(const LT* logits, const uint8_t* masks, int n, int A,
+__global__ void __launch_bounds__(256) sample_actions(const LT* logits, const uint8_t* masks, int n, int A, float temp,
                                                      int deterministic, uint64_t seed, uint64_t step, int64_t row0,
                                                      int32_t* act, float* logp, const uint8_t* row_sel = nullptr,
                                                      int sel = 0) {
@@ -309,12 +319,22 @@ __global__ void __launch_bounds__(256) sample_actions(const LT* logits, const ui
     float* const pr[1] = {probs[threadIdx.x >> 6]};
     const int rw[1] = {row};
     const bool ok[1] = {true};
-    sample_rows<1, F16, LT>(lg, mk, pr, A, deterministic, seed, step, row0, rw, ok, lane, act, logp);
+    sample_rows<1, F16, LT>(lg, mk, pr, A, temp, deterministic, seed, step, row0, rw, ok, lane, act, logp);
 }
 
 // PPO policy loss + entropy and its gradient w.r.t. the fp32 training logits.
 // Rows are minibatch-ordered; sample s = idx ? idx[start + r] : start + r addresses the
 // batch buffers.  Metrics are reduced per block (one atomic each).
+// temp (PPOLearnerConfig::policyTemperature, :411-415): the softmax runs on logit / temp + (-1e10) * !mask, an
+// fp32 division, and the logit gradient is the softmax's times 1 / temp -- that scaled value is what dlogits,
+// the bias partials and the H3 amax see.
+// mask_entropy (maskEntropy, :426-428): each row's entropy, in the gradient and in the metric, is divided by
+// log(the row's legal actions) instead of the launch constant log A.  No guard: a row with one legal action
+// divides by log 1 = 0, as the reference does (the Rocket League masks never produce one).
+// OPT: the instantiation that knows the two options; the launch takes it only when temp != 1 or mask_entropy is
+// set.  OPT = false is the kernel without them, statement for statement: x / 1 and x * 1 are exact, but under
+// this file's FMA contraction an extra factor regroups what fuses with what (the column sum's p (d - dot) + col
+// becomes one FMA or a rounded product and an add), and the defaults must keep their bits.
 // 16 lanes per row, 4 rows in parallel per wave (lane group q = lane / 16 owns row q of the pass),
 // each lane holding the PL_K actions i, i + 16, .., i + 16 (PL_K - 1) of its row: the row's
 // reductions take 4 shuffle steps and one instruction stream serves 4 rows.
@@ -331,12 +351,13 @@ __device__ __forceinline__ float grp_max(float v) {
     for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
-template <int K>
+template <int K, bool OPT>
 __global__ void __launch_bounds__(256) policy_loss(const float* logits, const uint8_t* masks, const int32_t* actions,
                                                   const float* old_logp, const float* adv, const int32_t* idx, int64_t start,
                                                   int n, int A, const float* adv_stats, float bsr, float clip_range,
-                                                  float ent_scale, float inv_log_a, float* dlogits, int ldd,
-                                                  float* metrics, float* bias_part, float* amax) {
+                                                  float ent_scale, float inv_log_a, float temp, int mask_entropy,
+                                                  float* dlogits, int ldd, float* metrics, float* bias_part,
+                                                  float* amax) {
     __shared__ float red[16][5];
     __shared__ float colred[16][16 * K];  // per (wave, lane group) column sums of dlogits
     uint32_t vmax = 0;  // max |dlogits| (H3 operand scale, when amax is given)
@@ -347,7 +368,8 @@ __global__ void __launch_bounds__(256) policy_loss(const float* logits, const ui
 #pragma unroll
     for (int k = 0; k < K; k++) col[k] = 0.f;
     const float g_pl = -bsr / (float)n;
-    const float g_ent = -ent_scale * bsr * inv_log_a / (float)n;  // d loss / d H_i (H_i unnormalised)
+    const float g_ent_a = -ent_scale * bsr * inv_log_a / (float)n;  // d loss / d H_i (H_i unnormalised)
+    const float inv_temp = 1.f / temp;  // d z / d logit (OPT)
 #pragma unroll
     for (int pass = 0; pass < PL_PASSES; pass++) {
         const int row = blockIdx.x * PL_ROWS + (w * PL_PASSES + pass) * 4 + grp;
@@ -356,14 +378,28 @@ __global__ void __launch_bounds__(256) policy_loss(const float* logits, const ui
         const int64_t sidx = idx ? (int64_t)idx[start + rowc] : start + rowc;
         const float* lg = logits + (int64_t)rowc * A;
         const uint8_t* mk = masks + sidx * A;
-        float z[K];
+        float z[K], legal_l = 0.f;
         bool in[K];
 #pragma unroll
         for (int k = 0; k < K; k++) {
             const int a = i + 16 * k;
             in[k] = a < A;
-            z[k] = in[k] ? lg[a] + (mk[a] ? 0.f : kDisabledLogit) : -INFINITY;
+            if constexpr (OPT) {
+                const bool on = in[k] && mk[a] != 0;
+                z[k] = in[k] ? lg[a] / temp + (on ? 0.f : kDisabledLogit) : -INFINITY;
+                legal_l += on ? 1.f : 0.f;
+            } else {
+                z[k] = in[k] ? lg[a] + (mk[a] ? 0.f : kDisabledLogit) : -INFINITY;
+            }
         }
+        // maskEntropy: the row's entropy over log(its legal actions) (PPOLearner.cpp:426-428), one legal action
+        // dividing by log 1 = 0 as the reference does; otherwise the launch constant 1 / log A
+        float inv_log = inv_log_a, g_ent = g_ent_a;
+        if constexpr (OPT)
+            if (mask_entropy) {
+                inv_log = 1.f / logf(grp_sum(legal_l));
+                g_ent = -ent_scale * bsr * inv_log / (float)n;
+            }
         const int a_raw = actions[sidx];
         const float old = old_logp[sidx], advr = adv[sidx];
         float m = z[0];
@@ -424,14 +460,14 @@ __global__ void __launch_bounds__(256) policy_loss(const float* logits, const ui
                     if (i + 16 * k < ldd) dl[i + 16 * k] = 0.f;
                     continue;
                 }
-                const float gk = p[k] * (d[k] - dot);
+                const float gk = OPT ? p[k] * (d[k] - dot) * inv_temp : p[k] * (d[k] - dot);
                 dl[i + 16 * k] = gk;
                 col[k] += gk;
                 const uint32_t b = mlp::abs_bits(gk);
                 vmax = b > vmax ? b : vmax;
             }
             const float lr = lp - old;
-            m_ent += ent * inv_log_a;
+            m_ent += ent * inv_log;
             m_kl += expf(lr) - 1.f - lr;
             m_pl += -pl;
             m_ratio += ratio;
@@ -464,18 +500,23 @@ __global__ void __launch_bounds__(256) policy_loss(const float* logits, const ui
     if (amax) mlp::h3_amax_commit(amax, vmax);
 }
 
-// the instantiation with ceil(A / 16) actions per lane (A = 90: 6 of the 8 slots PL_K allows)
-inline decltype(&policy_loss<PL_K>) policy_loss_any(int A) {
+// the instantiation with ceil(A / 16) actions per lane (A = 90: 6 of the 8 slots PL_K allows), with the policy
+// options (opt) or without them
+template <bool OPT>
+inline decltype(&policy_loss<PL_K, OPT>) policy_loss_any(int A) {
     switch ((A + 15) / 16) {
-        case 1: return &policy_loss<1>;
-        case 2: return &policy_loss<2>;
-        case 3: return &policy_loss<3>;
-        case 4: return &policy_loss<4>;
-        case 5: return &policy_loss<5>;
-        case 6: return &policy_loss<6>;
-        case 7: return &policy_loss<7>;
-        default: return &policy_loss<PL_K>;
+        case 1: return &policy_loss<1, OPT>;
+        case 2: return &policy_loss<2, OPT>;
+        case 3: return &policy_loss<3, OPT>;
+        case 4: return &policy_loss<4, OPT>;
+        case 5: return &policy_loss<5, OPT>;
+        case 6: return &policy_loss<6, OPT>;
+        case 7: return &policy_loss<7, OPT>;
+        default: return &policy_loss<PL_K, OPT>;
     }
+}
+inline decltype(&policy_loss<PL_K, false>) policy_loss_any(int A, bool opt) {
+    return opt ? policy_loss_any<true>(A) : policy_loss_any<false>(A);
 }
 
 // Critic MSE: loss = mean((v - t)^2) * bsr ; dv = 2 (v - t) / n * bsr.

@@ -34,6 +34,7 @@
 #include <atomic>
 #include <chrono>
 #include <cinttypes>
+#include <cmath>
 #include <map>
 #include <set>
 #include <sstream>
@@ -682,8 +683,8 @@ inline void Learner::ValidateConfig(const LearnerConfig& c) {
     if (c.deviceType == LearnerDeviceType::CPU) bad("deviceType CPU: this engine runs on the GPU only");
     if (c.numGames <= 0) bad("numGames must be positive");
     if (c.standardizeObs) bad("standardizeObs is not supported (obs standardisation is not on the device path)");
-    if (c.ppo.policyTemperature != 1) bad("ppo.policyTemperature must be 1");
-    if (c.ppo.maskEntropy) bad("ppo.maskEntropy is not supported");
+    if (!std::isfinite(c.ppo.policyTemperature) || !(c.ppo.policyTemperature > 0))
+        bad("ppo.policyTemperature must be finite and > 0");
     if (c.ppo.useGuidingPolicy) bad("ppo.useGuidingPolicy is not supported");
     if (!c.ppo.useHalfPrecision && (c.trainAgainstOldVersions || c.skillTracker.enabled))
         bad("ppo.useHalfPrecision = false with trainAgainstOldVersions or skillTracker: old policy versions run on "
@@ -760,6 +761,8 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
     c.n_shared_layers = 0;
     if (config.ppo.sharedHead.IsValid()) layers(config.ppo.sharedHead, c.shared_layers, c.n_shared_layers);
     c.deterministic = config.ppo.deterministic;
+    c.policy_temperature = config.ppo.policyTemperature;  // sampling (old versions too) and Learn
+    c.mask_entropy = config.ppo.maskEntropy ? 1 : 0;
     // PPOLearnerConfig::useHalfPrecision (PPOLearnerConfig.h:31): Model::Forward's half branch (bf16 inference,
     // the reference's seqHalf) or its fp32 branch (Models.cpp:36-68) -- the training forward's arithmetic
     c.infer_fp16 = config.ppo.useHalfPrecision ? RLGPU_INFER_BF16 : RLGPU_INFER_F32;

@@ -21,7 +21,7 @@
 //
 //   rlgpu_train [--iterations N] [--arenas A] [--rollout T] [--trajectories] [--f32-gemm] [--c2-model] [--seed S]
 //               [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] [--self-play] [--fp32-inference]
-//               [--rank r --world N --rccl-id FILE [--rccl-nonce STR]]
+//               [--policy-temperature X] [--mask-entropy] [--rank r --world N --rccl-id FILE [--rccl-nonce STR]]
 #include <execinfo.h>
 #include <signal.h>
 
@@ -168,6 +168,8 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(argv[i], "--resave-to")) resaveTo = next();
             else if (!std::strcmp(argv[i], "--self-play")) cfg.trainAgainstOldVersions = true;
             else if (!std::strcmp(argv[i], "--fp32-inference")) cfg.ppo.useHalfPrecision = false;
+            else if (!std::strcmp(argv[i], "--policy-temperature")) cfg.ppo.policyTemperature = std::strtof(next(), nullptr);
+            else if (!std::strcmp(argv[i], "--mask-entropy")) cfg.ppo.maskEntropy = true;
             else if (!std::strcmp(argv[i], "--rank")) opt.rank = std::atoi(next());
             else if (!std::strcmp(argv[i], "--world")) opt.world = std::atoi(next());
             else if (!std::strcmp(argv[i], "--rccl-id")) idFile = next();
@@ -181,7 +183,7 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) {
             std::fprintf(stderr, "%s\nusage: %s [--iterations N] [--arenas A] [--rollout T] [--trajectories] [--f32-gemm] "
                                  "[--c2-model] [--seed S] [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] "
-                                 "[--self-play] [--fp32-inference] [--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);
+                                 "[--self-play] [--fp32-inference] [--policy-temperature X] [--mask-entropy] [--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);
             return 2;
         }
     }

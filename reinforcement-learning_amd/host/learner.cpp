@@ -283,6 +283,8 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     pc.sample_row_offset = (int64_t)cfg.rank * P;  // rank r's players are players [r P, (r + 1) P) of the job
     pc.train_gemm = cfg.train_gemm;
     pc.infer_fp16 = cfg.infer_fp16;
+    pc.policy_temperature = cfg.policy_temperature;  // validated by rlgpu_ppo_create (0 = 1)
+    pc.mask_entropy = cfg.mask_entropy;
     ppo_ = new PPOLearnerGPU(pc, s_);
     if (hasColl_) {  // identical initial weights on every rank: rank 0's (sum of zeros elsewhere)
         float* params = nullptr;
@@ -934,8 +936,12 @@ extern "C" int rlgpu_learner_default_config(rlgpu_learner_config* c) {
         c->train_gemm = RLGPU_GEMM_F16X3;  // fp32-class training GEMMs at half the MFMAs of F32X6
         c->rank = 0;
         c->world = 1;
+        c->policy_temperature = 1.0f;  // PPOLearnerConfig defaults
+        c->mask_entropy = 0;
     });
 }
+
+extern "C" int32_t rlgpu_learner_config_size(void) { return (int32_t)sizeof(rlgpu_learner_config); }
 
 extern "C" int rlgpu_learner_create(const rlgpu_learner_config* cfg, const rlgpu_collective* coll, void* stream,
                                     rlgpu_learner** out) {

@@ -197,6 +197,8 @@ class LearnerConfig:
         self.train_gemm = 2               # rlgpu_ppo_config.train_gemm: 2 = f32 via scaled fp16 split (H3), 0 = bf16 x6 split, 1 = f32 MFMA
         self.infer_fp16 = False           # rlgpu_ppo_config.infer_fp16: fp16 inference copy (C5) instead of bf16
         self.frame_stack = 1              # K >= 2: stacked AdvancedObs frames (C4; no reference counterpart)
+        self.policy_temperature = 1.0     # PPOLearnerConfig::policyTemperature: collection, old versions and Learn
+        self.mask_entropy = False         # PPOLearnerConfig::maskEntropy: entropy over log(legal actions) per row
         self.collect_groups = 0           # rollout collection in arena groups on their own streams (0 = automatic)
         # checkpoints (LearnerConfig.h:31-38): None = no save / load
         self.checkpoint_folder = None
@@ -236,7 +238,8 @@ class _CConfig(ctypes.Structure):
                 ("terminals", ctypes.c_void_p), ("n_terminals", ctypes.c_int32),
                 ("experience_mode", ctypes.c_int32), ("ts_per_itr", ctypes.c_int64),
                 ("experience_capacity", ctypes.c_int32), ("arith", ctypes.c_int32),
-                ("activation", ctypes.c_int32), ("optimizer", ctypes.c_int32), ("collect_groups", ctypes.c_int32)]
+                ("activation", ctypes.c_int32), ("optimizer", ctypes.c_int32), ("collect_groups", ctypes.c_int32),
+                ("policy_temperature", ctypes.c_float), ("mask_entropy", ctypes.c_int32)]
 
 
 class _CBatch(ctypes.Structure):
@@ -274,6 +277,7 @@ def _bind():
     vp = ctypes.c_void_p
     L.rlgpu_learner_create.argtypes = [ctypes.POINTER(_CConfig), vp, vp, ctypes.POINTER(vp)]
     L.rlgpu_learner_destroy.argtypes = [vp]
+    L.rlgpu_learner_config_size.restype = ctypes.c_int32
     L.rlgpu_learner_handles.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.rlgpu_learner_rollout.argtypes = [vp, ctypes.POINTER(_CRollout)]
     L.rlgpu_learner_batch.argtypes = [vp, ctypes.POINTER(_CBatch)]
@@ -362,6 +366,7 @@ class Learner:
         c.experience_mode, c.ts_per_itr, c.experience_capacity = cfg.experience_mode, cfg.ts_per_itr, cfg.experience_capacity
         c.arith = cfg.arith
         c.collect_groups = cfg.collect_groups
+        c.policy_temperature, c.mask_entropy = cfg.policy_temperature, int(cfg.mask_entropy)
         c.rank, c.world = rank, world
         self._coll = None
         coll = None

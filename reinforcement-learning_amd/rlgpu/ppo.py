@@ -35,7 +35,8 @@ class _Cfg(ctypes.Structure):
                 ("entropy_scale", ctypes.c_float), ("max_grad_norm", ctypes.c_float),
                 ("max_rows", ctypes.c_int32), ("seed", ctypes.c_uint64), ("train_gemm", ctypes.c_int32),
                 ("infer_fp16", ctypes.c_int32), ("shared_layers", ctypes.c_int32 * MAX_LAYERS),
-                ("n_shared_layers", ctypes.c_int32), ("sample_row_offset", ctypes.c_int64)]
+                ("n_shared_layers", ctypes.c_int32), ("sample_row_offset", ctypes.c_int64),
+                ("policy_temperature", ctypes.c_float), ("mask_entropy", ctypes.c_int32)]
 
 GEMM_F32X6, GEMM_F32, GEMM_F16X3 = 0, 1, 2  # rlgpu_ppo_config.train_gemm (include/rlgpu_ppo.h)
 
@@ -51,6 +52,7 @@ def _bind():
     vp, i32, i64, u64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
     L.rlgpu_ppo_create.argtypes = [ctypes.POINTER(_Cfg), ctypes.POINTER(vp)]
     L.rlgpu_ppo_destroy.argtypes = [vp]
+    L.rlgpu_ppo_config_size.restype = i32
     L.rlgpu_ppo_buffers.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)]
     L.rlgpu_ppo_model_range.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.rlgpu_ppo_init_params.argtypes = [vp, u64, vp]
@@ -93,7 +95,10 @@ class PPO:
                  layer_norm=True, policy_lr=2.5e-4, critic_lr=2.5e-4, clip_range=0.2, entropy_scale=0.035,
                  max_grad_norm=0.5, max_rows=50_000, seed=42, init=True, device="cuda:0",
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, leaky_slope=0.01, train_gemm=GEMM_F16X3,
-                 infer_fp16=False, shared_layers=()):
+                 infer_fp16=False, shared_layers=(), policy_temperature=1.0, mask_entropy=False):
+        """policy_temperature (PPOLearnerConfig::policyTemperature): sampling and the minibatch loss divide the
+        logits by it (0 = the C default, 1).  mask_entropy (maskEntropy): each row's entropy over log(its legal
+        actions) instead of log(num_actions)."""
         import torch
         if not torch.cuda.is_available():
             raise _lib.RLGPUError("PPO needs an MI355X: the product path has no CPU fallback")
@@ -118,6 +123,7 @@ class PPO:
         c.max_rows, c.seed = max_rows, seed
         c.train_gemm = train_gemm
         c.infer_fp16 = int(infer_fp16)
+        c.policy_temperature, c.mask_entropy = policy_temperature, int(mask_entropy)
         h = ctypes.c_void_p()
         _lib.check(L.rlgpu_ppo_create(ctypes.byref(c), ctypes.byref(h)), "rlgpu_ppo_create")
         self._h = h
