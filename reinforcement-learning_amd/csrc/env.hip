@@ -207,26 +207,49 @@ void boost_pad_index_map(int out[RLGPU_PADS_FOR_MAP]) {
 }  // namespace rlgpu
 
 // ------------------------------------------------------------------ C ABI
+// Ownership: every device buffer that rlgpu_envset_create makes goes through alloc(), which records it in
+// `allocs`; free_set() frees that list, the two optional buffers (d_metrics, d_reward_values: explicit members,
+// made, resized and dropped by their enable calls after create) and the struct.  It is the only way a set
+// dies: rlgpu_envset_destroy, and create itself when any step after `new` throws.
 struct rlgpu_envset {
     rlgpu_envset_config cfg;
     int num_players;
     char* d_arenas = nullptr;
     float *d_obs = nullptr, *d_rewards = nullptr, *d_last_rewards = nullptr, *d_trunc_obs = nullptr;
     uint8_t *d_masks = nullptr, *d_terminals = nullptr;
-    unsigned long long* d_prof = nullptr;
+    unsigned long long* d_prof = nullptr;  // the caller's (rlgpu_envset_set_profile), not owned
     double* d_metrics = nullptr;   // StepCallback slots [num_arenas][RLGPU_STEP_METRIC_SLOTS] or null
     uint64_t metric_calls = 0;     // ExampleMain's stepCounter
-    bool metric_players = false;   // this step's player-metrics flag (rlgpu_envset_step_range)
+    bool metric_players = false;   // this step's player-metrics flag (launch)
     bool output_only = false;      // rlgpu_envset_set_output_only: rows given in rlgpu_step_outputs go only there
-    void *d_cell_tri = nullptr, *d_cell_start = nullptr, *d_tri = nullptr, *d_edge = nullptr;  // arena mesh (MeshView)
-    void* d_gjk = nullptr;  // per-lane box-triangle penetration-solver scratch (MeshView::gjk)
-    rl::MeshView mesh{};
+    rl::MeshView mesh{};           // arena mesh tables and the per-lane penetration-solver scratch (MeshView::gjk)
     rl::Plugins plug{};                 // host copy of the reward / terminal registry
     rl::Plugins* d_plug = nullptr;      // its device copy (StepArgs::plug)
     int32_t* d_player_start = nullptr;  // EnvState::arenaPlayerStartIdx
     float* d_reward_values = nullptr;   // [players][nr] per-reward values (rlgpu_envset_enable_reward_values) or null
     int pen_slots = rl::kPenSave;       // saved deferred penetration queries per workgroup and tick (tests:
                                         // RLGPU_DEBUG_PEN_SAVE_SLOTS at create, 0..kPenSave, exercises the restart path)
+    std::vector<void*> allocs;
+
+    template <class T>
+    T* alloc(size_t count) {
+        allocs.push_back(nullptr);  // the slot first: a buffer never exists outside the list
+        RLGPU_CHECK_HIP(hipMalloc(&allocs.back(), count * sizeof(T)));
+        return (T*)allocs.back();
+    }
+    template <class T>
+    T* alloc_zero(size_t count) {
+        T* p = alloc<T>(count);
+        RLGPU_CHECK_HIP(hipMemset(p, 0, count * sizeof(T)));
+        return p;
+    }
+    // a device copy of v, in a buffer of at least min_count elements
+    template <class T>
+    T* alloc_copy(const std::vector<T>& v, size_t min_count = 0) {
+        T* p = alloc<T>(std::max(v.size(), min_count));
+        if (!v.empty()) RLGPU_CHECK_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return p;
+    }
 };
 
 namespace {
@@ -322,46 +345,55 @@ extern "C" int rlgpu_envset_default_plugins(rlgpu_reward_spec* rewards, int32_t*
 }
 
 namespace {
-// the kernels' __constant__ symbols live once per device: uploaded the first time a set is created on a
-// device, under one lock (sets may be created from several threads, on several devices of one process)
+// the env kernel specialised for each arithmetic, indexed by RLGPU_ARITH_*: its constant upload and its launch
+struct EnvKernel {
+    void (*upload)(const rl::EnvConst& k, const rl::RsqrtLut* lut);
+    void (*launch)(const rl::StepArgs& g, int blocks, hipStream_t s);
+};
+const EnvKernel kEnvKernel[RLGPU_NUM_ARITH] = {{rl::env_k0_upload, rl::env_k0_launch},
+                                               {rl::env_k1_upload, rl::env_k1_launch},
+                                               {rl::env_k2_upload, rl::env_k2_launch}};
+static_assert(RLGPU_ARITH_MSVC_X64 == 0 && RLGPU_ARITH_GCC_X64 == 1 && RLGPU_ARITH_SCALAR == 2, "kEnvKernel's order");
+
+// The kernels' __constant__ symbols live once per device.  device_init(arith), called by whatever is about to
+// launch a kernel of this library's env family for that arithmetic (a set's create, a query), uploads under one
+// lock (sets may be created from several threads, on several devices of one process):
+//   - EnvConst, the first time on a device: to this file's copy (the query kernels') and to every kEnvKernel;
+//   - the x86 modes' rsqrtss table, the first time an SSE arithmetic asks on a device: this host's table
+//     (host/x86_arith.cpp, the same for every set) into device memory, its pointer into kRsqrtLut of this file
+//     and of the kernels that read it (the SSE entries; their upload call carries EnvConst with it).
 std::mutex g_init_mu;
-std::vector<char> g_const_ready, g_rsqrt_ready;  // indexed by HIP device
+struct DeviceInit {
+    bool consts = false, rsqrt = false;
+};
+std::vector<DeviceInit> g_device_init;  // indexed by HIP device
 
-bool device_flag(std::vector<char>& v, int* dev) {
-    RLGPU_CHECK_HIP(hipGetDevice(dev));
-    if ((int)v.size() <= *dev) v.resize(*dev + 1, 0);
-    return v[*dev] != 0;
-}
-
-// the x86 modes' rsqrtss: this host's table (host/x86_arith.cpp) in device memory, its pointer in the
-// kernels' kRsqrtLut (once per device; the table is the host CPU's, the same for every set)
-void ensure_rsqrt() {
+void device_init(int arith) {
     std::lock_guard<std::mutex> lk(g_init_mu);
     int dev = 0;
-    if (device_flag(g_rsqrt_ready, &dev)) return;
-    int bits = 0;
-    const std::vector<uint32_t>& t = rlgpu::x86_rsqrt_table_or_throw(&bits);
-    uint32_t* d = nullptr;
-    RLGPU_CHECK_HIP(hipMalloc(&d, t.size() * sizeof(uint32_t)));
-    RLGPU_CHECK_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    const rl::RsqrtLut L{d, bits};
-    RLGPU_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(rl::kRsqrtLut), &L, sizeof L));
+    RLGPU_CHECK_HIP(hipGetDevice(&dev));
+    if ((int)g_device_init.size() <= dev) g_device_init.resize(dev + 1);
+    DeviceInit& done = g_device_init[dev];
+    const bool consts = !done.consts, rsqrt = rl::sse_api(arith) && !done.rsqrt;
+    if (!consts && !rsqrt) return;
+    rl::RsqrtLut L{};
+    if (rsqrt) {
+        int bits = 0;
+        const std::vector<uint32_t>& t = rlgpu::x86_rsqrt_table_or_throw(&bits);
+        uint32_t* d = nullptr;
+        RLGPU_CHECK_HIP(hipMalloc(&d, t.size() * sizeof(uint32_t)));
+        RLGPU_CHECK_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        L = rl::RsqrtLut{d, bits};
+        RLGPU_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(rl::kRsqrtLut), &L, sizeof L));
+    }
     const rl::EnvConst k = rl::make_env_const();
-    rl::env_k0_upload(k, &L);
-    rl::env_k1_upload(k, &L);
-    g_rsqrt_ready[dev] = 1;
-}
-
-void ensure_const() {
-    std::lock_guard<std::mutex> lk(g_init_mu);
-    int dev = 0;
-    if (device_flag(g_const_ready, &dev)) return;
-    rl::EnvConst k = rl::make_env_const();
-    RLGPU_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(rl::C), &k, sizeof k));
-    rl::env_k0_upload(k, nullptr);
-    rl::env_k1_upload(k, nullptr);
-    rl::env_k2_upload(k, nullptr);
-    g_const_ready[dev] = 1;
+    if (consts) RLGPU_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(rl::C), &k, sizeof k));
+    for (int a = 0; a < RLGPU_NUM_ARITH; a++) {
+        const bool lut = rsqrt && rl::sse_api(a);
+        if (consts || lut) kEnvKernel[a].upload(k, lut ? &L : nullptr);
+    }
+    done.consts = true;
+    done.rsqrt = done.rsqrt || rsqrt;
 }
 
 // rlgpu_envset_set_output_only: the rows a step appends to its outputs are not also written to the set's own
@@ -373,81 +405,118 @@ void output_only_rows(const rlgpu_envset* e, rl::StepArgs& g) {
     if (g.out_trunc) g.trunc_obs = nullptr;
 }
 
-void launch(rlgpu_envset* e, rl::StepArgs g, hipStream_t s) {
-    g.arenas = e->d_arenas;
-    g.n = e->cfg.num_arenas;
-    g.obs = e->d_obs;
-    g.masks = e->d_masks;
-    g.rewards = e->d_rewards;
-    g.terminals = e->d_terminals;
-    g.last_rewards = e->cfg.save_rewards ? e->d_last_rewards : nullptr;
-    g.trunc_obs = e->d_trunc_obs;
+// the arenas [first, first + count) of the set; a range that is not the whole set starts at a multiple of
+// kArenas (a workgroup's first arena)
+struct Range {
+    int first, count;
+};
+Range whole(const rlgpu_envset* e) { return Range{0, e->cfg.num_arenas}; }
+
+// The one place StepArgs is filled from the set: `g` says what the launch does (step_args, or a reset mode),
+// launch() adds where.  Every per-arena / per-player pointer is moved to the range's first arena (offsets that
+// are zero for the whole set), and so are the penetration-solver scratch (one GjkScratch per lane of the range's
+// workgroups) and arena_offset, so each arena keeps its own Philox stream and a range computes what the
+// whole-set launch computes for its arenas.  rlgpu_envset_step_range refuses a set with a profile buffer, so
+// `prof` is only ever seen by whole-set launches.
+//
+// StepCallback cadence (Learner.cpp:796-797, ExampleMain.cpp:236-237: every 4th call gathers the player
+// metrics): a build launch whose range starts at arena 0 is the step's one StepCallback call -- it advances
+// metric_calls and stores the flag -- and every range of that step, that one included, reads the stored flag.
+// A whole-set launch starts at arena 0, so this is what both the whole-set and the range path did when each
+// kept its own copy of the rule; a step's ranges must begin with the one that holds arena 0.
+void launch(rlgpu_envset* e, rl::StepArgs g, Range r, hipStream_t s) {
+    const size_t a0 = (size_t)r.first, p0 = a0 * 4, nr = (size_t)e->plug.nr;
+    g.arenas = e->d_arenas + a0 * rl::kRec;
+    g.n = r.count;
+    g.obs = e->d_obs + p0 * RLGPU_OBS;
+    g.masks = e->d_masks + p0 * RLGPU_ACTIONS;
+    g.rewards = e->d_rewards + p0;
+    g.terminals = e->d_terminals + a0;
+    g.last_rewards = e->cfg.save_rewards ? e->d_last_rewards + a0 * nr : nullptr;
+    g.trunc_obs = e->d_trunc_obs + p0 * RLGPU_OBS;
     g.seed = e->cfg.seed;
     g.max_episode_steps = e->cfg.max_episode_steps;
     g.prof = e->d_prof;
     g.mesh = e->mesh;
+    g.mesh.gjk = e->mesh.gjk + a0 / rl::kArenas * rl::kWG;
     g.plug = e->d_plug;
     g.arith = e->cfg.arith;
-    g.arena_offset = e->cfg.arena_offset;
+    g.arena_offset = e->cfg.arena_offset + r.first;
     g.fuzz = e->cfg.state_setter == RLGPU_SS_FUZZED_KICKOFF;
     g.pen_slots = e->pen_slots;
-    g.reward_values = g.build ? e->d_reward_values : nullptr;
-    output_only_rows(e, g);
-    if (g.build && e->d_metrics) {  // one StepCallback call (Learner.cpp:796-797, ExampleMain.cpp:236-237)
-        g.metrics = e->d_metrics;
-        g.metrics_players = (++e->metric_calls % 4) == 0;
-    }
-    unsigned blocks = rlgpu::ceil_div(g.n, rl::kArenas);
-    switch (e->cfg.arith) {  // the kernel specialised for the set's arithmetic
-        case RLGPU_ARITH_MSVC_X64: rl::env_k0_launch(g, blocks, s); break;
-        case RLGPU_ARITH_GCC_X64: rl::env_k1_launch(g, blocks, s); break;
-        default: rl::env_k2_launch(g, blocks, s); break;
-    }
-    RLGPU_CHECK_HIP(hipGetLastError());
-}
-
-// the arenas [first, first + count) of the set (first % kArenas == 0): every per-arena / per-player pointer
-// moved to the range, the arenas' Philox streams and the penetration-solver scratch of their workgroups kept
-void launch_range(rlgpu_envset* e, rl::StepArgs g, int first, int count, bool metrics_players, hipStream_t s) {
-    const size_t P0 = (size_t)first * 4;
-    g.arenas = e->d_arenas + (size_t)first * rl::kRec;
-    g.n = count;
-    g.obs = e->d_obs + P0 * RLGPU_OBS;
-    g.masks = e->d_masks + P0 * RLGPU_ACTIONS;
-    g.rewards = e->d_rewards + P0;
-    g.terminals = e->d_terminals + first;
-    g.last_rewards = e->cfg.save_rewards ? e->d_last_rewards + (size_t)first * e->plug.nr : nullptr;
-    g.trunc_obs = e->d_trunc_obs + P0 * RLGPU_OBS;
-    g.seed = e->cfg.seed;
-    g.max_episode_steps = e->cfg.max_episode_steps;
-    g.prof = nullptr;
-    g.mesh = e->mesh;
-    g.mesh.gjk = e->mesh.gjk ? e->mesh.gjk + (size_t)(first / rl::kArenas) * rl::kWG : nullptr;
-    g.plug = e->d_plug;
-    g.arith = e->cfg.arith;
-    g.arena_offset = e->cfg.arena_offset + first;
-    g.fuzz = e->cfg.state_setter == RLGPU_SS_FUZZED_KICKOFF;
-    g.pen_slots = e->pen_slots;
-    g.reward_values = g.build && e->d_reward_values ? e->d_reward_values + P0 * e->plug.nr : nullptr;
+    g.reward_values = g.build && e->d_reward_values ? e->d_reward_values + p0 * nr : nullptr;
     output_only_rows(e, g);
     if (g.build && e->d_metrics) {
-        g.metrics = e->d_metrics + (size_t)first * RLGPU_STEP_METRIC_SLOTS;
-        g.metrics_players = metrics_players;
+        if (r.first == 0) e->metric_players = (++e->metric_calls % 4) == 0;
+        g.metrics = e->d_metrics + a0 * RLGPU_STEP_METRIC_SLOTS;
+        g.metrics_players = e->metric_players;
     }
-    const unsigned blocks = rlgpu::ceil_div(count, rl::kArenas);
-    switch (e->cfg.arith) {
-        case RLGPU_ARITH_MSVC_X64: rl::env_k0_launch(g, blocks, s); break;
-        case RLGPU_ARITH_GCC_X64: rl::env_k1_launch(g, blocks, s); break;
-        default: rl::env_k2_launch(g, blocks, s); break;
-    }
+    kEnvKernel[e->cfg.arith].launch(g, rlgpu::ceil_div(r.count, rl::kArenas), s);
     RLGPU_CHECK_HIP(hipGetLastError());
 }
 
-rl::StepArgs blank() {
+rl::StepArgs blank(rl::ResetMode reset = rl::kResetNone) {
     rl::StepArgs g;
     std::memset(&g, 0, sizeof g);
+    g.reset_mode = reset;
     return g;
 }
+
+// One statement of the env step: StepFirstHalf (actionDelay ticks) if first_half, StepSecondHalf (the rest of
+// tickSkip) and the builders if d_actions, then `reset`, with the experience append into `out` (may be null).
+// The fused step is all of it; the two-half entry points each ask for their half.
+rl::StepArgs step_args(const rlgpu_envset* e, bool first_half, const int32_t* d_actions,
+                       rl::ResetMode reset = rl::kResetNone, const rlgpu_step_outputs* out = nullptr) {
+    rl::StepArgs g = blank(reset);
+    if (first_half) g.ticks_first = e->cfg.action_delay;
+    if (d_actions) {
+        g.actions = d_actions;
+        g.ticks_second = e->cfg.tick_skip - e->cfg.action_delay;
+        g.build = 1;
+    }
+    if (out) {
+        g.out_obs = out->obs;
+        g.out_masks = out->masks;
+        g.out_rew = out->rewards;
+        g.out_term = out->terminals;
+        g.out_trunc = out->trunc_obs;
+    }
+    return g;
+}
+
+// rlgpu_envset_step / rlgpu_envset_step_range
+rl::StepArgs fused_step_args(const rlgpu_envset* e, const int32_t* d_actions, int32_t reset_terminated,
+                             const rlgpu_step_outputs* out) {
+    RLGPU_REQUIRE(e->cfg.action_delay > 0, "fused step needs actionDelay > 0");
+    return step_args(e, true, d_actions, reset_terminated ? rl::kResetTerminated : rl::kResetNone, out);
+}
+
+// arena records between the set (record stride kRec) and a host array of rlgpu_arena_state
+void copy_records(const rlgpu_envset* e, int first, int count, void* host, hipMemcpyKind dir) {
+    char* dev = e->d_arenas + (size_t)first * rl::kRec;
+    const size_t rec = sizeof(rlgpu_arena_state);
+    if (dir == hipMemcpyDeviceToHost)
+        RLGPU_CHECK_HIP(hipMemcpy2D(host, rec, dev, rl::kRec, rec, count, dir));
+    else
+        RLGPU_CHECK_HIP(hipMemcpy2D(dev, rl::kRec, host, rec, rec, count, dir));
+}
+
+// the StepCallback slots [num_arenas][RLGPU_STEP_METRIC_SLOTS], downloaded and waited for
+void download_metric_slots(const rlgpu_envset* e, double* h_out, hipStream_t s) {
+    RLGPU_REQUIRE(e->d_metrics, "step metrics are not enabled (rlgpu_envset_enable_step_metrics)");
+    RLGPU_CHECK_HIP(hipMemcpyAsync(h_out, e->d_metrics,
+                                   (size_t)e->cfg.num_arenas * RLGPU_STEP_METRIC_SLOTS * sizeof(double),
+                                   hipMemcpyDeviceToHost, s));
+    RLGPU_CHECK_HIP(hipStreamSynchronize(s));
+}
+
+void free_set(rlgpu_envset* e) {
+    for (void* p : e->allocs) (void)hipFree(p);
+    (void)hipFree(e->d_metrics);
+    (void)hipFree(e->d_reward_values);
+    delete e;
+}
+
 }  // namespace
 
 extern "C" int rlgpu_arena_state_size(void) { return (int)sizeof(rlgpu_arena_state); }
@@ -465,8 +534,7 @@ extern "C" int rlgpu_envset_create(const rlgpu_envset_config* cfg, rlgpu_envset*
         RLGPU_REQUIRE(cfg->state_setter == RLGPU_SS_KICKOFF || cfg->state_setter == RLGPU_SS_FUZZED_KICKOFF,
                       "rlgpu_envset_create: unknown state setter " + std::to_string(cfg->state_setter) + " (RLGPU_SS_*)");
         const rl::Plugins plug = plugins_from(cfg);
-        ensure_const();
-        if (rl::sse_api(cfg->arith)) ensure_rsqrt();
+        device_init(cfg->arith);
         // arena meshes (Arena::_SetupArenaCollisionShapes): triangle table + grid index in HBM
         std::vector<float> builtin;
         const float* tris = cfg->mesh_tris;
@@ -479,88 +547,68 @@ extern "C" int rlgpu_envset_create(const rlgpu_envset_config* cfg, rlgpu_envset*
         rlgpu::MeshGrid grid = rlgpu::build_mesh_grid(tris, ntris, cfg->mesh_tris ? cfg->mesh_object_ntris : nullptr,
                                                       cfg->mesh_tris ? cfg->mesh_objects : 1, cfg->arith);
         auto* e = new rlgpu_envset();
-        if (const char* v = getenv("RLGPU_DEBUG_PEN_SAVE_SLOTS")) e->pen_slots = std::max(0, std::min(atoi(v), rl::kPenSave));
-        e->cfg = *cfg;
-        e->cfg.mesh_tris = nullptr;  // host pointers are not kept
-        e->cfg.mesh_object_ntris = nullptr;
-        e->cfg.rewards = nullptr;
-        e->cfg.terminals = nullptr;
-        e->plug = plug;
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_plug, sizeof(rl::Plugins)));
-        RLGPU_CHECK_HIP(hipMemcpy(e->d_plug, &e->plug, sizeof(rl::Plugins), hipMemcpyHostToDevice));
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_cell_start, grid.cell_start.size() * sizeof(int)));
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_cell_tri, std::max<size_t>(grid.cell_tri.size(), 12) * sizeof(float)));
-        RLGPU_CHECK_HIP(hipMemcpy(e->d_cell_start, grid.cell_start.data(), grid.cell_start.size() * sizeof(int),
-                                  hipMemcpyHostToDevice));
-        if (!grid.cell_tri.empty())
-            RLGPU_CHECK_HIP(hipMemcpy(e->d_cell_tri, grid.cell_tri.data(), grid.cell_tri.size() * sizeof(float),
-                                      hipMemcpyHostToDevice));
-        e->mesh.cell_tri = (const float4*)e->d_cell_tri;
-        e->mesh.cell_start = (const int*)e->d_cell_start;
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_tri, grid.tri.size() * sizeof(float)));
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_edge, grid.edge.size() * sizeof(float)));
-        RLGPU_CHECK_HIP(hipMemcpy(e->d_tri, grid.tri.data(), grid.tri.size() * sizeof(float), hipMemcpyHostToDevice));
-        RLGPU_CHECK_HIP(hipMemcpy(e->d_edge, grid.edge.data(), grid.edge.size() * sizeof(float), hipMemcpyHostToDevice));
-        e->mesh.tri = (const float4*)e->d_tri;
-        e->mesh.edge = (const float4*)e->d_edge;
-        e->mesh.ox = grid.ox;
-        e->mesh.oy = grid.oy;
-        e->mesh.oz = grid.oz;
-        e->mesh.inv_cell = grid.inv_cell;
-        e->mesh.nx = grid.nx;
-        e->mesh.ny = grid.ny;
-        e->mesh.nz = grid.nz;
-        e->mesh.ntris = grid.ntris;
-        for (int k = 0; k < 6; k++) e->mesh.empty[k] = grid.empty[k];
-        int n = cfg->num_arenas;
-        {  // one GjkScratch per lane of the env kernel's grid (touched only by penetration-solver calls)
-            const size_t lanes = (size_t)rlgpu::ceil_div(n, rl::kArenas) * rl::kWG;
-            RLGPU_CHECK_HIP(hipMalloc(&e->d_gjk, lanes * sizeof(rl::gjk::GjkScratch)));
-            e->mesh.gjk = (rl::gjk::GjkScratch*)e->d_gjk;
-        }
-        e->num_players = 4 * n;
-        size_t P = (size_t)e->num_players;
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_arenas, (size_t)n * rl::kRec));
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_obs, P * RLGPU_OBS * sizeof(float)));
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_trunc_obs, P * RLGPU_OBS * sizeof(float)));
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_rewards, P * sizeof(float)));
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_last_rewards, (size_t)n * std::max(plug.nr, 1) * sizeof(float)));
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_masks, P * RLGPU_ACTIONS));
-        RLGPU_CHECK_HIP(hipMalloc(&e->d_terminals, (size_t)n));
-        RLGPU_CHECK_HIP(hipMemset(e->d_terminals, 0, (size_t)n));
-        RLGPU_CHECK_HIP(hipMemset(e->d_rewards, 0, P * sizeof(float)));
-        RLGPU_CHECK_HIP(hipMemset(e->d_trunc_obs, 0, P * RLGPU_OBS * sizeof(float)));
-        RLGPU_CHECK_HIP(hipMemset(e->d_last_rewards, 0, (size_t)n * std::max(plug.nr, 1) * sizeof(float)));
-        {  // EnvState::arenaPlayerStartIdx (EnvSet.h:35-65): 4 players per arena
-            std::vector<int32_t> start(n);
-            for (int i = 0; i < n; i++) start[i] = 4 * i;
-            RLGPU_CHECK_HIP(hipMalloc(&e->d_player_start, (size_t)n * sizeof(int32_t)));
-            RLGPU_CHECK_HIP(hipMemcpy(e->d_player_start, start.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        // initial records: Arena ctor + AddCar defaults (Arena.cpp:429-562, Car.cpp:195-277)
-        std::vector<char> host((size_t)n * rl::kRec, 0);
-        rl::EnvConst k = rl::make_env_const();
-        for (int i = 0; i < n; i++) {
-            auto* s = (rlgpu_arena_state*)&host[(size_t)i * rl::kRec];
-            s->ball.rot[0] = s->ball.rot[4] = s->ball.rot[8] = 1.f;
-            s->ball.pos[2] = k.ball_radius;
-            for (int c = 0; c < 4; c++) {
-                rlgpu_car& cs = s->cars[c];
-                cs.body.rot[0] = cs.body.rot[4] = cs.body.rot[8] = 1.f;
-                cs.is_on_ground = 1;
-                cs.boost = 100.f / 3.f;
-                cs.ball_hit_tick = -1;
-                cs.ball_hit_extra_tick = -1;
+        try {  // from here on the set owns what it makes: any throw frees all of it (free_set)
+            if (const char* v = getenv("RLGPU_DEBUG_PEN_SAVE_SLOTS")) e->pen_slots = std::max(0, std::min(atoi(v), rl::kPenSave));
+            e->cfg = *cfg;
+            e->cfg.mesh_tris = nullptr;  // host pointers are not kept
+            e->cfg.mesh_object_ntris = nullptr;
+            e->cfg.rewards = nullptr;
+            e->cfg.terminals = nullptr;
+            e->plug = plug;
+            e->d_plug = e->alloc_copy(std::vector<rl::Plugins>(1, plug));
+            e->mesh.cell_start = e->alloc_copy(grid.cell_start);
+            e->mesh.cell_tri = (const float4*)e->alloc_copy(grid.cell_tri, 12);
+            e->mesh.tri = (const float4*)e->alloc_copy(grid.tri);
+            e->mesh.edge = (const float4*)e->alloc_copy(grid.edge);
+            e->mesh.ox = grid.ox;
+            e->mesh.oy = grid.oy;
+            e->mesh.oz = grid.oz;
+            e->mesh.inv_cell = grid.inv_cell;
+            e->mesh.nx = grid.nx;
+            e->mesh.ny = grid.ny;
+            e->mesh.nz = grid.nz;
+            e->mesh.ntris = grid.ntris;
+            for (int k = 0; k < 6; k++) e->mesh.empty[k] = grid.empty[k];
+            const int n = cfg->num_arenas;
+            // one GjkScratch per lane of the env kernel's grid (touched only by penetration-solver calls)
+            e->mesh.gjk = e->alloc<rl::gjk::GjkScratch>((size_t)rlgpu::ceil_div(n, rl::kArenas) * rl::kWG);
+            e->num_players = 4 * n;
+            const size_t P = (size_t)e->num_players;
+            // initial records: Arena ctor + AddCar defaults (Arena.cpp:429-562, Car.cpp:195-277)
+            std::vector<char> host((size_t)n * rl::kRec, 0);
+            const rl::EnvConst k = rl::make_env_const();
+            for (int i = 0; i < n; i++) {
+                auto* s = (rlgpu_arena_state*)&host[(size_t)i * rl::kRec];
+                s->ball.rot[0] = s->ball.rot[4] = s->ball.rot[8] = 1.f;
+                s->ball.pos[2] = k.ball_radius;
+                for (int c = 0; c < 4; c++) {
+                    rlgpu_car& cs = s->cars[c];
+                    cs.body.rot[0] = cs.body.rot[4] = cs.body.rot[8] = 1.f;
+                    cs.is_on_ground = 1;
+                    cs.boost = 100.f / 3.f;
+                    cs.ball_hit_tick = -1;
+                    cs.ball_hit_extra_tick = -1;
+                }
+                for (int p = 0; p < RLGPU_PADS; p++) s->pads[p].is_active = 1;
             }
-            for (int p = 0; p < RLGPU_PADS; p++) s->pads[p].is_active = 1;
+            e->d_arenas = e->alloc_copy(host);
+            e->d_obs = e->alloc<float>(P * RLGPU_OBS);
+            e->d_trunc_obs = e->alloc_zero<float>(P * RLGPU_OBS);
+            e->d_rewards = e->alloc_zero<float>(P);
+            e->d_last_rewards = e->alloc_zero<float>((size_t)n * std::max(plug.nr, 1));
+            e->d_masks = e->alloc<uint8_t>(P * RLGPU_ACTIONS);
+            e->d_terminals = e->alloc_zero<uint8_t>((size_t)n);
+            std::vector<int32_t> start(n);  // EnvState::arenaPlayerStartIdx (EnvSet.h:35-65): 4 players per arena
+            for (int i = 0; i < n; i++) start[i] = 4 * i;
+            e->d_player_start = e->alloc_copy(start);
+            // EnvSet ctor: reset every arena (EnvSet.cpp:105-110)
+            launch(e, blank(rl::kResetAll), whole(e), nullptr);
+            RLGPU_CHECK_HIP(hipDeviceSynchronize());
+        } catch (...) {
+            free_set(e);
+            throw;
         }
-        RLGPU_CHECK_HIP(hipMemcpy(e->d_arenas, host.data(), host.size(), hipMemcpyHostToDevice));
-        *out = e;
-        // EnvSet ctor: reset every arena (EnvSet.cpp:105-110)
-        rl::StepArgs g = blank();
-        g.reset_mode = 4;
-        launch(e, g, nullptr);
-        RLGPU_CHECK_HIP(hipDeviceSynchronize());
+        *out = e;  // only a set that is complete has an owner
     });
 }
 
@@ -603,12 +651,7 @@ extern "C" int rlgpu_envset_enable_step_metrics(rlgpu_envset* e, int32_t enable)
 extern "C" int rlgpu_envset_step_metric_slots(rlgpu_envset* e, double* h_out, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e && h_out, "null argument");
-        RLGPU_REQUIRE(e->d_metrics, "step metrics are not enabled (rlgpu_envset_enable_step_metrics)");
-        hipStream_t s = rlgpu::as_stream(stream);
-        RLGPU_CHECK_HIP(hipMemcpyAsync(h_out, e->d_metrics,
-                                       (size_t)e->cfg.num_arenas * RLGPU_STEP_METRIC_SLOTS * sizeof(double),
-                                       hipMemcpyDeviceToHost, s));
-        RLGPU_CHECK_HIP(hipStreamSynchronize(s));
+        download_metric_slots(e, h_out, rlgpu::as_stream(stream));
     });
 }
 
@@ -616,12 +659,10 @@ extern "C" int rlgpu_envset_step_metrics(rlgpu_envset* e, double* h_total, uint6
                                          void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e, "null envset");
-        RLGPU_REQUIRE(e->d_metrics, "step metrics are not enabled (rlgpu_envset_enable_step_metrics)");
         const int n = e->cfg.num_arenas;
         std::vector<double> slots((size_t)n * RLGPU_STEP_METRIC_SLOTS);
         hipStream_t s = rlgpu::as_stream(stream);
-        RLGPU_CHECK_HIP(hipMemcpyAsync(slots.data(), e->d_metrics, slots.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        RLGPU_CHECK_HIP(hipStreamSynchronize(s));
+        download_metric_slots(e, slots.data(), s);
         double tot[RLGPU_NUM_STEP_METRICS] = {};
         double passes = 0, goals = 0;
         for (int a = 0; a < n; a++) {
@@ -645,24 +686,7 @@ extern "C" int rlgpu_envset_step_metrics(rlgpu_envset* e, double* h_total, uint6
 
 extern "C" int rlgpu_envset_destroy(rlgpu_envset* e) {
     return rlgpu::guarded([&] {
-        if (!e) return;
-        if (e->d_metrics) (void)hipFree(e->d_metrics);
-        (void)hipFree(e->d_arenas);
-        (void)hipFree(e->d_obs);
-        (void)hipFree(e->d_trunc_obs);
-        (void)hipFree(e->d_rewards);
-        (void)hipFree(e->d_last_rewards);
-        (void)hipFree(e->d_masks);
-        (void)hipFree(e->d_terminals);
-        (void)hipFree(e->d_cell_tri);
-        (void)hipFree(e->d_tri);
-        (void)hipFree(e->d_edge);
-        (void)hipFree(e->d_gjk);
-        (void)hipFree(e->d_cell_start);
-        (void)hipFree(e->d_plug);
-        (void)hipFree(e->d_player_start);
-        if (e->d_reward_values) (void)hipFree(e->d_reward_values);
-        delete e;
+        if (e) free_set(e);
     });
 }
 
@@ -688,10 +712,9 @@ extern "C" int rlgpu_envset_download_gamestates(rlgpu_envset* e, int32_t first, 
         RLGPU_REQUIRE(e && h_out, "rlgpu_envset_download_gamestates: null argument");
         RLGPU_REQUIRE(first >= 0 && count >= 0 && first + count <= e->cfg.num_arenas, "arena range out of bounds");
         if (count == 0) return;
-        RLGPU_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+        RLGPU_CHECK_HIP(hipStreamSynchronize(rlgpu::as_stream(stream)));
         std::vector<rlgpu_arena_state> rec((size_t)count);
-        RLGPU_CHECK_HIP(hipMemcpy2D(rec.data(), sizeof(rlgpu_arena_state), e->d_arenas + (size_t)first * rl::kRec, rl::kRec,
-                                    sizeof(rlgpu_arena_state), count, hipMemcpyDeviceToHost));
+        copy_records(e, first, count, rec.data(), hipMemcpyDeviceToHost);
         rlgpu::gamestates_from_arenas(rec.data(), count, e->cfg.tick_skip, h_out);
     });
 }
@@ -715,42 +738,30 @@ extern "C" int rlgpu_envset_buffers_get(rlgpu_envset* e, rlgpu_envset_buffers* o
 extern "C" int rlgpu_envset_reset(rlgpu_envset* e, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e, "null envset");
-        rl::StepArgs g = blank();
-        g.reset_mode = 2;
-        launch(e, g, rlgpu::as_stream(stream));
+        launch(e, blank(rl::kResetSet), whole(e), rlgpu::as_stream(stream));
     });
 }
 
 extern "C" int rlgpu_envset_reset_arenas(rlgpu_envset* e, const uint8_t* d_mask, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e, "null envset");
-        rl::StepArgs g = blank();
-        g.reset_mode = 3;
+        rl::StepArgs g = blank(rl::kResetMask);
         g.reset_mask = d_mask;
-        launch(e, g, rlgpu::as_stream(stream));
+        launch(e, g, whole(e), rlgpu::as_stream(stream));
     });
 }
 
 extern "C" int rlgpu_envset_step_first_half(rlgpu_envset* e, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e, "null envset");
-        rl::StepArgs g = blank();
-        g.ticks_first = e->cfg.action_delay;
-        if (g.ticks_first == 0) {  // still snapshot prev state / clear events
-            g.ticks_first = 0;
-        }
-        launch(e, g, rlgpu::as_stream(stream));
+        launch(e, step_args(e, true, nullptr), whole(e), rlgpu::as_stream(stream));
     });
 }
 
 extern "C" int rlgpu_envset_step_second_half(rlgpu_envset* e, const int32_t* d_actions, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e && d_actions, "rlgpu_envset_step_second_half: null argument");
-        rl::StepArgs g = blank();
-        g.actions = d_actions;
-        g.ticks_second = e->cfg.tick_skip - e->cfg.action_delay;
-        g.build = 1;
-        launch(e, g, rlgpu::as_stream(stream));
+        launch(e, step_args(e, false, d_actions), whole(e), rlgpu::as_stream(stream));
     });
 }
 
@@ -758,21 +769,7 @@ extern "C" int rlgpu_envset_step(rlgpu_envset* e, const int32_t* d_actions, int3
                                  const rlgpu_step_outputs* out, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e && d_actions, "rlgpu_envset_step: null argument");
-        RLGPU_REQUIRE(e->cfg.action_delay > 0, "fused step needs actionDelay > 0");
-        rl::StepArgs g = blank();
-        g.ticks_first = e->cfg.action_delay;
-        g.actions = d_actions;
-        g.ticks_second = e->cfg.tick_skip - e->cfg.action_delay;
-        g.build = 1;
-        g.reset_mode = reset_terminated ? 1 : 0;
-        if (out) {
-            g.out_obs = out->obs;
-            g.out_masks = out->masks;
-            g.out_rew = out->rewards;
-            g.out_term = out->terminals;
-            g.out_trunc = out->trunc_obs;
-        }
-        launch(e, g, rlgpu::as_stream(stream));
+        launch(e, fused_step_args(e, d_actions, reset_terminated, out), whole(e), rlgpu::as_stream(stream));
     });
 }
 
@@ -780,25 +777,11 @@ extern "C" int rlgpu_envset_step_range(rlgpu_envset* e, int32_t first, int32_t c
                                        int32_t reset_terminated, const rlgpu_step_outputs* out, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e && d_actions, "rlgpu_envset_step_range: null argument");
-        RLGPU_REQUIRE(e->cfg.action_delay > 0, "fused step needs actionDelay > 0");
+        const rl::StepArgs g = fused_step_args(e, d_actions, reset_terminated, out);
         RLGPU_REQUIRE(first >= 0 && count > 0 && first + count <= e->cfg.num_arenas && first % rl::kArenas == 0,
                       "rlgpu_envset_step_range: the range must lie in the set and start at a multiple of 4");
         RLGPU_REQUIRE(!e->d_prof, "rlgpu_envset_step_range: not with the per-phase profile");
-        rl::StepArgs g = blank();
-        g.ticks_first = e->cfg.action_delay;
-        g.actions = d_actions;
-        g.ticks_second = e->cfg.tick_skip - e->cfg.action_delay;
-        g.build = 1;
-        g.reset_mode = reset_terminated ? 1 : 0;
-        if (out) {
-            g.out_obs = out->obs;
-            g.out_masks = out->masks;
-            g.out_rew = out->rewards;
-            g.out_term = out->terminals;
-            g.out_trunc = out->trunc_obs;
-        }
-        if (first == 0 && e->d_metrics) e->metric_players = (++e->metric_calls % 4) == 0;  // one StepCallback call
-        launch_range(e, g, first, count, e->metric_players, rlgpu::as_stream(stream));
+        launch(e, g, Range{first, count}, rlgpu::as_stream(stream));
     });
 }
 
@@ -819,9 +802,7 @@ extern "C" int rlgpu_envset_sync(rlgpu_envset* e, void* stream) {
 extern "C" int rlgpu_envset_build_obs(rlgpu_envset* e, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e, "null envset");
-        rl::StepArgs g = blank();
-        g.reset_mode = 5;
-        launch(e, g, rlgpu::as_stream(stream));
+        launch(e, blank(rl::kRebuildObs), whole(e), rlgpu::as_stream(stream));
     });
 }
 
@@ -831,8 +812,7 @@ extern "C" int rlgpu_envset_get_arenas(rlgpu_envset* e, int32_t first, int32_t c
         RLGPU_REQUIRE(first >= 0 && count >= 0 && first + count <= e->cfg.num_arenas, "arena range out of bounds");
         if (count == 0) return;
         RLGPU_CHECK_HIP(hipDeviceSynchronize());
-        RLGPU_CHECK_HIP(hipMemcpy2D(h_out, sizeof(rlgpu_arena_state), e->d_arenas + (size_t)first * rl::kRec, rl::kRec,
-                                    sizeof(rlgpu_arena_state), count, hipMemcpyDeviceToHost));
+        copy_records(e, first, count, h_out, hipMemcpyDeviceToHost);
     });
 }
 
@@ -842,8 +822,7 @@ extern "C" int rlgpu_envset_set_arenas(rlgpu_envset* e, int32_t first, int32_t c
         RLGPU_REQUIRE(first >= 0 && count >= 0 && first + count <= e->cfg.num_arenas, "arena range out of bounds");
         if (count == 0) return;
         RLGPU_CHECK_HIP(hipDeviceSynchronize());
-        RLGPU_CHECK_HIP(hipMemcpy2D(e->d_arenas + (size_t)first * rl::kRec, rl::kRec, h_in, sizeof(rlgpu_arena_state),
-                                    sizeof(rlgpu_arena_state), count, hipMemcpyHostToDevice));
+        copy_records(e, first, count, const_cast<rlgpu_arena_state*>(h_in), hipMemcpyHostToDevice);
     });
 }
 
@@ -946,9 +925,8 @@ extern "C" int rlgpu_box_triangle_queries(int32_t n, const float* d_rot, const f
         RLGPU_REQUIRE(arith >= 0 && arith < RLGPU_NUM_ARITH, "rlgpu_box_triangle_queries: unknown arithmetic mode");
         if (n == 0) return;
         RLGPU_REQUIRE(d_rot && d_centre && d_tri && d_cbt && d_out, "rlgpu_box_triangle_queries: null argument");
-        ensure_const();
-        if (rl::sse_api(arith)) ensure_rsqrt();
-        hipStream_t s = (hipStream_t)stream;
+        device_init(arith);
+        hipStream_t s = rlgpu::as_stream(stream);
         RLGPU_REQUIRE(lds_first >= 0 && lds_first <= 3, "rlgpu_box_triangle_queries: lds_first must be 0 .. 3");
         void* scratch = nullptr;
         const int lanes = lds_first >= 2 ? rlgpu::ceil_div(n, 64) * 64 : n;
@@ -1020,8 +998,8 @@ extern "C" int rlgpu_linear_math_queries(int32_t op, int32_t arith, const float*
         RLGPU_REQUIRE(arith >= 0 && arith < RLGPU_NUM_ARITH, "rlgpu_linear_math_queries: unknown arithmetic mode");
         RLGPU_REQUIRE(n >= 0 && (n == 0 || (d_in && d_out)), "rlgpu_linear_math_queries: bad argument");
         if (n == 0) return;
-        if (rl::sse_api(arith)) ensure_rsqrt();
-        hipLaunchKernelGGL(rl::linear_math_kernel, dim3(rlgpu::ceil_div(n, 64)), dim3(64), 0, (hipStream_t)stream, (int)op,
+        device_init(arith);
+        hipLaunchKernelGGL(rl::linear_math_kernel, dim3(rlgpu::ceil_div(n, 64)), dim3(64), 0, rlgpu::as_stream(stream), (int)op,
                            (int)arith, d_in, (int)n, d_out);
         RLGPU_CHECK_HIP(hipGetLastError());
     });
@@ -1056,8 +1034,8 @@ extern "C" int rlgpu_box_box_queries(int32_t n, const float* d_rot_a, const floa
         RLGPU_REQUIRE(n >= 0, "rlgpu_box_box_queries: n must be >= 0");
         if (n == 0) return;
         RLGPU_REQUIRE(d_rot_a && d_centre_a && d_rot_b && d_centre_b && d_out, "rlgpu_box_box_queries: null argument");
-        ensure_const();
-        hipLaunchKernelGGL(rl::box_box_kernel, dim3(rlgpu::ceil_div(n, 64)), dim3(64), 0, (hipStream_t)stream, n, d_rot_a,
+        device_init(RLGPU_ARITH_SCALAR);  // reads EnvConst only
+        hipLaunchKernelGGL(rl::box_box_kernel, dim3(rlgpu::ceil_div(n, 64)), dim3(64), 0, rlgpu::as_stream(stream), n, d_rot_a,
                            d_centre_a, d_rot_b, d_centre_b, d_out);
         RLGPU_CHECK_HIP(hipGetLastError());
     });

@@ -7,7 +7,7 @@
 namespace rl {
 
 // the env set constants (make_env_const): one copy per translation unit, each uploaded by env.hip
-// (ensure_const: its own for the test kernels, the specialised env kernels' through env_kN_upload)
+// (device_init: its own for the test kernels, the specialised env kernels' through env_kN_upload)
 static __constant__ EnvConst C;
 
 #define DEV __device__ __forceinline__

@@ -4,12 +4,22 @@
 // Every translation unit that defines RLGPU_ENV_KERNEL (the kernel's name) and RLGPU_ENV_ARITH (an
 // RLGPU_ARITH_* mode, include/rlgpu_arith.h) gets the kernel specialised for that arithmetic: arith(A) is
 // then a constant (env_device.hpp), so the other builds' LinearMath and solver-row branches fold away and
-// do not hold registers (env_k0.hip, env_k1.hip, env_k2.hip).  Without RLGPU_ENV_KERNEL only StepArgs is
-// declared (env.hip's host code).
+// do not hold registers (env_k0.hip, env_k1.hip, env_k2.hip).  Without RLGPU_ENV_KERNEL only StepArgs and
+// ResetMode are declared (env.hip's host code).
 #pragma once
 #include "env_builders.hpp"
 
 namespace rl {
+
+// StepArgs::reset_mode: what the launch resets after (or instead of) its step
+enum ResetMode : int {
+    kResetNone = 0,
+    kResetTerminated = 1,  // the fused step: arenas whose episode ended this step
+    kResetSet = 2,         // EnvSet::Reset: arenas whose terminals[] code is set (and clears it)
+    kResetMask = 3,        // ResetArena: arenas of reset_mask (null = all)
+    kResetAll = 4,         // every arena (the EnvSet constructor)
+    kRebuildObs = 5        // no reset: rebuild the obs / mask rows from the records
+};
 
 struct StepArgs {
     char* arenas;
@@ -18,7 +28,7 @@ struct StepArgs {
     const int32_t* actions; // StepSecondHalf actions (null = skip second half)
     int ticks_second;       // tickSkip - actionDelay
     int build;              // run GameState / terminal / reward / obs builders
-    int reset_mode;         // 0 none, 1 reset terminated (fused), 2 EnvSet::Reset, 3 mask, 4 all, 5 obs only
+    int reset_mode;         // a ResetMode
     const uint8_t* reset_mask;
     float* obs;
     uint8_t* masks;
@@ -583,7 +593,7 @@ __global__ void __launch_bounds__(kWG) RLGPU_ENV_KERNEL(StepArgs g) {
             g.terminals[arena] = term;
             A->s.env.last_tick_count = A->s.env.tick_count;
         }
-        const bool fused_reset = g.reset_mode == 1 && valid && term != 0;
+        const bool fused_reset = g.reset_mode == kResetTerminated && valid && term != 0;
         if (valid) build_obs_rows(A, l);
         sync(); P.mark(13);
         if (valid) {
@@ -595,7 +605,7 @@ __global__ void __launch_bounds__(kWG) RLGPU_ENV_KERNEL(StepArgs g) {
             }
         }
         sync(); P.mark(13);
-        if (g.reset_mode == 1) {
+        if (g.reset_mode == kResetTerminated) {
             if (fused_reset && l == 0) kickoff_reset(A, g.seed, arena + g.arena_offset, g.fuzz != 0);
             sync(); P.mark(14);
             if (fused_reset) build_obs_rows(A, l);
@@ -608,20 +618,20 @@ __global__ void __launch_bounds__(kWG) RLGPU_ENV_KERNEL(StepArgs g) {
         }
     }
     // ---- EnvSet::Reset / ResetArena / obs rebuild
-    if (g.reset_mode >= 2) {
+    if (g.reset_mode >= kResetSet) {
         bool do_reset = false;
         if (valid) {
-            if (g.reset_mode == 2) do_reset = g.terminals[arena] != 0;
-            else if (g.reset_mode == 3) do_reset = g.reset_mask ? g.reset_mask[arena] != 0 : true;
-            else if (g.reset_mode == 4) do_reset = true;
+            if (g.reset_mode == kResetSet) do_reset = g.terminals[arena] != 0;
+            else if (g.reset_mode == kResetMask) do_reset = g.reset_mask ? g.reset_mask[arena] != 0 : true;
+            else if (g.reset_mode == kResetAll) do_reset = true;
         }
         sync(); P.mark(14);
         if (do_reset && l == 0) {
             kickoff_reset(A, g.seed, arena + g.arena_offset, g.fuzz != 0);
-            if (g.reset_mode == 2) g.terminals[arena] = 0;
+            if (g.reset_mode == kResetSet) g.terminals[arena] = 0;
         }
         sync(); P.mark(14);
-        bool rebuild = do_reset || (valid && g.reset_mode == 5);
+        bool rebuild = do_reset || (valid && g.reset_mode == kRebuildObs);
         if (rebuild) build_obs_rows(A, l);
         sync(); P.mark(14);
         if (rebuild) copy_rows(A, l, arena, g.obs, g.masks);

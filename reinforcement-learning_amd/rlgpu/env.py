@@ -75,6 +75,7 @@ def _bind():
     L.rlgpu_envset_step_first_half.argtypes = [vp, vp]
     L.rlgpu_envset_step_second_half.argtypes = [vp, vp, vp]
     L.rlgpu_envset_step.argtypes = [vp, vp, i32, ctypes.POINTER(StepOutputs), vp]
+    L.rlgpu_envset_step_range.argtypes = [vp, i32, i32, vp, i32, ctypes.POINTER(StepOutputs), vp]
     L.rlgpu_envset_sync.argtypes = [vp, vp]
     L.rlgpu_envset_build_obs.argtypes = [vp, vp]
     L.rlgpu_envset_get_arenas.argtypes = [vp, i32, i32, vp]
@@ -220,6 +221,14 @@ class EnvSet:
         o = ctypes.byref(out) if out is not None else None
         _lib.check(_lib.lib().rlgpu_envset_step(self._h, self._actions(actions), int(reset_terminated), o,
                                                 _lib.stream_ptr(stream)), "rlgpu_envset_step")
+
+    def step_range(self, first, count, actions, reset_terminated=True, out=None, stream=None):
+        """The fused step of arenas [first, first + count) only (rlgpu_envset_step_range; first a multiple
+        of 4).  `actions` is the whole set's [num_players] tensor; `out` holds the range's players' rows."""
+        o = ctypes.byref(out) if out is not None else None
+        a = ctypes.c_void_p(self._actions(actions).value + CARS * int(first) * actions.element_size())
+        _lib.check(_lib.lib().rlgpu_envset_step_range(self._h, int(first), int(count), a, int(reset_terminated), o,
+                                                      _lib.stream_ptr(stream)), "rlgpu_envset_step_range")
 
     def set_output_only(self, on=True):
         """rlgpu_envset_set_output_only: rows given to step(out=...) go only there, not also to self.obs /

@@ -407,3 +407,56 @@ def test_env_rejects_host_actions(gpu):
     g = EnvSet(2, device=gpu)
     with pytest.raises(RLGPUError):
         g.step(torch.zeros(8, dtype=torch.int32), True)
+
+
+def test_env_step_range_matches_whole_set(gpu):
+    """rlgpu_envset_step_range against rlgpu_envset_step: a set stepped as the ranges [0, 4) and [4, 10) (two
+    full workgroups, then a full and a half-filled one) on one stream equals a set stepped whole, bit for bit
+    after every step -- arena records, every state buffer, the reward values and the appended rollout rows --
+    through truncations (max episode length) and terminal resets (NoTouch after 0.5 s), with a non-zero
+    arena_offset (the ranges' Philox streams) and the StepCallback slots (24 steps = six player passes)."""
+    import torch
+    from rlgpu.env import EnvSet, StepOutputs
+    from rlgpu.plugins import terminal
+    n, T, P = 10, 24, 40
+    ranges = ((0, 4), (4, 6))
+
+    def mk():
+        e = EnvSet(n, seed=21, device=gpu, save_rewards=True, max_episode_steps=5, arena_offset=12,
+                   terminals=[terminal("NoTouchCondition", 0.5), terminal("ScoreLimitCondition", 3)])
+        e.enable_step_metrics(True)
+        e.enable_reward_values(True)
+        return e
+
+    def rollout():
+        return (torch.zeros((T, P, 167), device=gpu), torch.zeros((T, P, 90), dtype=torch.uint8, device=gpu),
+                torch.zeros((T, P), device=gpu), torch.zeros((T, P), dtype=torch.int8, device=gpu),
+                torch.zeros((T, P, 167), device=gpu))
+
+    def same(x, y, what):
+        assert torch.equal(x.contiguous().view(torch.uint8), y.contiguous().view(torch.uint8)), what
+
+    A, B = mk(), mk()
+    ra, rb = rollout(), rollout()
+    rng = np.random.default_rng(7)
+    saw_traj, saw_reset = set(), 0
+    for t in range(T):
+        a = torch.from_numpy(random_actions(A.action_masks.cpu().numpy(), rng)).to(gpu)
+        A.step(a, True, StepOutputs.of(*(x[t] for x in ra)))
+        for first, count in ranges:
+            B.step_range(first, count, a, True, StepOutputs.of(*(x[t, 4 * first:] for x in rb)))
+        torch.cuda.synchronize()
+        d = arena_diff(_state(A), _state(B))
+        assert not d, f"step {t}: arena state differs\n" + "\n".join(d)
+        for name in ("obs", "action_masks", "rewards", "terminals", "last_rewards", "trunc_obs"):
+            same(getattr(A, name), getattr(B, name), f"step {t}: {name}")
+        same(A.reward_values(), B.reward_values(), f"step {t}: reward values")
+        for x, y, name in zip(ra, rb, ("obs", "masks", "rewards", "terminals", "trunc_obs")):
+            same(x[t], y[t], f"step {t}: appended {name}")
+        saw_traj.update(np.unique(ra[3][t].cpu().numpy()).tolist())
+        saw_reset += int((A.terminals != 0).sum())
+    assert saw_traj - {0}, "no trajectory ended; the reset path was not run"
+    assert 2 in saw_traj and saw_reset > 0, (saw_traj, saw_reset)
+    ma, mb = A.step_metric_slots(), B.step_metric_slots()
+    np.testing.assert_array_equal(ma.view(np.uint64), mb.view(np.uint64), err_msg="step metric slots")
+    assert (ma[:, 30] == T // 4).all(), ma[:, 30]  # RLGPU_SM_SLOT_PASSES: every 4th step is a player pass
