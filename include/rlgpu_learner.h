@@ -98,8 +98,11 @@ typedef struct {
                                       the store would overwrite a live step (documented divergence). */
     int32_t arith;                 /* rlgpu_envset_config.arith: the reference build's Bullet arithmetic
                                       (include/rlgpu_arith.h; 0 = build.ps1's MSVC x64) */
-    int32_t activation;            /* PartialModelConfig::activationType of every model: RLGPU_ACT_LEAKY_RELU (0,
-                                      torch::nn::LeakyReLU, slope 0.01) or RLGPU_ACT_RELU */
+    int32_t activation;            /* PartialModelConfig::activationType of every model (rlgpu_ppo.h):
+                                      RLGPU_ACT_LEAKY_RELU (0, torch::nn::LeakyReLU, slope 0.01), RLGPU_ACT_RELU,
+                                      RLGPU_ACT_SIGMOID or RLGPU_ACT_TANH */
+    int32_t no_layer_norm;         /* 1: PartialModelConfig::addLayerNorm = false for every model (hidden layers
+                                      are Linear -> activation); 0 (a zero-initialised config): LayerNorm on */
     int32_t optimizer;             /* PartialModelConfig::optimType of every model (Models.h:40-56):
                                       RLGPU_OPT_ADAMW (0, libtorch AdamW: weight decay 1e-2) or RLGPU_OPT_ADAM
                                       (libtorch Adam: no weight decay) */
@@ -113,7 +116,6 @@ typedef struct {
     int32_t mask_entropy;          /* rlgpu_ppo_config.mask_entropy (PPOLearnerConfig::maskEntropy) */
 } rlgpu_learner_config;
 
-enum { RLGPU_ACT_LEAKY_RELU = 0, RLGPU_ACT_RELU = 1 };
 enum { RLGPU_OPT_ADAMW = 0, RLGPU_OPT_ADAM = 1 };
 
 enum { RLGPU_EXP_ROLLOUT = 0, RLGPU_EXP_TRAJECTORIES = 1 };

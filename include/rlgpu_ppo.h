@@ -2,7 +2,7 @@
  * rlgpu_ppo.h -- C ABI for the PPO actor/critic of the MI355X rollout engine.
  *
  * Replaces (GigaLearnCPP, libtorch-based):
- *   GGL::Model  [Linear -> LayerNorm -> LeakyReLU] x k -> Linear
+ *   GGL::Model  [Linear -> LayerNorm (optional) -> activation] x k -> Linear
  *                                   src/private/GigaLearnCPP/Util/Models.cpp:7-69, Models.h:21-163
  *   PPOLearner::InferActionsFromModels / InferPolicyProbsFromModels
  *                                   src/private/GigaLearnCPP/PPO/PPOLearner.cpp:78-184
@@ -48,6 +48,10 @@ typedef struct {
     int32_t n_critic_layers;
     int32_t layer_norm;                       /* ModelConfig::addLayerNorm (eps 1e-5, affine) */
     float leaky_slope;                        /* torch::nn::LeakyReLU default 0.01 */
+    int32_t activation;                       /* ModelConfig::activationType (RLGPU_ACT_*, Models.cpp:17-23):
+                                                 0 = LeakyReLU with leaky_slope (a zero-initialised config keeps
+                                                 its slope), 1 = ReLU (slope 0 whatever leaky_slope says),
+                                                 2 = sigmoid, 3 = tanh; of every hidden layer of every model */
     float policy_lr, critic_lr;               /* PPOLearnerConfig::policyLR / criticLR */
     float beta1, beta2, eps, weight_decay;    /* AdamW: 0.9, 0.999, 1e-8, 1e-2 */
     float clip_range;                         /* 0.2 */
@@ -96,6 +100,8 @@ typedef struct {
  *                     correction terms in separate f32 accumulators (the 3xTF32 scheme of fp32
  *                     emulation): half the MFMAs of F32X6, products within 2^-22 relative. */
 enum { RLGPU_GEMM_F32X6 = 0, RLGPU_GEMM_F32 = 1, RLGPU_GEMM_F16X3 = 2 };
+/* rlgpu_ppo_config.activation / rlgpu_learner_config.activation values (ModelActivationType, ModelConfig.h:14-19) */
+enum { RLGPU_ACT_LEAKY_RELU = 0, RLGPU_ACT_RELU = 1, RLGPU_ACT_SIGMOID = 2, RLGPU_ACT_TANH = 3 };
 /* rlgpu_ppo_config.infer_fp16 values */
 enum { RLGPU_INFER_BF16 = 0, RLGPU_INFER_F16 = 1, RLGPU_INFER_F32 = 2 };
 

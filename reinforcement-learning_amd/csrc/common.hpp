@@ -55,4 +55,8 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 inline unsigned ceil_div(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
+// infer_act.hip: one launch of the fused inference kernel's SIGMOID / TANH instance (infer::mlp_infer<f16, act>)
+// with the infer::InferArgs at args (bytes = its size, checked)
+void launch_mlp_infer_act(int act, bool f16, unsigned blocks, hipStream_t s, const void* args, size_t bytes);
+
 }  // namespace rlgpu

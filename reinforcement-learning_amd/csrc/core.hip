@@ -8,7 +8,7 @@ void set_last_error(const std::string& msg) { g_last_error = msg; }
 
 extern "C" const char* rlgpu_last_error(void) { return rlgpu::g_last_error.c_str(); }
 
-extern "C" int rlgpu_abi_version(void) { return 100; }
+extern "C" int rlgpu_abi_version(void) { return 101; }
 
 extern "C" int rlgpu_device_count(void) {
     int n = 0;

@@ -1,5 +1,5 @@
 // infer_kernels.hpp -- fused 16-bit MLP inference: one launch runs a whole actor / critic forward
-// (obs f32 -> bf16, every Linear + LayerNorm + LeakyReLU, the output Linear) and then either samples
+// (obs f32 -> bf16, every Linear + LayerNorm + activation, the output Linear) and then either samples
 // the actions (InferActions, PPOLearner.cpp:114-184) or writes the f32 outputs (InferCritic,
 // Learner.cpp:863-900; Model::Forward under RLGPU_INFER_BF16).
 //
@@ -19,8 +19,8 @@
 // hidden layer (<= 512 columns) for both 32-row halves, and column tile (w & 3) of row half (w >> 2)
 // of the output layer (<= 128 columns).  A fragments come from LDS (shared by the waves); each wave
 // streams its own weight tiles from L2 into registers one 64-deep K chunk ahead of its MFMAs.  After
-// a layer's MFMAs the accumulators (+ bias, rounded) overwrite Xs in place, then LayerNorm + LeakyReLU
-// and the sampler run with each wave on 8 rows interleaved, so their cross-lane reductions overlap.
+// a layer's MFMAs the accumulators (+ bias, rounded) overwrite Xs in place, then LayerNorm + activation
+// (mlp::act_fwd of the kernel's kind ACT) and the sampler run with each wave on 8 rows interleaved, so their cross-lane reductions overlap.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -143,11 +143,11 @@ DEV void linear_tiles(const uint16_t (*Xs)[IPITCH], const uint16_t* F, int KS, c
     }
 }
 
-// bf16(LeakyReLU(bf16(LN(z)))) in place on the rows w + IW g (g < IRW) of Xs, interleaved: the
+// bf16(act(bf16(LN(z)))) (act: mlp::act_fwd<ACT>) in place on the rows w + IW g (g < IRW) of Xs, interleaved: the
 // per-row arithmetic of mlp::ln_act_fwd_bf16<MAXH> (same sums in the same order, the centred value
-// computed once and reused, LeakyReLU as max(h, slope h) when 0 <= slope <= 1 -- equal to the
+// computed once and reused, LEAKY in act_fwd's maxform when 0 <= slope <= 1 -- equal to the
 // select for every h); FULL: H == 64 MAXH, no column masks.
-template <int MAXH, bool FULL, bool F16>
+template <int MAXH, bool FULL, bool F16, int ACT>
 DEV void ln_act_rows(uint16_t (*Xs)[IPITCH], const uint16_t* gamma, const uint16_t* beta, int H, float slope, int use_ln,
                      int w, int lane) {
     const bool vec = (H % 8 == 0) && (MAXH % 8 == 0);
@@ -220,7 +220,7 @@ DEV void ln_act_rows(uint16_t (*Xs)[IPITCH], const uint16_t* gamma, const uint16
 #pragma unroll
         for (int q = 0; q < MAXH; q++) {
             const float hv = v[rg][q];
-            o[q] = f2h<F16>(maxform ? fmaxf(hv, hv * slope) : (hv > 0.f ? hv : hv * slope));
+            o[q] = f2h<F16>(mlp::act_fwd<ACT>(hv, slope, maxform));
         }
         if (vec) {
 #pragma unroll
@@ -244,7 +244,7 @@ DEV void ln_act_rows(uint16_t (*Xs)[IPITCH], const uint16_t* gamma, const uint16
 // accumulator element r of a lane: row ti * 32 + (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the tile
 DEV int acc_row(int ti, int r, int lane) { return ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
-template <bool F16>
+template <bool F16, int ACT = mlp::ACT_LEAKY>
 __global__ void __launch_bounds__(IT, 1) mlp_infer(InferArgs a) {
     __shared__ uint16_t Xs[IR][IPITCH];
     __shared__ uint8_t Ms[IR * ppo::kMaxA];  // mode 1: the rows' action masks
@@ -377,11 +377,11 @@ __global__ void __launch_bounds__(IT, 1) mlp_infer(InferArgs a) {
         const uint16_t* bb = Pv[l][2];
         __syncthreads();
         if (l < 3) INFER_MARK(8 + l);
-        if (N == 512) ln_act_rows<8, true, F16>(Xs, gg, bb, N, a.slope, a.use_ln, w, lane);
-        else if (N <= 64) ln_act_rows<1, false, F16>(Xs, gg, bb, N, a.slope, a.use_ln, w, lane);
-        else if (N <= 128) ln_act_rows<2, false, F16>(Xs, gg, bb, N, a.slope, a.use_ln, w, lane);
-        else if (N <= 256) ln_act_rows<4, false, F16>(Xs, gg, bb, N, a.slope, a.use_ln, w, lane);
-        else ln_act_rows<8, false, F16>(Xs, gg, bb, N, a.slope, a.use_ln, w, lane);
+        if (N == 512) ln_act_rows<8, true, F16, ACT>(Xs, gg, bb, N, a.slope, a.use_ln, w, lane);
+        else if (N <= 64) ln_act_rows<1, false, F16, ACT>(Xs, gg, bb, N, a.slope, a.use_ln, w, lane);
+        else if (N <= 128) ln_act_rows<2, false, F16, ACT>(Xs, gg, bb, N, a.slope, a.use_ln, w, lane);
+        else if (N <= 256) ln_act_rows<4, false, F16, ACT>(Xs, gg, bb, N, a.slope, a.use_ln, w, lane);
+        else ln_act_rows<8, false, F16, ACT>(Xs, gg, bb, N, a.slope, a.use_ln, w, lane);
     }
     // output Linear: wave w owns column tile (w & 3) of row half (w >> 2)
     const int l = a.nl - 1, KS = (a.width[l] + 15) / 16, N = a.width[l + 1], JT = (N + 31) / 32;

@@ -1182,6 +1182,40 @@ DEV float wave_max_x(float v) {
     return v;
 }
 
+// The hidden layers' activation, the one statement of its arithmetic: every LayerNorm / activation kernel of the
+// training and inference paths takes the kind as a template parameter and goes through this pair.  The kinds are
+// rlgpu_ppo_config.activation's values (ppo.hip asserts it); RELU is LEAKY with slope 0, chosen by the host.
+//   LEAKY:   h > 0 ? h : h * slope (maxform, the inference kernels with 0 <= slope <= 1: max(h, slope h), equal
+//            to the select for every h)
+//   SIGMOID: 1 / (1 + exp(-h)), derivative s (1 - s)
+//   TANH:    tanh(h), derivative 1 - t^2
+// with the accurate expf / tanhf.  The backward kernels recompute h and call act_fwd again, so the derivative is
+// taken at the forward's own bits and no activation is stored twice.
+constexpr int ACT_LEAKY = 0, ACT_SIGMOID = 2, ACT_TANH = 3;
+template <int ACT>
+DEV float act_fwd(float h, float slope, bool maxform = false) {
+    static_assert(ACT == ACT_LEAKY || ACT == ACT_SIGMOID || ACT == ACT_TANH, "unknown activation kind");
+    if (ACT == ACT_SIGMOID) return 1.f / (1.f + expf(-h));
+    if (ACT == ACT_TANH) return tanhf(h);
+    return maxform ? fmaxf(h, h * slope) : (h > 0.f ? h : h * slope);
+}
+// da * (d act / d h) at the pre-activation h: the gradient da of the activation taken back through it
+template <int ACT>
+DEV float act_bwd(float h, float da, float slope) {
+    if (ACT == ACT_SIGMOID) {
+        const float s = act_fwd<ACT_SIGMOID>(h, slope);
+        return da * (s * (1.f - s));
+    }
+    if (ACT == ACT_TANH) {
+        const float t = act_fwd<ACT_TANH>(h, slope);
+        return da * (1.f - t * t);
+    }
+    return h > 0.f ? da : da * slope;
+}
+// A host-side picker's instance for a runtime kind: PICK<ACT>(args...) for act (anything else: LEAKY)
+#define RLGPU_ACT_SWITCH(act, PICK, ...)                                \
+    ((act) == ACT_SIGMOID ? PICK<ACT_SIGMOID>(__VA_ARGS__)              \
+                          : ((act) == ACT_TANH ? PICK<ACT_TANH>(__VA_ARGS__) : PICK<ACT_LEAKY>(__VA_ARGS__)))
 
 // Column ownership of the wave-per-row kernels: with MAXH >= 4 columns per lane, lane l owns the
 // 4-column groups starting at 4 l + 256 q (q < MAXH / 4), so every 16-byte load / store instruction
@@ -1192,7 +1226,7 @@ DEV int lcol(int lane, int q) {
     return MAXH >= 4 ? 4 * lane + 256 * (q >> 2) + (q & 3) : MAXH * lane + q;
 }
 
-// LayerNorm (eps 1e-5, biased variance) + LeakyReLU, training: one wave per row.
+// LayerNorm (eps 1e-5, biased variance) + activation (act_fwd<ACT>), training: one wave per row.
 // Keeps act [R,H] and the row statistics stats [R] = (mean, rstd) for the backward, which
 // recomputes xhat = (z - mean) * rstd from the untouched pre-norm input z with the same operations
 // (bit-identical to a stored xhat, one [R,H] write less per layer).
@@ -1241,7 +1275,7 @@ DEV void lnf_affine(const float* gamma, const float* beta, int H, int use_ln, in
 // activation, stats / max |act| / rank-1 head outputs of the rows below R.  The one statement of this
 // arithmetic: ln_act_fwd_f32 (z rows loaded from memory) and gemm_h3_rowln (z rows staged in LDS by the GEMM
 // that produced them) both call it, so their bits agree.
-template <int MAXH, int RF>
+template <int MAXH, int RF, int ACT = ACT_LEAKY>
 DEV void lnf_rows(const float (&v)[RF][MAXH], const int (&row)[RF], int R, int H, const float (&g)[MAXH],
                   const float (&b)[MAXH], float slope, int use_ln, bool vec, int lane, float* act, float2* stats,
                   uint32_t& vmax, const float* head_w, const float* head_b, float* head_out) {
@@ -1278,7 +1312,7 @@ DEV void lnf_rows(const float (&v)[RF][MAXH], const int (&row)[RF], int R, int H
         for (int q = 0; q < MAXH; q++) {
             const float xh = use_ln ? (v[r][q] - mean[r]) * rs[r] : v[r][q];
             const float hv = use_ln ? xh * g[q] + b[q] : xh;
-            a[q] = hv > 0.f ? hv : hv * slope;
+            a[q] = act_fwd<ACT>(hv, slope);
         }
         float* ao = act + (int64_t)row[r] * H;
         if (vec) {
@@ -1303,7 +1337,7 @@ DEV void lnf_rows(const float (&v)[RF][MAXH], const int (&row)[RF], int R, int H
         if (head_w) head1_row<MAXH>(a, head_w, head_b, H, vec, lane, head_out + row[r]);
     }
 }
-template <int MAXH, int ROWS = LNF_ROWS, int RFX = lnf_rf<MAXH>()>
+template <int MAXH, int ACT = ACT_LEAKY, int ROWS = LNF_ROWS, int RFX = lnf_rf<MAXH>()>
 __global__ void __launch_bounds__(256) ln_act_fwd_f32(const float* Z, const float* gamma, const float* beta, int R, int H,
                                                      float slope, int use_ln, float* act, float2* stats, float* amax,
                                                      const float* head_w = nullptr, const float* head_b = nullptr,
@@ -1336,12 +1370,13 @@ __global__ void __launch_bounds__(256) ln_act_fwd_f32(const float* Z, const floa
                 }
             }
         }
-        lnf_rows<MAXH, RF>(v, row, R, H, g, b, slope, use_ln, vec, lane, act, stats, vmax, head_w, head_b, head_out);
+        lnf_rows<MAXH, RF, ACT>(v, row, R, H, g, b, slope, use_ln, vec, lane, act, stats, vmax, head_w, head_b, head_out);
     }
     if (amax) h3_amax_commit(amax, vmax);
 }
 
-// ---- Full-row H3 forward GEMM with LayerNorm + LeakyReLU in the same launch (gemm_h3_rowln): one hidden layer's
+// ---- Full-row H3 forward GEMM with LayerNorm + LeakyReLU in the same launch (gemm_h3_rowln; LeakyReLU / ReLU only,
+// one non-template kernel: the other kinds keep the two-kernel path, ppo.hip rowfuse_fwd): one hidden layer's
 // gemm_x6<A_IK, B_JK, pre-split B, H3> + ln_act_fwd_f32<8> pair for a 512-column output.  A workgroup owns 64
 // rows across all 512 columns, so the f32 activation slice is loaded and split once per row block (not once per
 // 128-column tile) and z never has to be read back: 4 waves, each all 64 rows x 128 columns (2 x 4 MFMA blocks).
@@ -1513,7 +1548,7 @@ __global__ void __launch_bounds__(256, 2) gemm_h3_rowln(GemmArgs g, RowLnArgs ln
     if (ln.amax) h3_amax_commit(ln.amax, vmax);
 }
 
-// bf16 inference variant: Z bf16 in, bf16(LeakyReLU(bf16(LN(Z)))) out (torch bf16 module chain).
+// bf16 inference variant: Z bf16 in, bf16(act(bf16(LN(Z)))) out (torch bf16 module chain), act = act_fwd<ACT>.
 // With MAXH >= 8 columns per lane, lane l owns the 8-column groups at 8 l + 512 q (each 16-byte
 // load / store instruction of a wave covers one contiguous 1 KB span); gamma / beta in registers;
 // each wave walks LNF_ROWS/4 rows.
@@ -1521,7 +1556,7 @@ template <int MAXH>
 DEV int hcol(int lane, int q) {
     return MAXH >= 8 ? 8 * lane + 512 * (q >> 3) + (q & 7) : MAXH * lane + q;
 }
-template <int MAXH, bool F16>
+template <int MAXH, bool F16, int ACT = ACT_LEAKY>
 __global__ void __launch_bounds__(256) ln_act_fwd_bf16(const uint16_t* Z, const uint16_t* gamma, const uint16_t* beta, int R,
                                                       int H, float slope, int use_ln, uint16_t* out) {
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1575,7 +1610,7 @@ __global__ void __launch_bounds__(256) ln_act_fwd_bf16(const uint16_t* Z, const 
 #pragma unroll
         for (int q = 0; q < MAXH; q++) {
             float hv = use_ln ? h2f<F16>(f2h<F16>((v[q] - mean) * rs * g[q] + b[q])) : v[q];
-            o[q] = f2h<F16>(hv > 0.f ? hv : hv * slope);
+            o[q] = f2h<F16>(act_fwd<ACT>(hv, slope));
         }
         uint16_t* op = out + (int64_t)row * H;
         if (vec) {
@@ -1597,19 +1632,19 @@ __global__ void __launch_bounds__(256) ln_act_fwd_bf16(const uint16_t* Z, const 
     }
 }
 
-// Backward of LeakyReLU(LN(Z)): dZ from dA; per-block column partials of
+// Backward of act(LN(Z)), act = act_fwd<ACT>: dZ from dA; per-block column partials of
 // dbias = sum dZ, dgamma = sum dH*xhat, dbeta = sum dH -> part[blk][3][H] (the flat parameter
 // order Linear.bias, LayerNorm.weight, LayerNorm.bias, so one reduction serves all three).
 // Columns per lane: lcol (float4 loads / stores); gamma / beta stay in registers; each of the 4
 // waves walks LNB_ROWS/4 rows.
 constexpr int LNB_ROWS = 32;
 constexpr int LNB_ROWS_MIN = 16;  // fewest rows per block of any variant (partial buffers are sized for it)
-// The LayerNorm + LeakyReLU backward of one row that a wave holds in lcol layout: x the pre-norm z (left as
+// The LayerNorm + activation backward of one row that a wave holds in lcol layout: x the pre-norm z (left as
 // xhat), av the activation's gradient, st the row's (mean, rstd); writes the dZ row and adds the row to the
 // wave's column partials pz / pg / pb (and, HEAD, the rank-1 head's ph / phb with the row's dv) and to max |dZ|.
 // The one statement of this arithmetic: ln_act_bwd (dA rows loaded from memory) and gemm_h3_row_lnbwd (dA rows
 // staged in LDS by the GEMM that produced them) both call it, so their bits agree.
-template <int MAXH, bool HEAD>
+template <int MAXH, bool HEAD, int ACT = ACT_LEAKY>
 DEV void lnb_row(float (&x)[MAXH], const float (&av)[MAXH], const float2 st, float dv, const float (&g)[MAXH],
                  const float (&b)[MAXH], float slope, int use_ln, int H, bool vec, int lane, float* dz, float (&pz)[MAXH],
                  float (&pg)[MAXH], float (&pb)[MAXH], float (&ph)[MAXH], float& phb, uint32_t& vmax) {
@@ -1622,13 +1657,13 @@ DEV void lnb_row(float (&x)[MAXH], const float (&av)[MAXH], const float2 st, flo
 #pragma unroll
     for (int q = 0; q < MAXH; q++) {
         float h = x[q] * g[q] + b[q];
-        dh[q] = h > 0.f ? av[q] : av[q] * slope;
+        dh[q] = act_bwd<ACT>(h, av[q], slope);
         float gg = dh[q] * g[q];
         s1 += gg;
         s2 += gg * x[q];
         // the rank-1 head's weight gradient dv * act, act recomputed as the forward made it
         // (per-lane sums over the wave's rows in row order)
-        if (HEAD && lcol<MAXH>(lane, q) < H) ph[q] += dv * (h > 0.f ? h : h * slope);
+        if (HEAD && lcol<MAXH>(lane, q) < H) ph[q] += dv * act_fwd<ACT>(h, slope);
     }
     if (HEAD) phb += dv;
     float d[MAXH];
@@ -1666,7 +1701,7 @@ DEV void lnb_row(float (&x)[MAXH], const float (&av)[MAXH], const float2 st, flo
 }
 // ROWS rows per block, PR rows per wave and pass (loads issued before the reductions); every wave
 // adds its rows to its partials in ascending order whatever PR is, so PR changes no bit
-template <int MAXH, bool HEAD = false, int ROWS = LNB_ROWS, int PR = 2>
+template <int MAXH, bool HEAD = false, int ACT = ACT_LEAKY, int ROWS = LNB_ROWS, int PR = 2>
 __global__ void __launch_bounds__(256) ln_act_bwd(const float* dA, const float* Z, const float2* stats, const float* gamma,
                                                  const float* beta, int R, int H, float slope, int use_ln, float* dZ,
                                                  float* part, float* amax, const float* head_dv = nullptr,
@@ -1733,7 +1768,7 @@ __global__ void __launch_bounds__(256) ln_act_bwd(const float* dA, const float* 
         for (int j = 0; j < PR; j++) {
             const int row = r0 + rr + 4 * j;
             if (row >= R) break;
-            lnb_row<MAXH, HEAD>(xs[j], as[j], sts[j], dvs[j], g, b, slope, use_ln, H, vec, lane, dZ + (int64_t)row * H, pz, pg,
+            lnb_row<MAXH, HEAD, ACT>(xs[j], as[j], sts[j], dvs[j], g, b, slope, use_ln, H, vec, lane, dZ + (int64_t)row * H, pz, pg,
                                 pb, ph, phb, vmax);
         }
     }
@@ -1765,7 +1800,7 @@ __global__ void __launch_bounds__(256) ln_act_bwd(const float* dA, const float* 
 }
 
 // ---- Full-row H3 input-gradient GEMM with the LayerNorm + LeakyReLU backward of the layer below in the same
-// launch (gemm_h3_row_lnbwd): a gemm_x6<A_IK, B_JK, pre-split B, H3> dA GEMM of 512 output columns + the
+// launch (gemm_h3_row_lnbwd; LeakyReLU / ReLU only, as gemm_h3_rowln: ppo.hip rowfuse_bwd): a gemm_x6<A_IK, B_JK, pre-split B, H3> dA GEMM of 512 output columns + the
 // ln_act_bwd<8> that reads it.  gemm_h3_rowln's tile, prologue and K loop (h3_row_kloop) on the fragment-order
 // copy of the layer's backward planes; the epilogue value is h3_out's with gemm_x6's arguments (no bias: 0.f).
 // The finished dA rows are staged in LDS, 32 rows at a time, and never reach memory: each wave takes whole
@@ -1876,7 +1911,7 @@ constexpr int LNW_ROWS = 32;
 DEV int wcol(int k) { return 4 * (int)threadIdx.x + 1024 * k; }
 DEV float4 ld4(const float* p, int c, int H) { return c < H ? *reinterpret_cast<const float4*>(p + c) : make_float4(0.f, 0.f, 0.f, 0.f); }
 
-template <int NV, int LNW_RB = 4>
+template <int NV, int ACT = ACT_LEAKY, int LNW_RB = 4>
 __global__ void __launch_bounds__(256) ln_act_fwd_wide(const float* Z, const float* gamma, const float* beta, int R, int H,
                                                       float slope, int use_ln, float* act, float2* stats, float* amax,
                                                       const float*, const float*, float*) {
@@ -1949,7 +1984,7 @@ __global__ void __launch_bounds__(256) ln_act_fwd_wide(const float* Z, const flo
                 for (int e = 0; e < 4; e++) {
                     const float xh = use_ln ? (vv[e] - mean[j]) * rs[j] : vv[e];
                     const float hv = use_ln ? xh * gg[e] + bb[e] : xh;
-                    a[e] = hv > 0.f ? hv : hv * slope;
+                    a[e] = act_fwd<ACT>(hv, slope);
                     const uint32_t bits = abs_bits(a[e]);
                     vmax = bits > vmax ? bits : vmax;
                 }
@@ -1961,7 +1996,7 @@ __global__ void __launch_bounds__(256) ln_act_fwd_wide(const float* Z, const flo
     if (amax) h3_amax_commit(amax, vmax);
 }
 
-template <int NV, int LNW_RB = 4>
+template <int NV, int ACT = ACT_LEAKY, int LNW_RB = 4>
 __global__ void __launch_bounds__(256) ln_act_bwd_wide(const float* dA, const float* Z, const float2* stats, const float* gamma,
                                                       const float* beta, int R, int H, float slope, int use_ln, float* dZ,
                                                       float* part, float* amax, const float*, const float*, float*) {
@@ -2003,7 +2038,7 @@ __global__ void __launch_bounds__(256) ln_act_bwd_wide(const float* dA, const fl
                 for (int e = 0; e < 4; e++) {
                     if (use_ln) x[j][k][e] = (x[j][k][e] - st[j].x) * st[j].y;  // the forward's xhat, same ops
                     const float h = x[j][k][e] * gg[e] + bb[e];
-                    dh[j][k][e] = h > 0.f ? dh[j][k][e] : dh[j][k][e] * slope;
+                    dh[j][k][e] = act_bwd<ACT>(h, dh[j][k][e], slope);
                     const float t = dh[j][k][e] * gg[e];
                     s1 += t;
                     s2 += t * x[j][k][e];
@@ -2066,69 +2101,77 @@ __global__ void __launch_bounds__(256) ln_act_bwd_wide(const float* dA, const fl
 }
 
 // the wide kernels for H in (512, 4096] with H % 4 == 0 (null: not applicable)
+template <int ACT>
 inline decltype(&ln_act_fwd_wide<2>) ln_act_fwd_wide_any(int H) {
     if (H <= 512 || H % 4 != 0 || H > 4096) return nullptr;
-    if (H <= 1024) return &ln_act_fwd_wide<1>;
-    if (H <= 2048) return &ln_act_fwd_wide<2>;
-    return &ln_act_fwd_wide<4>;
+    if (H <= 1024) return &ln_act_fwd_wide<1, ACT>;
+    if (H <= 2048) return &ln_act_fwd_wide<2, ACT>;
+    return &ln_act_fwd_wide<4, ACT>;
 }
+template <int ACT>
 inline decltype(&ln_act_bwd_wide<2>) ln_act_bwd_wide_any(int H) {
     if (H <= 512 || H % 4 != 0 || H > 4096) return nullptr;
-    if (H <= 1024) return &ln_act_bwd_wide<1>;
-    if (H <= 2048) return &ln_act_bwd_wide<2>;
-    return &ln_act_bwd_wide<4>;
+    if (H <= 1024) return &ln_act_bwd_wide<1, ACT>;
+    if (H <= 2048) return &ln_act_bwd_wide<2, ACT>;
+    return &ln_act_bwd_wide<4, ACT>;
 }
 
-// NPER (columns per lane) dispatch: H <= 64 * NPER
-#define RLGPU_NPER_DISPATCH(NAME)                                  \
-    inline decltype(&NAME<16>) NAME##_any(int H) {                 \
-        if (H <= 64) return &NAME<1>;                              \
-        if (H <= 128) return &NAME<2>;                             \
-        if (H <= 256) return &NAME<4>;                             \
-        if (H <= 512) return &NAME<8>;                             \
-        if (H <= 1024) return &NAME<16>;                           \
-        return &NAME<32>;                                          \
-    }
-RLGPU_NPER_DISPATCH(ln_act_fwd_f32)
+// NPER (columns per lane) dispatch: H <= 64 * NPER.  KERN<NPER, PRE..., ACT> for every kind ACT
+#define RLGPU_NPER_RETURN(H, KERN, ...)                 \
+    if (H <= 64) return &KERN<1, __VA_ARGS__>;          \
+    if (H <= 128) return &KERN<2, __VA_ARGS__>;         \
+    if (H <= 256) return &KERN<4, __VA_ARGS__>;         \
+    if (H <= 512) return &KERN<8, __VA_ARGS__>;         \
+    if (H <= 1024) return &KERN<16, __VA_ARGS__>;       \
+    return &KERN<32, __VA_ARGS__>
+template <int ACT>
+inline decltype(&ln_act_fwd_f32<16>) ln_act_fwd_f32_any(int H) {
+    RLGPU_NPER_RETURN(H, ln_act_fwd_f32, ACT);
+}
+template <bool F16, int ACT>
+inline decltype(&ln_act_fwd_bf16<16, F16>) ln_act_fwd_bf16_any_of(int H) {
+    RLGPU_NPER_RETURN(H, ln_act_fwd_bf16, F16, ACT);
+}
+// the 16-bit inference LayerNorm / activation kernel of width H for the activation kind act
 template <bool F16>
-inline decltype(&ln_act_fwd_bf16<16, F16>) ln_act_fwd_bf16_any(int H) {
-    if (H <= 64) return &ln_act_fwd_bf16<1, F16>;
-    if (H <= 128) return &ln_act_fwd_bf16<2, F16>;
-    if (H <= 256) return &ln_act_fwd_bf16<4, F16>;
-    if (H <= 512) return &ln_act_fwd_bf16<8, F16>;
-    if (H <= 1024) return &ln_act_fwd_bf16<16, F16>;
-    return &ln_act_fwd_bf16<32, F16>;
+inline decltype(&ln_act_fwd_bf16<16, F16>) ln_act_fwd_bf16_any(int H, int act) {
+    if (act == ACT_SIGMOID) return ln_act_fwd_bf16_any_of<F16, ACT_SIGMOID>(H);
+    if (act == ACT_TANH) return ln_act_fwd_bf16_any_of<F16, ACT_TANH>(H);
+    return ln_act_fwd_bf16_any_of<F16, ACT_LEAKY>(H);
 }
-RLGPU_NPER_DISPATCH(ln_act_bwd)
-// the variant that also emits a following rank-1 head's dw / db partials (head_part)
-inline decltype(&ln_act_bwd<16, true>) ln_act_bwd_head_any(int H) {
-    if (H <= 64) return &ln_act_bwd<1, true>;
-    if (H <= 128) return &ln_act_bwd<2, true>;
-    if (H <= 256) return &ln_act_bwd<4, true>;
-    if (H <= 512) return &ln_act_bwd<8, true>;
-    if (H <= 1024) return &ln_act_bwd<16, true>;
-    return &ln_act_bwd<32, true>;
+// HEAD: the variant that also emits a following rank-1 head's dw / db partials (head_part)
+template <bool HEAD, int ACT>
+inline decltype(&ln_act_bwd<16>) ln_act_bwd_any(int H) {
+    RLGPU_NPER_RETURN(H, ln_act_bwd, HEAD, ACT);
 }
 
-// The LayerNorm kernels by width: the wide workgroup-per-row-group kernels above 512 columns (not for the
-// rank-1 head's fused backward), the wave-per-row kernels below.
-inline decltype(&ln_act_fwd_f32<8>) ln_act_fwd_f32_pick(int H, int* rows, bool head = false) {
+// The LayerNorm kernels by width and activation kind: the wide workgroup-per-row-group kernels above 512 columns
+// (not for the rank-1 head's fused backward), the wave-per-row kernels below.
+template <int ACT>
+inline decltype(&ln_act_fwd_f32<8>) ln_act_fwd_f32_pick_of(int H, int* rows, bool head) {
     *rows = LNF_ROWS;
     if (!head)
-        if (auto f = ln_act_fwd_wide_any(H)) {
+        if (auto f = ln_act_fwd_wide_any<ACT>(H)) {
             *rows = LNW_ROWS;
             return f;
         }
-    return ln_act_fwd_f32_any(H);
+    return ln_act_fwd_f32_any<ACT>(H);
 }
-inline decltype(&ln_act_bwd<8>) ln_act_bwd_pick(int H, bool head, int* rows) {
+template <int ACT>
+inline decltype(&ln_act_bwd<8>) ln_act_bwd_pick_of(int H, bool head, int* rows) {
     *rows = LNB_ROWS;
     if (!head)
-        if (auto f = ln_act_bwd_wide_any(H)) {
+        if (auto f = ln_act_bwd_wide_any<ACT>(H)) {
             *rows = LNW_ROWS;
             return f;
         }
-    return head ? ln_act_bwd_head_any(H) : ln_act_bwd_any(H);
+    return head ? ln_act_bwd_any<true, ACT>(H) : ln_act_bwd_any<false, ACT>(H);
+}
+inline decltype(&ln_act_fwd_f32<8>) ln_act_fwd_f32_pick(int act, int H, int* rows, bool head = false) {
+    return RLGPU_ACT_SWITCH(act, ln_act_fwd_f32_pick_of, H, rows, head);
+}
+inline decltype(&ln_act_bwd<8>) ln_act_bwd_pick(int act, int H, bool head, int* rows) {
+    return RLGPU_ACT_SWITCH(act, ln_act_bwd_pick_of, H, head, rows);
 }
 
 // One tile of a deterministic column reduction of per-block partials: tile (x, y) of a G-group grid sums the

@@ -48,11 +48,12 @@ struct Layer {
 
 struct Model {
     std::vector<Layer> L;  // hidden layers then the output layer (last; none for the shared head)
-    bool head_only = false;  // the shared head: every layer is [Linear -> LayerNorm -> LeakyReLU]
+    bool head_only = false;  // the shared head: every layer is [Linear -> LayerNorm -> activation]
     int in, out;
     int64_t off, count;
     float lr;
     int mode = 0;  // training GEMM arithmetic (rlgpu_ppo_config.train_gemm)
+    int akind = mlp::ACT_LEAKY;  // activation kind of the hidden layers (mlp::act_fwd)
     // fp32 training workspace (per model, so the two models' passes can overlap on two streams)
     std::vector<float*> xhat, act, rstd;
     float *y = nullptr, *dy = nullptr, *dA = nullptr, *dZ = nullptr, *mid = nullptr;  // y: model output
@@ -75,9 +76,9 @@ struct Model {
 // One Linear layer of a model's 16-bit inference forward (rlgpu_ppo::chain)
 struct Link {
     const Layer* L;
-    bool hidden;  // [Linear -> LayerNorm -> LeakyReLU]; false: the output Linear
+    bool hidden;  // [Linear -> LayerNorm -> activation]; false: the output Linear
 };
-// hidden [Linear -> LayerNorm -> LeakyReLU] layers of a model (all of the shared head's)
+// hidden [Linear -> LayerNorm -> activation] layers of a model (all of the shared head's)
 inline int nhid(const Model& m) { return (int)m.L.size() - (m.head_only ? 0 : 1); }
 constexpr int kAmaxDZ = RLGPU_MAX_LAYERS, kAmaxOut = 2 * RLGPU_MAX_LAYERS, kAmaxSlots = 2 * RLGPU_MAX_LAYERS + 1;
 inline bool split_mode(int mode) { return mode == RLGPU_GEMM_F32X6 || mode == RLGPU_GEMM_F16X3; }
@@ -109,7 +110,8 @@ inline bool h3_quad(int J) {
 // Hidden layer L of forward_train on the full-row kernel mlp::gemm_h3_rowln (the H3 forward GEMM with its
 // LayerNorm + LeakyReLU in the same launch; same bits as gemm_x6 + ln_act_fwd_f32).  Eligible output width:
 // exactly 512 columns (mlp::RLN_J: the kernel's tile is the whole row, and its LayerNorm part is
-// ln_act_fwd_f32<8>'s column layout); every other width keeps the two-kernel path.  RLGPU_H3_ROWFUSE=0:
+// ln_act_fwd_f32<8>'s column layout); every other width keeps the two-kernel path, and so does every layer of a
+// SIGMOID / TANH model (the full-row kernels are single LeakyReLU kernels: gemm_x6 + ln_act_fwd_f32<8, ACT>).  RLGPU_H3_ROWFUSE=0:
 // never, 1: every eligible layer; unset: on (C2 minibatch 1.57 -> 1.49 ms, learn phase 126.9 -> 120.2 ms per
 // iteration against the two-kernel path, profiles/r07a_rowfuse_bench_pairs.txt).
 // The one predicate behind both the launch (forward_train) and the fragment-order planes it reads
@@ -117,12 +119,13 @@ inline bool h3_quad(int J) {
 constexpr bool kRowFuseDefault = true;
 inline bool rowfuse_fwd(const Model& m, const Layer& L) {
     static const int knob = tri_knob("RLGPU_H3_ROWFUSE");
-    return m.mode == RLGPU_GEMM_F16X3 && L.out == mlp::RLN_J && L.fwd.frag >= 0 && knob_or(knob, kRowFuseDefault);
+    return m.mode == RLGPU_GEMM_F16X3 && m.akind == mlp::ACT_LEAKY && L.out == mlp::RLN_J && L.fwd.frag >= 0 &&
+           knob_or(knob, kRowFuseDefault);
 }
 // The input-gradient GEMM of layer L on the full-row kernel mlp::gemm_h3_row_lnbwd (the H3 dA GEMM of a layer with
 // the LayerNorm + LeakyReLU backward of the hidden layer below it in the same launch; dA is never stored; same
 // bits as gemm_x6 + ln_act_bwd<8>).  Eligible: a layer of exactly 512 inputs (mlp::RLN_J) above a hidden layer
-// (`below`; null for a model's first layer); everything else keeps the two-kernel path.
+// (`below`; null for a model's first layer) of a LeakyReLU / ReLU model; everything else keeps the two-kernel path.
 // RLGPU_H3_ROWFUSE_BWD=0: never, 1: every eligible layer; unset: on
 // (C2 minibatch 1.49 -> 1.36 ms, learn phase 122.1 -> 110.8 ms per iteration against the two-kernel path,
 // profiles/r08a_rowfuse_bwd_bench_pairs.txt).  Independent of RLGPU_H3_ROWFUSE.
@@ -130,7 +133,7 @@ inline bool rowfuse_fwd(const Model& m, const Layer& L) {
 constexpr bool kRowFuseBwdDefault = true;
 inline bool rowfuse_bwd(const Model& m, const Layer& L, const Layer* below) {
     static const int knob = tri_knob("RLGPU_H3_ROWFUSE_BWD");
-    return m.mode == RLGPU_GEMM_F16X3 && below && below->out == mlp::RLN_J && L.in == mlp::RLN_J && L.bwd.frag >= 0 &&
+    return m.mode == RLGPU_GEMM_F16X3 && m.akind == mlp::ACT_LEAKY && below && below->out == mlp::RLN_J && L.in == mlp::RLN_J && L.bwd.frag >= 0 &&
            knob_or(knob, kRowFuseBwdDefault);
 }
 inline int gemm_slots(int mode) {
@@ -528,7 +531,7 @@ void forward_train(rlgpu_ppo* h, int mi, const Operand& x, int n, float* out, hi
     for (int l = 0; l < nh; l++) {
         const Layer& L = m.L[l];
         const bool fuse = head1 && l == nh - 1;
-        // LayerNorm + LeakyReLU of z = m.xhat[l] into m.act[l] (and the rank-1 head's output)
+        // LayerNorm + activation of z = m.xhat[l] into m.act[l] (and the rank-1 head's output)
         const mlp::RowLnArgs ln{L.g >= 0 ? P + L.g : nullptr, L.be >= 0 ? P + L.be : nullptr, h->cfg.leaky_slope, h->cfg.layer_norm,
                                 m.act[l], reinterpret_cast<float2*>(m.rstd[l]), amax_slot(m, l), fuse ? P + O->w : nullptr,
                                 fuse ? P + O->b : nullptr, fuse ? out : nullptr};
@@ -544,7 +547,7 @@ void forward_train(rlgpu_ppo* h, int mi, const Operand& x, int n, float* out, hi
             // bytes: z read, act written, (mean, rstd) written
             ktime::Span span(ktime::LN_FWD, (double)n * (8.0 * L.out + 8.0), s);
             int lnf_rows = 0;
-            const auto lnf = mlp::ln_act_fwd_f32_pick(L.out, &lnf_rows, fuse);
+            const auto lnf = mlp::ln_act_fwd_f32_pick(m.akind, L.out, &lnf_rows, fuse);
             hipLaunchKernelGGL(lnf, dim3(ceil_div(n, lnf_rows)), dim3(256), 0, s, m.xhat[l], ln.gamma, ln.beta, n, L.out, ln.slope,
                                ln.use_ln, ln.act, ln.stats, ln.amax, ln.head_w, ln.head_b, ln.head_out);
             RLGPU_CHECK_HIP(hipGetLastError());
@@ -621,7 +624,7 @@ void backward(rlgpu_ppo* h, int mi, const Operand& x, int n, const float* dout, 
         const float* bb = L.be >= 0 ? P + L.be : nullptr;
         const bool r1 = rank1 && l == nh - 1;  // dA of the rank-1 head, recomputed in the kernel
         int lnb_rows = 0;
-        const auto lnb = mlp::ln_act_bwd_pick(L.out, r1, &lnb_rows);
+        const auto lnb = mlp::ln_act_bwd_pick(m.akind, L.out, r1, &lnb_rows);
         // this layer's dZ: never the buffer its dA is in
         float* dz = fused_dz ? fused_dz : (dA_in == m.dZ ? m.dA : m.dZ);
         const int nb = (int)ceil_div(n, lnb_rows);
@@ -695,7 +698,8 @@ const uint16_t* forward_half(rlgpu_ppo* h, int mi, const float* X, int n, hipStr
         if (!k.hidden) return h->logits_h;
         const uint16_t* gg = L.hg >= 0 ? P + L.hg : nullptr;
         const uint16_t* bb = L.hbe >= 0 ? P + L.hbe : nullptr;
-        hipLaunchKernelGGL(f16(h) ? mlp::ln_act_fwd_bf16_any<true>(L.out) : mlp::ln_act_fwd_bf16_any<false>(L.out), dim3(ceil_div(n, mlp::LNF_ROWS)), dim3(256), 0, s, h->zh, gg, bb, n, L.out,
+        hipLaunchKernelGGL(f16(h) ? mlp::ln_act_fwd_bf16_any<true>(L.out, h->cfg.activation) : mlp::ln_act_fwd_bf16_any<false>(L.out, h->cfg.activation),
+                           dim3(ceil_div(n, mlp::LNF_ROWS)), dim3(256), 0, s, h->zh, gg, bb, n, L.out,
                            h->cfg.leaky_slope, h->cfg.layer_norm, h->ah[cur]);
         RLGPU_CHECK_HIP(hipGetLastError());
         in = h->ah[cur];
@@ -805,7 +809,11 @@ void infer_fused(rlgpu_ppo* h, int mi, bool ver, const Rows& r, float* out_f, co
     if (a.trace && ceil_div(n, infer::IR) * 16 > g_infer_trace_cap)
         throw rlgpu::Error(RLGPU_ERR_INVALID_ARG, "rlgpu_debug_infer_trace: buffer of " + std::to_string(g_infer_trace_cap) +
                                                       " entries, this launch needs " + std::to_string(ceil_div(n, infer::IR) * 16));
-    RLGPU_H16_LAUNCH(f16(h), infer::mlp_infer, dim3(ceil_div(n, infer::IR)), dim3(infer::IT), 0, s, a);
+    // the LeakyReLU / ReLU instances are this unit's; SIGMOID / TANH: infer_act.hip
+    if (h->cfg.activation != mlp::ACT_LEAKY)
+        rlgpu::launch_mlp_infer_act(h->cfg.activation, f16(h), ceil_div(n, infer::IR), s, &a, sizeof(a));
+    else
+        RLGPU_H16_LAUNCH(f16(h), infer::mlp_infer, dim3(ceil_div(n, infer::IR)), dim3(infer::IT), 0, s, a);
     RLGPU_CHECK_HIP(hipGetLastError());
 }
 
@@ -885,6 +893,7 @@ void build_model(rlgpu_ppo* h, Model& m, int in, const int32_t* layers, int nl, 
     m.out = m.head_only ? layers[nl] : out;
     m.lr = lr;
     m.mode = h->cfg.train_gemm;
+    m.akind = h->cfg.activation;
     m.off = h->nparams;
     int prev = in;
     for (int l = 0; l <= nl; l++) {
@@ -924,9 +933,9 @@ void build_model(rlgpu_ppo* h, Model& m, int in, const int32_t* layers, int nl, 
             const bool h3 = m.mode == RLGPU_GEMM_F16X3;
             // fragment-order copies: a hidden layer's own full row forward, and backward where a hidden layer below
             // consumes this layer's dA (the first layer's goes to the model input)
-            L.fwd = add_side(m, L.out, L.in, h3 && hidden && L.out == mlp::RLN_J);
+            L.fwd = add_side(m, L.out, L.in, h3 && m.akind == mlp::ACT_LEAKY && hidden && L.out == mlp::RLN_J);
             if (l > 0 || input_grad)  // dA of the first layer only behind the shared head
-                L.bwd = add_side(m, L.in, L.out, h3 && l > 0 && L.in == mlp::RLN_J);
+                L.bwd = add_side(m, L.in, L.out, h3 && m.akind == mlp::ACT_LEAKY && l > 0 && L.in == mlp::RLN_J);
         }
         m.L.push_back(L);
         prev = L.out;
@@ -966,6 +975,9 @@ void refresh_half(rlgpu_ppo* h, hipStream_t s) {
     }
 }
 
+static_assert(mlp::ACT_LEAKY == RLGPU_ACT_LEAKY_RELU && mlp::ACT_SIGMOID == RLGPU_ACT_SIGMOID && mlp::ACT_TANH == RLGPU_ACT_TANH,
+              "mlp::ACT_* are rlgpu_ppo_config.activation's values");
+
 }  // namespace
 
 extern "C" int32_t rlgpu_ppo_config_size(void) { return (int32_t)sizeof(rlgpu_ppo_config); }
@@ -980,6 +992,8 @@ extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
         RLGPU_REQUIRE(std::isfinite(cfg->policy_temperature) && cfg->policy_temperature >= 0.f,
                       "policy_temperature must be finite and > 0 (0 = the default, 1)");
         RLGPU_REQUIRE(cfg->mask_entropy == 0 || cfg->mask_entropy == 1, "mask_entropy must be 0 or 1");
+        RLGPU_REQUIRE(cfg->activation >= RLGPU_ACT_LEAKY_RELU && cfg->activation <= RLGPU_ACT_TANH,
+                      "activation must be RLGPU_ACT_LEAKY_RELU (0), _RELU (1), _SIGMOID (2) or _TANH (3)");
         RLGPU_REQUIRE(cfg->n_policy_layers >= 1 && cfg->n_policy_layers <= RLGPU_MAX_LAYERS && cfg->n_critic_layers >= 1 &&
                           cfg->n_critic_layers <= RLGPU_MAX_LAYERS,
                       "1..8 hidden layers per model");
@@ -995,6 +1009,10 @@ extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
         try {
             h->cfg = *cfg;
             if (h->cfg.policy_temperature == 0.f) h->cfg.policy_temperature = 1.f;
+            if (h->cfg.activation == RLGPU_ACT_RELU) {  // the kernels' LEAKY kind with slope 0
+                h->cfg.activation = RLGPU_ACT_LEAKY_RELU;
+                h->cfg.leaky_slope = 0.f;
+            }
             const bool sh = cfg->n_shared_layers > 0;
             h->nm = sh ? 3 : 2;
             // PPOLearner::MakeModels (PPOLearner.cpp:42-74): behind a shared head the policy / critic

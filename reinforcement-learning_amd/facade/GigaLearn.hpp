@@ -504,6 +504,8 @@ struct ModelSpec {
     const char* name;   // Model::modelName
     int inputs, outputs;
     std::vector<int> layers;
+    bool layerNorm = true;                   // ModelConfig::addLayerNorm
+    const char* activation = "leaky_relu";   // ModelConfig::activationType, as rlgpu_optim_lt names it
     std::string FileName(const char* suffix = "") const {  // GetSuffixedSavePath: upper-cased name + suffix + .lt
         std::string n = name;
         for (auto& c : n) c = (char)std::toupper((unsigned char)c);
@@ -512,17 +514,22 @@ struct ModelSpec {
     std::vector<std::string> HelperShape() const {
         std::vector<std::string> a{std::to_string(inputs), std::to_string(outputs)};
         for (int h : layers) a.push_back(std::to_string(h));
+        if (!layerNorm) a.push_back("--no-layer-norm");
+        a.push_back("--activation");
+        a.push_back(activation);
         return a;
     }
-    // parameter shapes in parameters() order (Linear weight [out, in], bias, LayerNorm weight, bias; output Linear)
+    // parameter shapes in parameters() order (Linear weight [out, in], bias, with LayerNorm its weight, bias; output Linear)
     std::vector<std::string> ParamShapes() const {
         std::vector<std::string> s;
         int last = inputs;
         for (int h : layers) {
             s.push_back(std::to_string(h) + "x" + std::to_string(last));
             s.push_back(std::to_string(h));
-            s.push_back(std::to_string(h));
-            s.push_back(std::to_string(h));
+            if (layerNorm) {
+                s.push_back(std::to_string(h));
+                s.push_back(std::to_string(h));
+            }
             last = h;
         }
         if (outputs > 0) {
@@ -697,10 +704,12 @@ inline void Learner::ValidateConfig(const LearnerConfig& c) {
         if (k == 2 && !m.IsValid()) continue;
         if (!m.IsValid()) bad(std::string("ppo.") + names[k] + " has no layers");
         if ((int)m.layerSizes.size() > RLGPU_MAX_LAYERS) bad(std::string("ppo.") + names[k] + ": more than 8 layers");
-        if (!m.addLayerNorm) bad(std::string("ppo.") + names[k] + ".addLayerNorm = false is not supported");
-        if (m.activationType != ModelActivationType::LEAKY_RELU && m.activationType != ModelActivationType::RELU)
-            bad(std::string("ppo.") + names[k] + ".activationType must be LEAKY_RELU or RELU");
+        if (m.activationType != ModelActivationType::RELU && m.activationType != ModelActivationType::LEAKY_RELU &&
+            m.activationType != ModelActivationType::SIGMOID && m.activationType != ModelActivationType::TANH)
+            bad(std::string("ppo.") + names[k] + ".activationType must be RELU, LEAKY_RELU, SIGMOID or TANH");
+        // one setting for every model: per-model activationType / addLayerNorm are not supported
         if (m.activationType != c.ppo.policy.activationType) bad("every model must use the same activationType");
+        if (m.addLayerNorm != c.ppo.policy.addLayerNorm) bad("every model must use the same addLayerNorm");
         if (m.optimType != ModelOptimType::ADAMW && m.optimType != ModelOptimType::ADAM)
             bad(std::string("ppo.") + names[k] + ".optimType must be ADAMW or ADAM");
         if (m.optimType != c.ppo.policy.optimType) bad("every model must use the same optimType");
@@ -768,7 +777,12 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
     c.infer_fp16 = config.ppo.useHalfPrecision ? RLGPU_INFER_BF16 : RLGPU_INFER_F32;
     c.train_gemm = options.trainGemm;
     c.arith = options.arith;
-    c.activation = config.ppo.policy.activationType == ModelActivationType::RELU ? RLGPU_ACT_RELU : RLGPU_ACT_LEAKY_RELU;
+    const ModelActivationType at = config.ppo.policy.activationType;  // of every model (ValidateConfig)
+    c.activation = at == ModelActivationType::RELU      ? RLGPU_ACT_RELU
+                   : at == ModelActivationType::SIGMOID ? RLGPU_ACT_SIGMOID
+                   : at == ModelActivationType::TANH    ? RLGPU_ACT_TANH
+                                                        : RLGPU_ACT_LEAKY_RELU;
+    c.no_layer_norm = config.ppo.policy.addLayerNorm ? 0 : 1;
     c.optimizer = config.ppo.policy.optimType == ModelOptimType::ADAM ? RLGPU_OPT_ADAM : RLGPU_OPT_ADAMW;
     c.rank = options.rank;
     c.world = options.world;
@@ -794,9 +808,14 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
 
     // the PPO handle's models (PPOLearner::MakeModels): shared head feeds policy and critic
     const int feat = c.n_shared_layers ? config.ppo.sharedHead.layerSizes.back() : RLGPU_OBS;
-    models.push_back({0, "policy", feat, RLGPU_ACTIONS, config.ppo.policy.layerSizes});
-    models.push_back({1, "critic", feat, 1, config.ppo.critic.layerSizes});
-    if (c.n_shared_layers) models.push_back({2, "shared_head", RLGPU_OBS, 0, config.ppo.sharedHead.layerSizes});
+    const bool ln = c.no_layer_norm == 0;
+    const char* an = at == ModelActivationType::RELU      ? "relu"
+                     : at == ModelActivationType::SIGMOID ? "sigmoid"
+                     : at == ModelActivationType::TANH    ? "tanh"
+                                                          : "leaky_relu";
+    models.push_back({0, "policy", feat, RLGPU_ACTIONS, config.ppo.policy.layerSizes, ln, an});
+    models.push_back({1, "critic", feat, 1, config.ppo.critic.layerSizes, ln, an});
+    if (c.n_shared_layers) models.push_back({2, "shared_head", RLGPU_OBS, 0, config.ppo.sharedHead.layerSizes, ln, an});
     std::printf("Model parameter counts:\n");
     int64_t total = 0;
     for (int m : {0, 1, 2}) {

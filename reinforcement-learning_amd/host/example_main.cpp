@@ -21,7 +21,8 @@
 //
 //   rlgpu_train [--iterations N] [--arenas A] [--rollout T] [--trajectories] [--f32-gemm] [--c2-model] [--seed S]
 //               [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] [--self-play] [--fp32-inference]
-//               [--policy-temperature X] [--mask-entropy] [--rank r --world N --rccl-id FILE [--rccl-nonce STR]]
+//               [--policy-temperature X] [--mask-entropy] [--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm]
+//               [--rank r --world N --rccl-id FILE [--rccl-nonce STR]]
 #include <execinfo.h>
 #include <signal.h>
 
@@ -170,6 +171,18 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(argv[i], "--fp32-inference")) cfg.ppo.useHalfPrecision = false;
             else if (!std::strcmp(argv[i], "--policy-temperature")) cfg.ppo.policyTemperature = std::strtof(next(), nullptr);
             else if (!std::strcmp(argv[i], "--mask-entropy")) cfg.ppo.maskEntropy = true;
+            else if (!std::strcmp(argv[i], "--activation")) {  // ModelConfig::activationType of every model
+                const std::string a = next();
+                ModelActivationType t;
+                if (a == "relu") t = ModelActivationType::RELU;
+                else if (a == "leaky_relu") t = ModelActivationType::LEAKY_RELU;
+                else if (a == "sigmoid") t = ModelActivationType::SIGMOID;
+                else if (a == "tanh") t = ModelActivationType::TANH;
+                else throw std::invalid_argument("activationType must be relu, leaky_relu, sigmoid or tanh, not " + a);
+                for (PartialModelConfig* m : {&cfg.ppo.policy, &cfg.ppo.critic, &cfg.ppo.sharedHead}) m->activationType = t;
+            } else if (!std::strcmp(argv[i], "--no-layer-norm")) {  // ModelConfig::addLayerNorm = false, every model
+                for (PartialModelConfig* m : {&cfg.ppo.policy, &cfg.ppo.critic, &cfg.ppo.sharedHead}) m->addLayerNorm = false;
+            }
             else if (!std::strcmp(argv[i], "--rank")) opt.rank = std::atoi(next());
             else if (!std::strcmp(argv[i], "--world")) opt.world = std::atoi(next());
             else if (!std::strcmp(argv[i], "--rccl-id")) idFile = next();
@@ -183,7 +196,8 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) {
             std::fprintf(stderr, "%s\nusage: %s [--iterations N] [--arenas A] [--rollout T] [--trajectories] [--f32-gemm] "
                                  "[--c2-model] [--seed S] [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] "
-                                 "[--self-play] [--fp32-inference] [--policy-temperature X] [--mask-entropy] [--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);
+                                 "[--self-play] [--fp32-inference] [--policy-temperature X] [--mask-entropy] "
+                                 "[--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm] [--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);
             return 2;
         }
     }

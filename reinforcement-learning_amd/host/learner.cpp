@@ -260,12 +260,14 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     pc.n_critic_layers = cfg.n_critic_layers;
     std::memcpy(pc.shared_layers, cfg.shared_layers, sizeof(pc.shared_layers));
     pc.n_shared_layers = cfg.n_shared_layers;
-    RLGPU_REQUIRE(cfg.activation == RLGPU_ACT_LEAKY_RELU || cfg.activation == RLGPU_ACT_RELU,
-                  "Learner: activation must be RLGPU_ACT_LEAKY_RELU or RLGPU_ACT_RELU");
+    RLGPU_REQUIRE(cfg.activation >= RLGPU_ACT_LEAKY_RELU && cfg.activation <= RLGPU_ACT_TANH,
+                  "Learner: activation must be RLGPU_ACT_LEAKY_RELU, _RELU, _SIGMOID or _TANH");
+    RLGPU_REQUIRE(cfg.no_layer_norm == 0 || cfg.no_layer_norm == 1, "Learner: no_layer_norm must be 0 or 1");
     RLGPU_REQUIRE(cfg.optimizer == RLGPU_OPT_ADAMW || cfg.optimizer == RLGPU_OPT_ADAM,
                   "Learner: optimizer must be RLGPU_OPT_ADAMW or RLGPU_OPT_ADAM");
-    pc.layer_norm = 1;
-    pc.leaky_slope = cfg.activation == RLGPU_ACT_RELU ? 0.f : 0.01f;
+    pc.layer_norm = cfg.no_layer_norm ? 0 : 1;
+    pc.activation = cfg.activation;
+    pc.leaky_slope = 0.01f;  // torch::nn::LeakyReLU's default; RLGPU_ACT_RELU is slope 0 in rlgpu_ppo_create
     pc.policy_lr = cfg.policy_lr;
     pc.critic_lr = cfg.critic_lr;
     pc.beta1 = 0.9f;

@@ -6,14 +6,17 @@
 // PyTorch (plumbing); rlgpu/checkpoint.py drives it.
 //
 // It also writes and reads the model archives <NAME>.lt (GGL::Model::Save / Load, Models.cpp:116-166): the
-// Sequential GGL::Model builds (Models.cpp:7-33: per hidden layer Linear, LayerNorm, LeakyReLU; then the output
-// Linear unless out is 0, the shared head's addOutputLayer = false) saved with torch::save(seq, stream) and
+// Sequential GGL::Model builds (Models.cpp:7-33: per hidden layer Linear, LayerNorm unless addLayerNorm is false,
+// the activation of AddActivationFunc; then the output Linear unless out is 0, the shared head's addOutputLayer =
+// false) saved with torch::save(seq, stream) and
 // read with torch::load(seq, stream), with Model::Load's parameter-size check.
 //
 // usage: rlgpu_optim_lt save <out.lt> <state.f32> <step> <lr> <beta1> <beta2> <eps> <weight_decay> <shape>...
 //        rlgpu_optim_lt load <in.lt> <state.f32> <shape>...
-//        rlgpu_optim_lt model-save <out.lt> <params.f32> <obs> <out> <h1> [h2 ...]
-//        rlgpu_optim_lt model-load <in.lt> <params.f32> <obs> <out> <h1> [h2 ...]
+//        rlgpu_optim_lt model-save <out.lt> <params.f32> <obs> <out> <h1> [h2 ...] [--no-layer-norm] [--activation NAME]
+//        rlgpu_optim_lt model-load <in.lt> <params.f32> <obs> <out> <h1> [h2 ...] [--no-layer-norm] [--activation NAME]
+//   --no-layer-norm: ModelConfig::addLayerNorm = false (no LayerNorm modules: the module indices, the archive's
+//   keys, shift); --activation relu | leaky_relu (default) | sigmoid | tanh: the archive holds no trace of it.
 //   params.f32: the model's parameters flat in parameters() order (model-load writes them).
 //   shape: dimensions joined by 'x' (e.g. 384x167), one per model parameter in parameters() order;
 //   state.f32: every parameter's exp_avg (flat, parameter order), then every exp_avg_sq.  load writes
@@ -47,14 +50,17 @@ std::vector<torch::Tensor> make_params(char** shapes, int n) {
     return ps;
 }
 
-torch::nn::Sequential make_model(int obs, int out, const std::vector<int>& layers) {
+torch::nn::Sequential make_model(int obs, int out, const std::vector<int>& layers, bool layer_norm, const std::string& act) {
     torch::nn::Sequential seq;
     int last = obs;
     for (int h : layers) {
         seq->push_back(torch::nn::Linear(last, h));
-        seq->push_back(torch::nn::LayerNorm(torch::nn::LayerNormOptions({(int64_t)h})));
+        if (layer_norm) seq->push_back(torch::nn::LayerNorm(torch::nn::LayerNormOptions({(int64_t)h})));
         last = h;
-        seq->push_back(torch::nn::LeakyReLU());
+        if (act == "relu") seq->push_back(torch::nn::ReLU());  // AddActivationFunc (Models.cpp:17-23)
+        else if (act == "sigmoid") seq->push_back(torch::nn::Sigmoid());
+        else if (act == "tanh") seq->push_back(torch::nn::Tanh());
+        else seq->push_back(torch::nn::LeakyReLU());
     }
     if (out > 0) seq->push_back(torch::nn::Linear(last, out));
     return seq;
@@ -70,8 +76,17 @@ std::vector<int64_t> seq_sizes(torch::nn::Sequential& seq) {  // GetSeqSizes (Mo
 int model_mode(bool save, int argc, char** argv) {
     if (argc < 7) return 2;
     std::vector<int> layers;
-    for (int i = 6; i < argc; i++) layers.push_back(std::atoi(argv[i]));
-    torch::nn::Sequential seq = make_model(std::atoi(argv[4]), std::atoi(argv[5]), layers);
+    bool layer_norm = true;
+    std::string act = "leaky_relu";
+    for (int i = 6; i < argc; i++) {
+        const std::string a = argv[i];
+        if (a == "--no-layer-norm") layer_norm = false;
+        else if (a == "--activation" && i + 1 < argc) act = argv[++i];
+        else if (a.rfind("--", 0) == 0 || std::atoi(argv[i]) <= 0) return 2;
+        else layers.push_back(std::atoi(argv[i]));
+    }
+    if (layers.empty() || (act != "relu" && act != "leaky_relu" && act != "sigmoid" && act != "tanh")) return 2;
+    torch::nn::Sequential seq = make_model(std::atoi(argv[4]), std::atoi(argv[5]), layers, layer_norm, act);
     torch::NoGradGuard ng;
     int64_t total = 0;
     for (auto& p : seq->parameters()) total += p.numel();

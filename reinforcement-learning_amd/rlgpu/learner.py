@@ -197,6 +197,8 @@ class LearnerConfig:
         self.train_gemm = 2               # rlgpu_ppo_config.train_gemm: 2 = f32 via scaled fp16 split (H3), 0 = bf16 x6 split, 1 = f32 MFMA
         self.infer_fp16 = False           # rlgpu_ppo_config.infer_fp16: fp16 inference copy (C5) instead of bf16
         self.frame_stack = 1              # K >= 2: stacked AdvancedObs frames (C4; no reference counterpart)
+        self.activation = "leaky_relu"    # ModelConfig::activationType of every model: leaky_relu, relu, sigmoid, tanh
+        self.layer_norm = True            # ModelConfig::addLayerNorm of every model
         self.policy_temperature = 1.0     # PPOLearnerConfig::policyTemperature: collection, old versions and Learn
         self.mask_entropy = False         # PPOLearnerConfig::maskEntropy: entropy over log(legal actions) per row
         self.collect_groups = 0           # rollout collection in arena groups on their own streams (0 = automatic)
@@ -238,7 +240,8 @@ class _CConfig(ctypes.Structure):
                 ("terminals", ctypes.c_void_p), ("n_terminals", ctypes.c_int32),
                 ("experience_mode", ctypes.c_int32), ("ts_per_itr", ctypes.c_int64),
                 ("experience_capacity", ctypes.c_int32), ("arith", ctypes.c_int32),
-                ("activation", ctypes.c_int32), ("optimizer", ctypes.c_int32), ("collect_groups", ctypes.c_int32),
+                ("activation", ctypes.c_int32), ("no_layer_norm", ctypes.c_int32), ("optimizer", ctypes.c_int32),
+                ("collect_groups", ctypes.c_int32),
                 ("policy_temperature", ctypes.c_float), ("mask_entropy", ctypes.c_int32)]
 
 
@@ -365,6 +368,8 @@ class Learner:
         c.frame_stack = cfg.frame_stack
         c.experience_mode, c.ts_per_itr, c.experience_capacity = cfg.experience_mode, cfg.ts_per_itr, cfg.experience_capacity
         c.arith = cfg.arith
+        from .ppo import activation_id
+        c.activation, c.no_layer_norm = activation_id(cfg.activation), int(not cfg.layer_norm)
         c.collect_groups = cfg.collect_groups
         c.policy_temperature, c.mask_entropy = cfg.policy_temperature, int(cfg.mask_entropy)
         c.rank, c.world = rank, world
@@ -389,7 +394,8 @@ class Learner:
         max_rows = max(min(cfg.mini_batch_size, rows_cap), min(4 * cfg.num_arenas, 65536))  # host/learner.cpp
         self.ppo = PPO.wrap(ph.value, self.device, cfg.policy_layers, cfg.critic_layers, max_rows,
                             obs_size=OBS * max(1, cfg.frame_stack), metrics_source=self._metrics, owner=self,
-                            shared_layers=cfg.shared_layers,
+                            shared_layers=cfg.shared_layers, layer_norm=bool(cfg.layer_norm), activation=cfg.activation,
+                            leaky_slope=0.0 if cfg.activation == "relu" else 0.01,
                             optim_options={"lr": (cfg.policy_lr, cfg.critic_lr, min(cfg.policy_lr, cfg.critic_lr)),
                                            "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 1e-2})
         r = _CRollout()

@@ -28,7 +28,7 @@ class _Cfg(ctypes.Structure):
     _fields_ = [("obs_size", ctypes.c_int32), ("num_actions", ctypes.c_int32),
                 ("policy_layers", ctypes.c_int32 * MAX_LAYERS), ("n_policy_layers", ctypes.c_int32),
                 ("critic_layers", ctypes.c_int32 * MAX_LAYERS), ("n_critic_layers", ctypes.c_int32),
-                ("layer_norm", ctypes.c_int32), ("leaky_slope", ctypes.c_float),
+                ("layer_norm", ctypes.c_int32), ("leaky_slope", ctypes.c_float), ("activation", ctypes.c_int32),
                 ("policy_lr", ctypes.c_float), ("critic_lr", ctypes.c_float),
                 ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("weight_decay", ctypes.c_float), ("clip_range", ctypes.c_float),
@@ -39,6 +39,15 @@ class _Cfg(ctypes.Structure):
                 ("policy_temperature", ctypes.c_float), ("mask_entropy", ctypes.c_int32)]
 
 GEMM_F32X6, GEMM_F32, GEMM_F16X3 = 0, 1, 2  # rlgpu_ppo_config.train_gemm (include/rlgpu_ppo.h)
+# rlgpu_ppo_config.activation / rlgpu_learner_config.activation (RLGPU_ACT_*, ModelActivationType)
+ACTIVATIONS = {"leaky_relu": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
+
+
+def activation_id(name):
+    """RLGPU_ACT_* of an activation name."""
+    if name not in ACTIVATIONS:
+        raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, not {name!r}")
+    return ACTIVATIONS[name]
 
 
 _bound = False
@@ -95,8 +104,9 @@ class PPO:
                  layer_norm=True, policy_lr=2.5e-4, critic_lr=2.5e-4, clip_range=0.2, entropy_scale=0.035,
                  max_grad_norm=0.5, max_rows=50_000, seed=42, init=True, device="cuda:0",
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, leaky_slope=0.01, train_gemm=GEMM_F16X3,
-                 infer_fp16=False, shared_layers=(), policy_temperature=1.0, mask_entropy=False):
-        """policy_temperature (PPOLearnerConfig::policyTemperature): sampling and the minibatch loss divide the
+                 infer_fp16=False, shared_layers=(), policy_temperature=1.0, mask_entropy=False, activation="leaky_relu"):
+        """activation (ModelConfig::activationType of every model): "leaky_relu" (with leaky_slope), "relu", "sigmoid"
+        or "tanh".  policy_temperature (PPOLearnerConfig::policyTemperature): sampling and the minibatch loss divide the
         logits by it (0 = the C default, 1).  mask_entropy (maskEntropy): each row's entropy over log(its legal
         actions) instead of log(num_actions)."""
         import torch
@@ -115,8 +125,8 @@ class PPO:
         c.n_shared_layers = len(shared_layers)
         for i, v in enumerate(shared_layers):
             c.shared_layers[i] = v
-        c.layer_norm, c.leaky_slope = int(layer_norm), leaky_slope
-        self.leaky_slope = leaky_slope
+        c.layer_norm, c.leaky_slope, c.activation = int(layer_norm), leaky_slope, activation_id(activation)
+        self.leaky_slope, self.activation = leaky_slope, activation
         c.policy_lr, c.critic_lr = policy_lr, critic_lr
         c.beta1, c.beta2, c.eps, c.weight_decay = betas[0], betas[1], eps, weight_decay
         c.clip_range, c.entropy_scale, c.max_grad_norm = clip_range, entropy_scale, max_grad_norm
@@ -147,7 +157,8 @@ class PPO:
 
     @classmethod
     def wrap(cls, handle, device, policy_layers, critic_layers, max_rows, obs_size=167, num_actions=90,
-             layer_norm=True, leaky_slope=0.01, metrics_source=None, owner=None, shared_layers=(), optim_options=None):
+             layer_norm=True, leaky_slope=0.01, metrics_source=None, owner=None, shared_layers=(), optim_options=None,
+             activation="leaky_relu"):
         """A PPO view of a handle owned elsewhere (the C++ Learner's PPOLearner): not destroyed
         by this object.  metrics_source(reset) -> (sums, count) replaces the own metric buffer."""
         import torch
@@ -159,6 +170,8 @@ class PPO:
         self.policy_layers, self.critic_layers, self.layer_norm = tuple(policy_layers), tuple(critic_layers), layer_norm
         self.shared_layers = tuple(shared_layers)
         self.leaky_slope, self.max_rows = leaky_slope, max_rows
+        activation_id(activation)
+        self.activation = activation
         self.optim_options = optim_options
         p, g, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
         _lib.check(L.rlgpu_ppo_buffers(self._h, ctypes.byref(p), ctypes.byref(g), ctypes.byref(n)), "rlgpu_ppo_buffers")
@@ -231,7 +244,7 @@ class PPO:
         import torch
         layers = (self.policy_layers, self.critic_layers, self.shared_layers)[model]
         out = None if model == 2 else self.model_out(model)
-        seq = make_sequential(self.model_in(model), out, layers, self.layer_norm, self.leaky_slope)
+        seq = make_sequential(self.model_in(model), out, layers, self.layer_norm, self.leaky_slope, self.activation)
         flat = self.model_slice(model).detach().cpu()
         o = 0
         with torch.no_grad():
@@ -359,17 +372,18 @@ class PPO:
         return [p.numel() for p in self.torch_module(model).parameters()]
 
 
-def make_sequential(obs_size, out, layers, layer_norm=True, leaky_slope=0.01):
-    """GGL::Model's module list (Models.cpp:7-33): per hidden layer Linear [, LayerNorm],
-    LeakyReLU; then the output Linear (none when out is None: the shared head, addOutputLayer
-    false).  CPU, torch default init."""
+def make_sequential(obs_size, out, layers, layer_norm=True, leaky_slope=0.01, activation="leaky_relu"):
+    """GGL::Model's module list (Models.cpp:7-33): per hidden layer Linear [, LayerNorm], the
+    activation (AddActivationFunc: ReLU, LeakyReLU(leaky_slope), Sigmoid or Tanh); then the output
+    Linear (none when out is None: the shared head, addOutputLayer false).  CPU, torch default init."""
     import torch
+    act = (lambda: torch.nn.LeakyReLU(leaky_slope), torch.nn.ReLU, torch.nn.Sigmoid, torch.nn.Tanh)[activation_id(activation)]
     mods, prev = [], obs_size
     for hdim in layers:
         mods.append(torch.nn.Linear(prev, hdim))
         if layer_norm:
             mods.append(torch.nn.LayerNorm(hdim))
-        mods.append(torch.nn.LeakyReLU(leaky_slope))
+        mods.append(act())
         prev = hdim
     if out is not None:
         mods.append(torch.nn.Linear(prev, out))

@@ -2,6 +2,7 @@
 rlgpu_ppo_infer_critic over a C2 rollout (129 x 16,384 rows), bf16 MFMA path.
 
     python tools/infer_bench.py [infer_fp16]     0 bf16 (default), 1 fp16, 2 the fp32 training forward
+                                [activation]     leaky_relu (default), relu, sigmoid, tanh
 """
 import os
 import sys
@@ -14,7 +15,8 @@ from rlgpu.ppo import PPO  # noqa: E402
 
 dev = torch.device("cuda:0")
 ppo = PPO(167, 90, (512, 512), (512, 512), max_rows=65536, seed=1, device=dev,
-          infer_fp16=int(sys.argv[1]) if len(sys.argv) > 1 else 0)
+          infer_fp16=int(sys.argv[1]) if len(sys.argv) > 1 else 0,
+          activation=sys.argv[2] if len(sys.argv) > 2 else "leaky_relu")
 P = 16384
 obs = torch.randn(P, 167, device=dev)
 masks = torch.ones(P, 90, dtype=torch.uint8, device=dev)

@@ -5,6 +5,7 @@ without the env.  Prints ms per minibatch (HIP events); run under rocprofv3 --ke
 for per-kernel durations.
 
 usage: python tools/learn_bench.py [minibatches=24] [train_gemm=h3|x6|f32] [width=512] [depth=2]
+       [activation=leaky_relu|relu|sigmoid|tanh]
 (width 2048, depth 4 = the C5 leg's model)
 """
 import os
@@ -32,7 +33,8 @@ tgt = torch.randn((N,), device=dev, generator=g)
 width = int(sys.argv[3]) if len(sys.argv) > 3 else 512
 depth = int(sys.argv[4]) if len(sys.argv) > 4 else 2
 layers = (width,) * depth
-p = PPO(max_rows=MB, seed=123, train_gemm=mode, policy_layers=layers, critic_layers=layers)
+activation = sys.argv[5] if len(sys.argv) > 5 else "leaky_relu"
+p = PPO(max_rows=MB, seed=123, train_gemm=mode, policy_layers=layers, critic_layers=layers, activation=activation)
 p.adv_normalizer(adv)
 idx = permutation(N, 7, 0)
 
@@ -54,7 +56,7 @@ run(nmb)
 e1.record()
 torch.cuda.synchronize()
 print(f"learn_bench {layers}: {e0.elapsed_time(e1) / nmb:.3f} ms per 50k minibatch (+ optimizer step every {N // MB}), "
-      f"mode {sys.argv[2] if len(sys.argv) > 2 else 'h3'}, {nmb} minibatches", flush=True)
+      f"mode {sys.argv[2] if len(sys.argv) > 2 else 'h3'}, {activation}, {nmb} minibatches", flush=True)
 print("metrics finite:", bool(np.isfinite(p.metrics.cpu().numpy()).all()))
 kernel_timing(True)
 run(8)
