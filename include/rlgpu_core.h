@@ -13,6 +13,8 @@
 #ifndef RLGPU_CORE_H
 #define RLGPU_CORE_H
 
+#include <stdint.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -34,6 +36,23 @@ int rlgpu_abi_version(void);
 
 /* Number of visible HIP devices (0 if no GPU); never fails. */
 int rlgpu_device_count(void);
+
+/* Compute-unit partitions (host/cu_partition.cpp): `groups` CU masks of `words` = 8 uint32 each (bit k of a mask
+ * is bit k % 32 of word k / 32), pairwise disjoint, covering every CU, each with the same number of CUs in every
+ * XCD under either plausible bit-to-CU mapping.  Host only.  RLGPU_ERR_UNSUPPORTED for a cu_count other than 256
+ * (8 XCDs of 32 CUs, MI355X) or a group count outside 2, 4, 8, 16: no balance can be shown for those. */
+int rlgpu_cu_partition(int32_t cu_count, int32_t groups, uint32_t* masks, int32_t words);
+
+/* Diagnostics: a stream of the current device restricted to partition `group` of `groups` (what the Learner's
+ * collection groups run on), the mask the runtime reports for a stream (hipExtStreamGetCUMask), and the
+ * stream's end. */
+int rlgpu_debug_cu_stream_create(int32_t groups, int32_t group, void** stream);
+int rlgpu_debug_cu_stream_mask(void* stream, uint32_t* mask, int32_t words);
+int rlgpu_debug_cu_stream_destroy(void* stream);
+/* Diagnostics: one launch of n_workgroups single-wave workgroups on `stream`, each holding all 512 registers per
+ * lane of its SIMD (as an env workgroup does) for hold_us microseconds (0 .. 2000), then writing
+ * d_out[4 w .. 4 w + 3] = its XCD id, shader-engine id, CU id within the engine, and the raw HW_ID register. */
+int rlgpu_debug_cu_probe(void* stream, uint32_t* d_out, int32_t n_workgroups, int32_t hold_us);
 
 #ifdef __cplusplus
 }

@@ -107,10 +107,12 @@ typedef struct {
                                       RLGPU_OPT_ADAMW (0, libtorch AdamW: weight decay 1e-2) or RLGPU_OPT_ADAM
                                       (libtorch Adam: no weight decay) */
     int32_t collect_groups;        /* the rollout collection's arena groups, each stepped and inferred on its own
-                                      stream so one group's launch tail overlaps the others' work (same results
-                                      bit for bit; measured slower so far); 0 / 1 = one launch per step; G > 1
+                                      stream and its own partition of the device's CUs, so one group's launch tail
+                                      overlaps the others' work (same results bit for bit); 0 = automatic (2 groups
+                                      from 4096 arenas on, else one); 1 = one launch per step; G = 2, 4, 8 or 16
                                       when the policy runs on the fused inference kernel, without host plugins or
-                                      frame stacking, and 4 G | num_arenas */
+                                      frame stacking, 4 G | num_arenas and the device is a 256-CU MI355X; one
+                                      launch per step otherwise */
     float policy_temperature;      /* rlgpu_ppo_config.policy_temperature (PPOLearnerConfig::policyTemperature):
                                       collection, old versions and Learn alike; 0 = 1 */
     int32_t mask_entropy;          /* rlgpu_ppo_config.mask_entropy (PPOLearnerConfig::maskEntropy) */

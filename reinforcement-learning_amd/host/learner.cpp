@@ -15,6 +15,7 @@
 
 #include "../csrc/common.hpp"
 #include "../csrc/learner_kernels.hpp"
+#include "cu_partition.hpp"
 
 namespace {
 constexpr int OBS = RLGPU_OBS, ACT = RLGPU_ACTIONS;
@@ -387,17 +388,66 @@ Learner::~Learner() {
 
 // Arena groups for the rollout collection: a launch lasts as long as its slowest workgroup, so with the
 // arenas split into groups stepped (and inferred) on their own streams, one group's launch tail could overlap
-// the other groups' work (tools/env_streams.py, env steps alone: 0.84 -> 0.75 ms per step of 4,096 arenas with 4
-// groups).  In the Learner, with the inference between the steps, it measured slower (collection 139 -> 152 ms
-// with 2 groups, 260 ms with 4: profiles/r05y_collect_groups.txt), so the default stays one launch per step.
+// the other groups' work.  On plain streams that measured slower in the Learner (collection 139 -> 152 ms with 2
+// groups: profiles/r05y_collect_groups.txt): a group's 8-wave inference workgroups had to wait for whole CUs among
+// the other groups' one-wave-per-SIMD env workgroups.  So every group's stream gets a disjoint CU partition
+// (EnsureGroupStreams), and each chain of inference -> step -> inference has its CUs to itself.
+// Measured (profiles/r14a_collect_partition_*.txt, 4,096 arenas, T = 128): the env launch shortens with the group
+// count (0.956 ms at one group, 0.901 / 0.861 / 0.845 at 2 / 4 / 8, HIP events), every group runs on a hardware
+// queue of its own, and a group's inference launch takes what the whole device's does (48 against 52 us).  The
+// collection takes 133.1 -> 126.8 ms with 2 groups in three alternating bench pairs.  With 4 / 8 groups it takes
+// 124.3 / 120.0 ms without the bench's per-launch timing events (2 groups: 123.3, one: 129.0) but 131.5 / 130.5 ms
+// with them.  What bounds the gain: the phase lasts as long as its slowest group's chain, and the groups' chains
+// differ by a few per cent (busy 0.89 .. 0.96 of the phase with 4 groups).  Supposed, not measured: why the timing
+// events cost 4 and 8 groups so much more than 2.  Hence 2 groups, which gain either way, when the choice is
+// automatic.
 // Each arena's step and each player's draw are the same as in one launch (the arenas' Philox streams and the
 // sampler's rows are global), so the rollout is bit-identical.  Only for the fused inference kernel (no
 // per-handle row buffers), without a step hook or stacked frames, and for whole workgroups of arenas.
+constexpr int kAutoCollectGroups = 2;     // collect_groups = 0: the count that measured best (above)
+constexpr int kAutoCollectArenas = 4096;  // ... from one env workgroup per SIMD of the device on, the regime measured;
+                                          // smaller launches leave SIMDs free anyway and were not measured
+
 int Learner::CollectGroups() const {
-    const int want = cfg_.collect_groups > 0 ? cfg_.collect_groups : 1;  // automatic = one group (see below)
+    const int want = cfg_.collect_groups > 0                   ? cfg_.collect_groups
+                     : cfg_.num_arenas >= kAutoCollectArenas ? kAutoCollectGroups
+                                                             : 1;
     if (want <= 1 || hook_ || K_ > 1 || trajMode() || !rlgpu_ppo_fused_infer(ppo_->handle(), 0)) return 1;
     if (cfg_.num_arenas % (4 * want) != 0) return 1;
     return want;
+}
+
+// The G group streams, each on its own CU partition (host/cu_partition.cpp), and their events.  A masked stream
+// cannot be made non-blocking (hipExtStreamCreateWithCUMask takes no flags), so unlike the learner's other side
+// streams these synchronise with the legacy null stream; during the collection nothing is enqueued on s_ between
+// the start and the join events, which remain the only coupling that orders any work.  False when the device has
+// no balanced partition into G or a stream cannot be created: the collection then runs as one group.
+bool Learner::EnsureGroupStreams(int G) {
+    if ((int)gs_.size() == G) return true;
+    if (gsRefused_ == G) return false;
+    for (auto s : gs_) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    for (auto e : gsEnd_) (void)hipEventDestroy(e);
+    gs_.clear();
+    gsEnd_.clear();
+    std::vector<hipStream_t> ss;
+    for (int g = 0; g < G; g++) {
+        hipStream_t s = nullptr;
+        if (rlgpu::cu_partition_stream(G, g, &s) != hipSuccess) {
+            (void)hipGetLastError();
+            for (auto x : ss) (void)hipStreamDestroy(x);
+            gsRefused_ = G;
+            return false;
+        }
+        ss.push_back(s);
+    }
+    gs_ = ss;
+    gsEnd_.assign(G, nullptr);
+    for (int g = 0; g < G; g++) hipCheck(hipEventCreateWithFlags(&gsEnd_[g], hipEventDisableTiming), "group event");
+    if (!gsStart_) hipCheck(hipEventCreateWithFlags(&gsStart_, hipEventDisableTiming), "group event");
+    return true;
 }
 
 void Learner::CollectGrouped(int G) {
@@ -405,17 +455,6 @@ void Learner::CollectGrouped(int G) {
     const rlgpu_rollout_view& v = exp_.v;
     const uint8_t* old = OldRows();
     const int Na = cfg_.num_arenas / G, Pg = 4 * Na;
-    if ((int)gs_.size() != G) {
-        for (auto s : gs_) (void)hipStreamDestroy(s);
-        for (auto e : gsEnd_) (void)hipEventDestroy(e);
-        gs_.assign(G, nullptr);
-        gsEnd_.assign(G, nullptr);
-        for (int g = 0; g < G; g++) {
-            hipCheck(hipStreamCreateWithFlags(&gs_[g], hipStreamNonBlocking), "group stream");
-            hipCheck(hipEventCreateWithFlags(&gsEnd_[g], hipEventDisableTiming), "group event");
-        }
-        if (!gsStart_) hipCheck(hipEventCreateWithFlags(&gsStart_, hipEventDisableTiming), "group event");
-    }
     if (envTiming_) EnsureEvents((size_t)2 * T * G);
     hipCheck(hipEventRecord(gsStart_, s_), "group start");
     for (int g = 0; g < G; g++) hipCheck(hipStreamWaitEvent(gs_[g], gsStart_, 0), "group wait");
@@ -448,7 +487,7 @@ void Learner::Collect() {
         CollectTrajectories();
         return;
     }
-    if (const int G = CollectGroups(); G > 1) {
+    if (const int G = CollectGroups(); G > 1 && EnsureGroupStreams(G)) {
         collectGroupsUsed_ = G;
         CollectGrouped(G);
         return;

@@ -219,12 +219,14 @@ private:
     int K_ = 1;                 // frames stacked (config C4)
     float* hist_ = nullptr;     // [K-1][P][OBS] frame history
     std::vector<hipEvent_t> ev_;
-    // the rollout collection in arena groups (rlgpu_learner_config.collect_groups): one stream per group, joined
-    // to s_ by events at the phase's start and end
+    // the rollout collection in arena groups (rlgpu_learner_config.collect_groups): one stream per group, each on
+    // its own CU partition (host/cu_partition.hpp), joined to s_ by events at the phase's start and end
     std::vector<hipStream_t> gs_;
     std::vector<hipEvent_t> gsEnd_;
     hipEvent_t gsStart_ = nullptr;
+    int gsRefused_ = 0;  // the group count whose partition streams could not be made (not tried again)
     int CollectGroups() const;
+    bool EnsureGroupStreams(int G);
     int collectGroupsUsed_ = 1;
     void CollectGrouped(int G);
     // device scratch

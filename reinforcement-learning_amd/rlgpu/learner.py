@@ -201,7 +201,8 @@ class LearnerConfig:
         self.layer_norm = True            # ModelConfig::addLayerNorm of every model
         self.policy_temperature = 1.0     # PPOLearnerConfig::policyTemperature: collection, old versions and Learn
         self.mask_entropy = False         # PPOLearnerConfig::maskEntropy: entropy over log(legal actions) per row
-        self.collect_groups = 0           # rollout collection in arena groups on their own streams (0 = automatic)
+        self.collect_groups = 0           # rollout collection in arena groups on their own streams and CU partitions
+                                          # (0 = automatic: 2 groups from 4096 arenas on; 1 = one launch per step)
         # checkpoints (LearnerConfig.h:31-38): None = no save / load
         self.checkpoint_folder = None
         self.ts_per_save = 10_000_000     # 0 = every iteration (Learner.cpp:44-45)
