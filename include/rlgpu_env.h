@@ -299,6 +299,30 @@ int rlgpu_envset_step(rlgpu_envset* env, const int32_t* d_actions, int32_t reset
  * per-phase profile (rlgpu_envset_set_profile). */
 int rlgpu_envset_step_range(rlgpu_envset* env, int32_t first, int32_t count, const int32_t* d_actions,
                             int32_t reset_terminated, const rlgpu_step_outputs* out, void* stream);
+/* The collection loop: T = `steps` fused steps (with reset of terminated arenas) and the policy's sampling forward
+ * before each, in ONE launch.  A 64-thread workgroup owns its 4 arenas and their 16 players for all T steps: per
+ * step it runs the forward of its own rows of rollout row t on its one wave (the fused inference kernel's
+ * arithmetic: rlgpu_ppo_infer_actions_wave), writes actions[t] / logp[t], steps its arenas and appends row t + 1,
+ * rewards[t], terminals[t] and the truncation rows -- no workgroup waits for another.  Every array, the arena
+ * records and the StepCallback sums are what T calls of rlgpu_ppo_infer_actions_rows (row0 0, rng_step + t) and
+ * rlgpu_envset_step leave, bit for bit.  Row 0 of obs / masks is the caller's (the previous rollout's row T).
+ * Eligible (rlgpu_envset_collect_loop_ok, else RLGPU_ERR_UNSUPPORTED): the msvc_x64 arithmetic (the one the loop
+ * kernel is built for), action_delay > 0, no per-phase profile, and a policy that
+ * rlgpu_ppo_wave_infer accepts with RLGPU_OBS inputs and RLGPU_ACTIONS outputs.  The env timing figure of such a
+ * launch includes the in-workgroup inference. */
+typedef struct {
+    float* obs;          /* [steps + 1][players][RLGPU_OBS] */
+    uint8_t* masks;      /* [steps + 1][players][RLGPU_ACTIONS] */
+    int32_t* actions;    /* [steps][players] */
+    float* logp;         /* [steps][players] */
+    float* rewards;      /* [steps][players] */
+    int8_t* terminals;   /* [steps][players] trajectory codes */
+    float* trunc_obs;    /* [steps][players][RLGPU_OBS] (rows of code 2), may be NULL */
+} rlgpu_collect_rollout;
+struct rlgpu_ppo;
+int rlgpu_envset_collect_loop_ok(rlgpu_envset* env, struct rlgpu_ppo* policy);
+int rlgpu_envset_collect_loop(rlgpu_envset* env, struct rlgpu_ppo* policy, int32_t steps, const rlgpu_collect_rollout* rollout,
+                              int32_t deterministic, uint64_t rng_step, void* stream);
 int rlgpu_envset_sync(rlgpu_envset* env, void* stream);
 /* Output-only rows (default off): a fused step given `out` rows for obs / masks / truncation obs writes those
  * rows only there, not also into the set's own buffers (rlgpu_envset_buffers obs / masks / trunc_obs), which

@@ -112,7 +112,13 @@ typedef struct {
                                       from 4096 arenas on, else one); 1 = one launch per step; G = 2, 4, 8 or 16
                                       when the policy runs on the fused inference kernel, without host plugins or
                                       frame stacking, 4 G | num_arenas and the device is a 256-CU MI355X; one
-                                      launch per step otherwise */
+                                      launch per step otherwise; -1 = the collection loop: the whole rollout in
+                                      one launch (rlgpu_envset_collect_loop, same results bit for bit) in every
+                                      iteration where it is eligible -- no host plugins, frame stacking, trajectory
+                                      mode or old version playing, and the entry's own conditions -- and the
+                                      automatic choice's path otherwise.  The report then has env_launch_arenas =
+                                      num_arenas and env_kernel_ms (min / median / max alike) = the launch's time /
+                                      rollout_len, the in-workgroup inference included */
     float policy_temperature;      /* rlgpu_ppo_config.policy_temperature (PPOLearnerConfig::policyTemperature):
                                       collection, old versions and Learn alike; 0 = 1 */
     int32_t mask_entropy;          /* rlgpu_ppo_config.mask_entropy (PPOLearnerConfig::maskEntropy) */

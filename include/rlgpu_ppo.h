@@ -183,6 +183,17 @@ int rlgpu_ppo_infer_actions_rows(rlgpu_ppo* h, const float* d_obs, const uint8_t
                                  int32_t* d_actions, float* d_logp, void* stream);
 /* 1 when model `model` (0 policy, 1 critic) runs on the fused inference kernel, else 0. */
 int rlgpu_ppo_fused_infer(rlgpu_ppo* h, int32_t model);
+/* The one-wave form of the fused inference kernel (16 rows per 64-thread workgroup; the forward that the collection
+ * loop runs inside the env workgroups, rlgpu_envset_collect_loop): the same arithmetic per row, so the same bits.
+ * rlgpu_ppo_wave_infer: 1 when model `model` is eligible -- rlgpu_ppo_fused_infer's conditions (16-bit inference,
+ * widths <= 512, outputs <= 128) and LeakyReLU / ReLU.  infer_actions_wave takes rlgpu_ppo_infer_actions_rows'
+ * arguments and writes what it writes; infer_values_wave writes the f32 outputs [n][outputs] of model 0 / 1 (the
+ * 16-bit-rounded output Linear, as rlgpu_ppo_forward's precision 1).  Not eligible: RLGPU_ERR_UNSUPPORTED. */
+int rlgpu_ppo_wave_infer(rlgpu_ppo* h, int32_t model);
+int rlgpu_ppo_infer_actions_wave(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int32_t n, int64_t row0,
+                                 int32_t deterministic, uint64_t rng_step, const uint8_t* d_old_rows,
+                                 int32_t* d_actions, float* d_logp, void* stream);
+int rlgpu_ppo_infer_values_wave(rlgpu_ppo* h, int32_t model, const float* d_obs, int32_t n, float* d_out, void* stream);
 /* InferCriticBatched: bf16 critic forward over n rows (any n; off the fused kernel in chunks of max_rows). */
 int rlgpu_ppo_infer_critic(rlgpu_ppo* h, const float* d_obs, int64_t n, float* d_values, void* stream);
 

@@ -58,5 +58,18 @@ inline unsigned ceil_div(int64_t a, int64_t b) { return (unsigned)((a + b - 1) /
 // infer_act.hip: one launch of the fused inference kernel's SIGMOID / TANH instance (infer::mlp_infer<f16, act>)
 // with the infer::InferArgs at args (bytes = its size, checked)
 void launch_mlp_infer_act(int act, bool f16, unsigned blocks, hipStream_t s, const void* args, size_t bytes);
+// infer_wave.hip: one launch of the one-wave form (infer::mlp_infer_wave<f16>, LeakyReLU / ReLU), 16 rows per workgroup
+void launch_mlp_infer_wave(bool f16, unsigned blocks, hipStream_t s, const void* args, size_t bytes);
 
+}  // namespace rlgpu
+
+// ppo.hip, for env.hip's collection loop (rlgpu_envset_collect_loop): whether the policy runs on the one-wave
+// inference kernel with these obs / action widths, and the infer::InferArgs bytes (blob, at most cap) of its sampling
+// forward over rollout row 0 -- n rows of d_obs / d_masks, global rows from the handle's sample_row_offset, the draw
+// of rng_step -- with *f16 its 16-bit format.
+struct rlgpu_ppo;
+namespace rlgpu {
+bool ppo_wave_policy(rlgpu_ppo* h, int obs_size, int num_actions);
+void ppo_wave_args(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int64_t n, int deterministic, uint64_t rng_step,
+                   int32_t* d_actions, float* d_logp, void* blob, size_t cap, bool* f16);
 }  // namespace rlgpu

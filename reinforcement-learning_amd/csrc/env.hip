@@ -13,6 +13,7 @@
 #include "env_step.hpp"
 #include "mesh.hpp"
 #include "../../include/rlgpu_gamestate.h"
+#include "../../include/rlgpu_ppo.h"
 
 namespace rl {
 // the specialised env kernels (env_k0.hip .. env_k2.hip, one per RLGPU_ARITH_* mode)
@@ -22,6 +23,9 @@ void env_k2_upload(const EnvConst& k, const RsqrtLut* lut);
 void env_k0_launch(const StepArgs& g, int blocks, hipStream_t s);
 void env_k1_launch(const StepArgs& g, int blocks, hipStream_t s);
 void env_k2_launch(const StepArgs& g, int blocks, hipStream_t s);
+// the collection loop kernel (env_step.hpp): built for RLGPU_ARITH_MSVC_X64 only
+void env_collect_k0_upload(const EnvConst& k, const RsqrtLut* lut);
+void env_collect_k0_launch(const CollectArgs& c, bool f16, int blocks, hipStream_t s);
 
 // ------------------------------------------------------------------ host: constants
 static m3 host_euler_ypr(float yaw, float pitch, float roll) {  // btMatrix3x3::setEulerYPR
@@ -358,7 +362,8 @@ static_assert(RLGPU_ARITH_MSVC_X64 == 0 && RLGPU_ARITH_GCC_X64 == 1 && RLGPU_ARI
 // The kernels' __constant__ symbols live once per device.  device_init(arith), called by whatever is about to
 // launch a kernel of this library's env family for that arithmetic (a set's create, a query), uploads under one
 // lock (sets may be created from several threads, on several devices of one process):
-//   - EnvConst, the first time on a device: to this file's copy (the query kernels') and to every kEnvKernel;
+//   - EnvConst, the first time on a device: to this file's copy (the query kernels'), to every kEnvKernel and to the
+//     collection loop kernel's unit;
 //   - the x86 modes' rsqrtss table, the first time an SSE arithmetic asks on a device: this host's table
 //     (host/x86_arith.cpp, the same for every set) into device memory, its pointer into kRsqrtLut of this file
 //     and of the kernels that read it (the SSE entries; their upload call carries EnvConst with it).
@@ -391,6 +396,7 @@ void device_init(int arith) {
     for (int a = 0; a < RLGPU_NUM_ARITH; a++) {
         const bool lut = rsqrt && rl::sse_api(a);
         if (consts || lut) kEnvKernel[a].upload(k, lut ? &L : nullptr);
+        if ((consts || lut) && a == RLGPU_ARITH_MSVC_X64) rl::env_collect_k0_upload(k, lut ? &L : nullptr);
     }
     done.consts = true;
     done.rsqrt = done.rsqrt || rsqrt;
@@ -413,7 +419,7 @@ struct Range {
 Range whole(const rlgpu_envset* e) { return Range{0, e->cfg.num_arenas}; }
 
 // The one place StepArgs is filled from the set: `g` says what the launch does (step_args, or a reset mode),
-// launch() adds where.  Every per-arena / per-player pointer is moved to the range's first arena (offsets that
+// placed() adds where, launch() launches it.  Every per-arena / per-player pointer is moved to the range's first arena (offsets that
 // are zero for the whole set), and so are the penetration-solver scratch (one GjkScratch per lane of the range's
 // workgroups) and arena_offset, so each arena keeps its own Philox stream and a range computes what the
 // whole-set launch computes for its arenas.  rlgpu_envset_step_range refuses a set with a profile buffer, so
@@ -424,7 +430,7 @@ Range whole(const rlgpu_envset* e) { return Range{0, e->cfg.num_arenas}; }
 // metric_calls and stores the flag -- and every range of that step, that one included, reads the stored flag.
 // A whole-set launch starts at arena 0, so this is what both the whole-set and the range path did when each
 // kept its own copy of the rule; a step's ranges must begin with the one that holds arena 0.
-void launch(rlgpu_envset* e, rl::StepArgs g, Range r, hipStream_t s) {
+rl::StepArgs placed(rlgpu_envset* e, rl::StepArgs g, Range r) {
     const size_t a0 = (size_t)r.first, p0 = a0 * 4, nr = (size_t)e->plug.nr;
     g.arenas = e->d_arenas + a0 * rl::kRec;
     g.n = r.count;
@@ -451,7 +457,10 @@ void launch(rlgpu_envset* e, rl::StepArgs g, Range r, hipStream_t s) {
         g.metrics = e->d_metrics + a0 * RLGPU_STEP_METRIC_SLOTS;
         g.metrics_players = e->metric_players;
     }
-    kEnvKernel[e->cfg.arith].launch(g, rlgpu::ceil_div(r.count, rl::kArenas), s);
+    return g;
+}
+void launch(rlgpu_envset* e, const rl::StepArgs& g, Range r, hipStream_t s) {
+    kEnvKernel[e->cfg.arith].launch(placed(e, g, r), rlgpu::ceil_div(r.count, rl::kArenas), s);
     RLGPU_CHECK_HIP(hipGetLastError());
 }
 
@@ -782,6 +791,41 @@ extern "C" int rlgpu_envset_step_range(rlgpu_envset* e, int32_t first, int32_t c
                       "rlgpu_envset_step_range: the range must lie in the set and start at a multiple of 4");
         RLGPU_REQUIRE(!e->d_prof, "rlgpu_envset_step_range: not with the per-phase profile");
         launch(e, g, Range{first, count}, rlgpu::as_stream(stream));
+    });
+}
+
+extern "C" int rlgpu_envset_collect_loop_ok(rlgpu_envset* e, rlgpu_ppo* policy) {
+    return e && policy && e->cfg.arith == RLGPU_ARITH_MSVC_X64 && e->cfg.action_delay > 0 && !e->d_prof &&
+           rlgpu::ppo_wave_policy(policy, RLGPU_OBS, RLGPU_ACTIONS);
+}
+
+extern "C" int rlgpu_envset_collect_loop(rlgpu_envset* e, rlgpu_ppo* policy, int32_t steps, const rlgpu_collect_rollout* ro,
+                                         int32_t deterministic, uint64_t rng_step, void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(e && policy && ro && steps > 0, "rlgpu_envset_collect_loop: bad argument");
+        RLGPU_REQUIRE(ro->obs && ro->masks && ro->actions && ro->logp && ro->rewards && ro->terminals,
+                      "rlgpu_envset_collect_loop: null rollout array");
+        if (!rlgpu_envset_collect_loop_ok(e, policy))
+            throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "rlgpu_envset_collect_loop: not eligible (msvc_x64 arithmetic, no "
+                                                      "profile, a policy on the one-wave inference kernel)");
+        const int64_t P = e->num_players;
+        // step 0's fused step with its append (rollout row 1 / row 0); the kernel moves the rows on per step
+        const rlgpu_step_outputs out{ro->obs + P * RLGPU_OBS, ro->masks + P * RLGPU_ACTIONS, ro->rewards, ro->terminals,
+                                     ro->trunc_obs};
+        rl::CollectArgs c;
+        std::memset(&c, 0, sizeof c);
+        c.metric_calls = (int)(e->metric_calls % 4);  // before placed() counts step 0's call
+        c.g = placed(e, fused_step_args(e, ro->actions, 1, &out), whole(e));
+        if (c.g.metrics) {  // the other steps' StepCallback calls; the stored flag is the last step's
+            e->metric_calls += (uint64_t)(steps - 1);
+            e->metric_players = e->metric_calls % 4 == 0;
+        }
+        c.T = steps;
+        c.P = P;
+        bool f16 = false;
+        rlgpu::ppo_wave_args(policy, ro->obs, ro->masks, P, deterministic, rng_step, ro->actions, ro->logp, c.inf.b,
+                             sizeof c.inf.b, &f16);
+        rl::env_collect_k0_launch(c, f16, rlgpu::ceil_div(e->cfg.num_arenas, rl::kArenas), rlgpu::as_stream(stream));
     });
 }
 

@@ -147,9 +147,12 @@ DEV void linear_tiles(const uint16_t (*Xs)[IPITCH], const uint16_t* F, int KS, c
 // per-row arithmetic of mlp::ln_act_fwd_bf16<MAXH> (same sums in the same order, the centred value
 // computed once and reused, LEAKY in act_fwd's maxform when 0 <= slope <= 1 -- equal to the
 // select for every h); FULL: H == 64 MAXH, no column masks.
-template <int MAXH, bool FULL, bool F16, int ACT>
+// The rows are w + RS g, g < NRW: the 8-wave kernel's IRW rows IW apart by default; the one-wave form below takes 8
+// consecutive rows per call (NRW = 8, RS = 1).
+template <int MAXH, bool FULL, bool F16, int ACT, int NRW = IRW, int RS = IW>
 DEV void ln_act_rows(uint16_t (*Xs)[IPITCH], const uint16_t* gamma, const uint16_t* beta, int H, float slope, int use_ln,
                      int w, int lane) {
+    constexpr int IRW = NRW, IW = RS;  // shadow the 8-wave kernel's constants
     const bool vec = (H % 8 == 0) && (MAXH % 8 == 0);
     const bool maxform = slope >= 0.f && slope <= 1.f;
     auto in = [&](int q) { return FULL || mlp::hcol<MAXH>(lane, q) < H; };
@@ -421,6 +424,174 @@ __global__ void __launch_bounds__(IT, 1) mlp_infer(InferArgs a) {
         ppo::sample_rows_looped<IRW, F16>(rowfn, N, a.temp, a.det, a.seed, a.step, a.row0, lane, a.act, a.logp, mark);
     }
     INFER_MARK(15);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The one-wave form: the same forward for WR = 16 rows on one wavefront, for a caller that has a single wave and
+// ~35 KB of LDS (the env workgroup of the collection loop, env_step.hpp; mlp_infer_wave below runs it alone).
+// Per row it is mlp_infer's arithmetic, operation for operation: the rows are the lower half of one 32-row MFMA
+// tile whose upper 16 rows are zeros (a row's accumulators do not depend on the tile's other rows), the K steps,
+// the fragment-major weights, the 16-bit rounding of (acc + bias), ln_act_rows and sample_rows_looped are the same.
+// The wave owns every output column tile, so a layer cannot overwrite its input in place: two buffers, swapped per
+// layer.  The column tiles are taken WNC = 4 per K sweep (64 accumulator + 128 prefetch registers).  The bias and
+// LayerNorm vectors are read from the 16-bit parameter copy where they are used (no LDS copy: 27 KB in mlp_infer).
+constexpr int WR = 16;   // rows per wave
+constexpr int WNC = 4;   // column tiles per K sweep
+struct WaveLDS {
+    uint16_t X[2][WR][IPITCH];       // layer input / output, swapped per layer
+    uint8_t M[WR * ppo::kMaxA];      // mode 1: the rows' action masks
+    uint8_t Sel[WR];                 // mode 1: row is written
+};
+
+// acc[c] = Xs[rows 0..15 | 16 zero rows] . W[column tile min(jt0 + c, JT - 1)]^T; tiles jt0 + c >= JT skip their MFMAs
+template <int NC, bool F16>
+DEV void linear_tiles_wave(const uint16_t (*Xs)[IPITCH], const uint16_t* F, int KS, int jt0, int JT, int lane,
+                           f32x16 (&acc)[NC]) {
+    const uint16_t* base[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        base[c] = F + ((int64_t)min(jt0 + c, JT - 1) * KS * 64 + lane) * 8;
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[c][r] = 0.f;
+    }
+    const int nc_act = min(NC, JT - jt0);
+    const bool live = (lane & 31) < WR;  // the tile's rows 16..31 are zeros
+    const uint16_t* arow = Xs[lane & (WR - 1)] + 8 * (lane >> 5);
+    const int nch = (KS + 3) / 4;  // 64-deep chunks
+    auto load = [&](u32x4 (&b)[4][NC], int kc) {
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const int ks = min(kc * 4 + s, KS - 1);
+#pragma unroll
+            for (int c = 0; c < NC; c++) b[s][c] = *reinterpret_cast<const u32x4*>(base[c] + ks * 512);
+        }
+    };
+    auto step = [&](const u32x4 (&b)[4][NC], int kc) {
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const int ks = kc * 4 + s;
+            if (ks >= KS) break;
+            u32x4 t = *reinterpret_cast<const u32x4*>(arow + ks * 16);
+            const u32x4 z = {0u, 0u, 0u, 0u};
+            t = live ? t : z;
+            const bf16x8 av = __builtin_bit_cast(bf16x8, t);
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                if (c >= nc_act) break;
+                acc[c] = mlp::mfma16<F16>(av, __builtin_bit_cast(bf16x8, b[s][c]), acc[c]);
+            }
+        }
+    };
+    u32x4 b0[4][NC], b1[4][NC];
+    load(b0, 0);
+    for (int kc = 0; kc < nch; kc += 2) {
+        load(b1, kc + 1);
+        step(b0, kc);
+        load(b0, kc + 2);
+        step(b1, kc + 1);
+    }
+}
+
+// The forward of `rows` <= WR rows by the calling wave (64 lanes, all of them call): X [rows][a.in] f32 obs, masks
+// [rows][outputs] (mode 1), row0 the global number of row 0 (the sampler's Philox counter) and `step` its step;
+// row_sel / act / logp / out_f are the rows' own (indexed from row 0).  The network is a's (P, F, widths, offsets,
+// slope, use_ln, mode, det, temp, seed, sel); a's row pointers, n, row0 and step are not read.
+template <bool F16, int ACT>
+DEV void wave_infer(const InferArgs& a, WaveLDS& S, const float* X, const uint8_t* masks, int rows, int64_t row0,
+                    uint64_t step, const uint8_t* row_sel, int32_t* act, float* logp, float* out_f, int lane) {
+    uint16_t (*in)[IPITCH] = S.X[0];
+    uint16_t (*out)[IPITCH] = S.X[1];
+    const int A = a.width[a.nl];
+    {  // obs -> 16-bit (mlp::rows_to_bf16), zeros past `in` up to the first MFMA step boundary and in the rows past `rows`
+        const int k16 = (a.in + 15) / 16 * 16;
+#pragma unroll 4
+        for (int r = 0; r < WR; r++)
+            for (int c = lane; c < k16; c += 64) {
+                const float x = X[(int64_t)min(r, rows - 1) * a.in + min(c, a.in - 1)];
+                in[r][c] = (r < rows && c < a.in) ? f2h<F16>(x) : (uint16_t)0;
+            }
+    }
+    if (a.mode == 1) {
+        for (int f = lane; f < rows * A; f += 64) S.M[f] = masks[f];
+        if (lane < WR) {
+            uint8_t selv = 1;
+            if (row_sel) selv = (row_sel[min(lane, rows - 1)] != 0) == (a.sel != 0);
+            S.Sel[lane] = lane < rows && selv;
+        }
+    }
+    f32x16 acc[WNC];
+    for (int l = 0; l + 1 < a.nl; l++) {
+        const int KS = (a.width[l] + 15) / 16, N = a.width[l + 1], JT = (N + 31) / 32;
+        const int n16 = (N + 15) / 16 * 16;
+        const uint16_t* bias = a.P + a.hb[l];
+        __syncthreads();  // the layer's input is complete; the previous layer's reads of `out` are done
+        for (int jt0 = 0; jt0 < JT; jt0 += WNC) {
+            linear_tiles_wave<WNC, F16>(in, a.F + a.fw[l], KS, jt0, JT, lane, acc);
+#pragma unroll
+            for (int c = 0; c < WNC; c++) {
+                const int j = (jt0 + c) * 32 + (lane & 31);
+                if (jt0 + c >= JT || j >= n16) continue;
+                const float bj = j < N ? h2f<F16>(bias[j]) : 0.f;
+#pragma unroll
+                for (int r = 0; r < 8; r++)  // accumulator elements 0..7: the tile's rows 0..15
+                    out[acc_row(0, r, lane)][j] = j < N ? f2h<F16>(acc[c][r] + bj) : (uint16_t)0;
+            }
+        }
+        const uint16_t* gg = a.P + (a.hg[l] >= 0 ? a.hg[l] : 0);
+        const uint16_t* bb = a.P + (a.hbe[l] >= 0 ? a.hbe[l] : 0);
+        __syncthreads();
+#pragma unroll 1
+        for (int w = 0; w < WR; w += 8) {
+            if (N == 512) ln_act_rows<8, true, F16, ACT, 8, 1>(out, gg, bb, N, a.slope, a.use_ln, w, lane);
+            else if (N <= 64) ln_act_rows<1, false, F16, ACT, 8, 1>(out, gg, bb, N, a.slope, a.use_ln, w, lane);
+            else if (N <= 128) ln_act_rows<2, false, F16, ACT, 8, 1>(out, gg, bb, N, a.slope, a.use_ln, w, lane);
+            else if (N <= 256) ln_act_rows<4, false, F16, ACT, 8, 1>(out, gg, bb, N, a.slope, a.use_ln, w, lane);
+            else ln_act_rows<8, false, F16, ACT, 8, 1>(out, gg, bb, N, a.slope, a.use_ln, w, lane);
+        }
+        uint16_t (*t)[IPITCH] = in;
+        in = out;
+        out = t;
+    }
+    // output Linear (<= 4 column tiles: one sweep)
+    const int l = a.nl - 1, KS = (a.width[l] + 15) / 16, N = a.width[l + 1], JT = (N + 31) / 32;
+    __syncthreads();
+    linear_tiles_wave<WNC, F16>(in, a.F + a.fw[l], KS, 0, JT, lane, acc);
+#pragma unroll
+    for (int c = 0; c < WNC; c++) {
+        const int j = c * 32 + (lane & 31);
+        if (c >= JT || j >= N) continue;
+        const float bj = h2f<F16>(a.P[a.hb[l] + j]);
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const int i = acc_row(0, r, lane);
+            const uint16_t y = f2h<F16>(acc[c][r] + bj);
+            if (a.mode == 0) {  // f32 outputs: the 16-bit-rounded Linear output
+                if (i < rows) out_f[(int64_t)i * N + j] = h2f<F16>(y);
+            } else {
+                out[i][j] = y;
+            }
+        }
+    }
+    if (a.mode == 0) return;
+    __syncthreads();
+    const auto rowfn = [&](int g, const uint16_t*& lg, const uint8_t*& mk, float*& pr, int& row, bool& ok) {
+        lg = out[g];
+        mk = S.M + g * N;
+        pr = reinterpret_cast<float*>(&out[g][kSampleProbs]);  // the row past its logits: the probs
+        row = g;
+        ok = S.Sel[g] != 0;
+    };
+    ppo::sample_rows_looped<WR, F16>(rowfn, N, a.temp, a.det, a.seed, step, row0, lane, act, logp);
+}
+
+// wave_infer alone: one 64-thread workgroup per WR rows, InferArgs as mlp_infer takes them
+template <bool F16, int ACT = mlp::ACT_LEAKY>
+__global__ void __launch_bounds__(64) mlp_infer_wave(InferArgs a) {
+    __shared__ WaveLDS S;
+    const int r0 = blockIdx.x * WR, A = a.width[a.nl];
+    wave_infer<F16, ACT>(a, S, a.X + (int64_t)r0 * a.in, a.masks ? a.masks + (int64_t)r0 * A : nullptr, min(WR, a.n - r0),
+                         a.row0 + r0, a.step, a.row_sel ? a.row_sel + r0 : nullptr, a.act ? a.act + r0 : nullptr,
+                         a.logp ? a.logp + r0 : nullptr, a.out_f ? a.out_f + (int64_t)r0 * A : nullptr, (int)threadIdx.x);
 }
 
 }  // namespace infer

@@ -768,9 +768,10 @@ struct Draw {
     Draw sub(int64_t b) const { return {det, step, act + b, logp ? logp + b : nullptr, row_sel ? row_sel + b : nullptr, sel}; }
 };
 
-// one fused forward of model mi over a block with the 16-bit copy of the current parameters or (ver) of the old
-// version's: writes f32 outputs to out_f (d null, the kernel's mode 0) or samples actions (d, mode 1)
-void infer_fused(rlgpu_ppo* h, int mi, bool ver, const Rows& r, float* out_f, const Draw* d, hipStream_t s) {
+// One fused forward of model mi over a block with the 16-bit copy of the current parameters or (ver) of the old
+// version's: writes f32 outputs to out_f (d null, the kernel's mode 0) or samples actions (d, mode 1).  fused_args:
+// its launch arguments (the one-wave form takes the same); infer_fused: the launch.
+infer::InferArgs fused_args(const rlgpu_ppo* h, int mi, bool ver, const Rows& r, float* out_f, const Draw* d) {
     const auto& c = h->chain[mi];
     const int n = (int)r.n;
     infer::InferArgs a{};
@@ -804,6 +805,22 @@ void infer_fused(rlgpu_ppo* h, int mi, bool ver, const Rows& r, float* out_f, co
         a.logp = d->logp;
         a.row_sel = d->row_sel;
         a.sel = d->sel;
+    }
+    return a;
+}
+
+// Model mi runs on the one-wave form of the fused kernel too (infer::wave_infer: 16 rows per wavefront): built for
+// LeakyReLU / ReLU only.
+bool wave_ok(const rlgpu_ppo* h, int mi) { return fused_ok(h, mi) && h->cfg.activation == mlp::ACT_LEAKY; }
+
+// wave: on infer::mlp_infer_wave (the caller has checked wave_ok)
+void infer_fused(rlgpu_ppo* h, int mi, bool ver, const Rows& r, float* out_f, const Draw* d, hipStream_t s, bool wave = false) {
+    const int n = (int)r.n;
+    infer::InferArgs a = fused_args(h, mi, ver, r, out_f, d);
+    if (wave) {
+        rlgpu::launch_mlp_infer_wave(f16(h), ceil_div(n, infer::WR), s, &a, sizeof(a));
+        RLGPU_CHECK_HIP(hipGetLastError());
+        return;
     }
     a.trace = g_infer_trace;
     if (a.trace && ceil_div(n, infer::IR) * 16 > g_infer_trace_cap)
@@ -1252,6 +1269,53 @@ extern "C" int rlgpu_ppo_infer_actions_rows(rlgpu_ppo* h, const float* d_obs, co
                                                       "(widths, RLGPU_FUSED_INFER = 0 or fp32 inference)");
         const Rows rows{d_obs, n, row0 + h->cfg.sample_row_offset, d_masks};
         infer_policy(h, rows, Draw{deterministic, rng_step, d_actions, d_logp}, d_old_rows, INT64_MAX, rlgpu::as_stream(stream));
+    });
+}
+
+bool rlgpu::ppo_wave_policy(rlgpu_ppo* h, int obs_size, int num_actions) {
+    return h && wave_ok(h, 0) && h->cfg.obs_size == obs_size && h->cfg.num_actions == num_actions;
+}
+void rlgpu::ppo_wave_args(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int64_t n, int deterministic,
+                          uint64_t rng_step, int32_t* d_actions, float* d_logp, void* blob, size_t cap, bool* f16_out) {
+    RLGPU_REQUIRE(h && wave_ok(h, 0), "ppo_wave_args: the policy is not on the one-wave kernel");
+    const Draw d{deterministic, rng_step, d_actions, d_logp};
+    const infer::InferArgs a = fused_args(h, 0, false, Rows{d_obs, n, h->cfg.sample_row_offset, d_masks}, nullptr, &d);
+    RLGPU_REQUIRE(sizeof(a) <= cap, "ppo_wave_args: InferArgs do not fit the blob");
+    std::memcpy(blob, &a, sizeof(a));
+    *f16_out = f16(h);
+}
+
+extern "C" int rlgpu_ppo_wave_infer(rlgpu_ppo* h, int32_t model) { return h && model >= 0 && model < 3 && wave_ok(h, model); }
+
+extern "C" int rlgpu_ppo_infer_actions_wave(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int32_t n, int64_t row0,
+                                            int32_t deterministic, uint64_t rng_step, const uint8_t* d_old_rows,
+                                            int32_t* d_actions, float* d_logp, void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && d_obs && d_masks && d_actions, "null argument");
+        RLGPU_REQUIRE(n >= 0 && row0 >= 0, "n and row0 must be >= 0");
+        RLGPU_REQUIRE(!d_old_rows || h->has_ver, "rlgpu_ppo_infer_actions_wave: old rows without a version set");
+        if (!wave_ok(h, 0))
+            throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "rlgpu_ppo_infer_actions_wave: the policy is not eligible for the one-wave "
+                                                      "kernel (the fused kernel's conditions and LeakyReLU / ReLU)");
+        if (n == 0) return;
+        const Rows rows{d_obs, n, row0 + h->cfg.sample_row_offset, d_masks};
+        Draw d{deterministic, rng_step, d_actions, d_logp, d_old_rows, 0};
+        for (d.sel = 0; d.sel < (d_old_rows ? 2 : 1); d.sel++) {  // infer_policy's passes, unchunked
+            if (d.sel) d.logp = nullptr;
+            infer_fused(h, 0, d.sel != 0, rows, nullptr, &d, rlgpu::as_stream(stream), true);
+        }
+    });
+}
+
+extern "C" int rlgpu_ppo_infer_values_wave(rlgpu_ppo* h, int32_t model, const float* d_obs, int32_t n, float* d_out,
+                                           void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && d_obs && d_out && n >= 0 && model >= 0 && model < 2, "rlgpu_ppo_infer_values_wave: bad argument");
+        if (!wave_ok(h, model))
+            throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "rlgpu_ppo_infer_values_wave: the model is not eligible for the one-wave "
+                                                      "kernel (the fused kernel's conditions and LeakyReLU / ReLU)");
+        if (n == 0) return;
+        infer_fused(h, model, false, Rows{d_obs, n, 0, nullptr}, d_out, nullptr, rlgpu::as_stream(stream), true);
     });
 }
 

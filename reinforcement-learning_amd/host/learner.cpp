@@ -482,9 +482,47 @@ void Learner::CollectGrouped(int G) {
     }
 }
 
+// The collection loop (rlgpu_envset_collect_loop): the whole rollout in one launch on s_, every env workgroup
+// looping over the T steps of its own 4 arenas with the policy forward of its 16 players inside it, so no step
+// waits for the slowest workgroup of the step before.  Per iteration, only where it computes what the per-step path
+// does: CollectGroups()'s conditions, no old version playing (the loop runs one set of weights), and what the entry
+// itself asks for (the msvc_x64 arithmetic, no env profile, a policy on the one-wave kernel).  Any arena count: a last
+// workgroup with fewer than 4 arenas runs its fewer rows, as in the per-step kernel.
+// collect_groups = 0 selects it from kAutoCollectArenas on: it won its A/B against 2 groups there (DESIGN.md section
+// 11: the collection 127.0 -> about 98 ms); ineligible iterations keep the 2 groups
+constexpr bool kAutoCollectLoop = true;
+
+bool Learner::CollectLoopOk() const {
+    if (hook_ || K_ > 1 || trajMode() || oldTeam_ >= 0) return false;
+    return rlgpu_envset_collect_loop_ok(env_->handle(), ppo_->handle()) != 0;
+}
+
+void Learner::CollectLoop() {
+    const rlgpu_rollout_view& v = exp_.v;
+    const rlgpu_collect_rollout ro{v.obs, v.masks, v.actions, v.logp, v.rewards, v.terms, v.trunc_obs};
+    if (envTiming_) {
+        EnsureEvents(2);
+        hipCheck(hipEventRecord(ev_[0], s_), "event");
+    }
+    RlgpuCheck(rlgpu_envset_collect_loop(env_->handle(), ppo_->handle(), exp_.T, &ro, cfg_.deterministic != 0,
+                                         (uint64_t)stats.rng_step, s_),
+               "collection loop");
+    if (envTiming_) hipCheck(hipEventRecord(ev_[1], s_), "event");
+    stats.rng_step += exp_.T;
+}
+
 void Learner::Collect() {
     if (trajMode()) {
         CollectTrajectories();
+        return;
+    }
+    collectLoopUsed_ = false;
+    const bool wantLoop = cfg_.collect_groups < 0 ||
+                          (kAutoCollectLoop && cfg_.collect_groups == 0 && cfg_.num_arenas >= kAutoCollectArenas);
+    if (wantLoop && CollectLoopOk()) {
+        collectGroupsUsed_ = 1;
+        collectLoopUsed_ = true;
+        CollectLoop();
         return;
     }
     if (const int G = CollectGroups(); G > 1 && EnsureGroupStreams(G)) {
@@ -920,9 +958,11 @@ rlgpu_learner_report Learner::Iterate() {
         // per env launch: T per group (the trajectory mode records no per-step events)
         const int nt = trajMode() ? 0 : exp_.T * std::max(1, collectGroupsUsed_);
         std::vector<float> each(nt);
+        float loop = 0;  // the collection loop: one launch, reported as its T equal shares (inference included)
+        if (collectLoopUsed_) hipCheck(hipEventElapsedTime(&loop, ev_[0], ev_[1]), "elapsed");
         for (int t = 0; t < nt; t++) {
-            float x = 0;
-            hipCheck(hipEventElapsedTime(&x, ev_[2 * t], ev_[2 * t + 1]), "elapsed");
+            float x = loop / (float)nt;
+            if (!collectLoopUsed_) hipCheck(hipEventElapsedTime(&x, ev_[2 * t], ev_[2 * t + 1]), "elapsed");
             ms += x;
             each[t] = x;
         }

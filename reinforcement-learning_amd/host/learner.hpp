@@ -229,6 +229,10 @@ private:
     bool EnsureGroupStreams(int G);
     int collectGroupsUsed_ = 1;
     void CollectGrouped(int G);
+    // the rollout collection in one launch (collect_groups = -1; rlgpu_envset_collect_loop)
+    bool collectLoopUsed_ = false;
+    bool CollectLoopOk() const;
+    void CollectLoop();
     // device scratch
     uint8_t* oldRows_[2] = {nullptr, nullptr};
     // the rows that act with the old version this iteration (self-play), or null

@@ -202,7 +202,8 @@ class LearnerConfig:
         self.policy_temperature = 1.0     # PPOLearnerConfig::policyTemperature: collection, old versions and Learn
         self.mask_entropy = False         # PPOLearnerConfig::maskEntropy: entropy over log(legal actions) per row
         self.collect_groups = 0           # rollout collection in arena groups on their own streams and CU partitions
-                                          # (0 = automatic: 2 groups from 4096 arenas on; 1 = one launch per step)
+                                          # (0 = automatic: 2 groups from 4096 arenas on; 1 = one launch per step;
+                                          # -1 = the collection loop, the whole rollout in one launch, where eligible)
         # checkpoints (LearnerConfig.h:31-38): None = no save / load
         self.checkpoint_folder = None
         self.ts_per_save = 10_000_000     # 0 = every iteration (Learner.cpp:44-45)
@@ -515,7 +516,8 @@ class Learner:
         L = _lib.lib()
         if fn is None:
             self._hook = None
-            _lib.check(L.rlgpu_learner_set_step_hook(self._h, None, None), "rlgpu_learner_set_step_hook")
+            # a NULL function pointer of the bound type (argtypes, once set below, refuse a plain None)
+            _lib.check(L.rlgpu_learner_set_step_hook(self._h, ctypes.cast(None, self._HOOK), None), "rlgpu_learner_set_step_hook")
             return
 
         def thunk(_user, phase):

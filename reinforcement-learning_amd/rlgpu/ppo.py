@@ -77,6 +77,10 @@ def _bind():
     L.rlgpu_ppo_set_optimizer_step.argtypes = [vp, i64]
     L.rlgpu_ppo_set_version.argtypes = [vp, vp, vp]
     L.rlgpu_ppo_infer_actions_mixed.argtypes = [vp, vp, vp, i32, i32, u64, vp, vp, vp, vp]
+    L.rlgpu_ppo_infer_actions_rows.argtypes = [vp, vp, vp, i32, i64, i32, u64, vp, vp, vp, vp]
+    L.rlgpu_ppo_infer_actions_wave.argtypes = [vp, vp, vp, i32, i64, i32, u64, vp, vp, vp, vp]
+    L.rlgpu_ppo_infer_values_wave.argtypes = [vp, i32, vp, i32, vp, vp]
+    L.rlgpu_ppo_wave_infer.argtypes = [vp, i32]
     L.rlgpu_permutation.argtypes = [i64, u64, u64, vp, vp]
     L.rlgpu_kernel_timing.argtypes = [i32]
     L.rlgpu_kernel_timing_read.argtypes = [vp, vp, vp, i32]
@@ -307,6 +311,38 @@ class PPO:
                                                             step, _lib.ptr(old_rows), _lib.ptr(actions), _lib.ptr(logp),
                                                             _lib.stream_ptr()), "rlgpu_ppo_infer_actions_mixed")
         return actions, logp
+
+    def _actions_rows(self, entry, obs, masks, row0, step, deterministic, old_rows, actions, logp):
+        import torch
+        n = obs.shape[0]
+        actions = torch.empty(n, dtype=torch.int32, device=self.device) if actions is None else actions
+        logp = torch.empty(n, device=self.device) if logp is None else logp
+        _lib.check(getattr(_lib.lib(), entry)(self._h, _lib.ptr(obs), _lib.ptr(masks), n, row0, int(deterministic), step,
+                                              _lib.ptr(old_rows) if old_rows is not None else None, _lib.ptr(actions),
+                                              _lib.ptr(logp), _lib.stream_ptr()), entry)
+        return actions, logp
+
+    def infer_actions_rows(self, obs, masks, row0=0, step=0, deterministic=False, old_rows=None, actions=None, logp=None):
+        """rlgpu_ppo_infer_actions_rows: the rows are rows [row0, row0 + n) of the sampler's numbering (fused kernel only)."""
+        return self._actions_rows("rlgpu_ppo_infer_actions_rows", obs, masks, row0, step, deterministic, old_rows, actions, logp)
+
+    def infer_actions_wave(self, obs, masks, row0=0, step=0, deterministic=False, old_rows=None, actions=None, logp=None):
+        """The same call on the one-wave form of the fused kernel (16 rows per 64-thread workgroup, the collection
+        loop's inference): the same actions and log probs, bit for bit.  RLGPUError when the policy is not eligible
+        (wave_infer_ok)."""
+        return self._actions_rows("rlgpu_ppo_infer_actions_wave", obs, masks, row0, step, deterministic, old_rows, actions, logp)
+
+    def infer_values_wave(self, model, obs, out=None):
+        """The 16-bit forward of model 0 / 1 on the one-wave kernel: f32 outputs [n, outputs] (= forward(model, x, half=True))."""
+        import torch
+        n = obs.shape[0]
+        out = torch.empty((n, self.model_out(model)), device=self.device) if out is None else out
+        _lib.check(_lib.lib().rlgpu_ppo_infer_values_wave(self._h, model, _lib.ptr(obs), n, _lib.ptr(out), _lib.stream_ptr()),
+                   "rlgpu_ppo_infer_values_wave")
+        return out
+
+    def wave_infer_ok(self, model=0):
+        return bool(_lib.lib().rlgpu_ppo_wave_infer(self._h, model))
 
     def infer_critic(self, obs, out=None):
         import torch
