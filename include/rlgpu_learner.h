@@ -245,6 +245,16 @@ int rlgpu_learner_finish_iteration(rlgpu_learner* h);
  * rlgpu_ppo_set_version (its rows are simulated but not trained or counted); -1 = off. */
 int rlgpu_learner_set_old_team(rlgpu_learner* h, int32_t team);
 
+/* Guiding policy (PPOLearnerConfig::useGuidingPolicy / guidingStrength, PPOLearner.cpp:35-38,458-468): d_policy_params
+ * is the frozen policy's flat fp32 parameters in rlgpu_ppo_set_guide's layout (the policy's, then the shared head's);
+ * every later learn phase runs one guide pass over the rows it trains on (T * P rows of the rollout, or the combined
+ * batch's in RLGPU_EXP_TRAJECTORIES) and adds guiding_strength * mean |guide probs - probs| to every minibatch's loss
+ * (rlgpu_ppo_minibatch_guided; metric RLGPU_M_GUIDING_LOSS).  Collection is untouched.  guiding_strength finite and
+ * >= 0; RLGPU_ERR_UNSUPPORTED with fp32 inference.  guide_logits: a read-only view of the last learn phase's guide
+ * logits, [rows][RLGPU_ACTIONS] in the 16-bit inference format (NULL / 0 before the first guided learn). */
+int rlgpu_learner_set_guide(rlgpu_learner* h, const float* d_policy_params, float guiding_strength);
+int rlgpu_learner_guide_logits(rlgpu_learner* h, const uint16_t** d_logits, int64_t* rows);
+
 /* Host plugins and a StepCallbackFn inside the collection loop (Learner.cpp:676-861; EnvSet.cpp:163-255).
  * With a hook set, every collection step runs: the env step WITHOUT resetting terminated arenas, then
  * fn(user, RLGPU_HOOK_AFTER_STEP) -- the env set (rlgpu_learner_handles) holds the post-step, pre-reset state;

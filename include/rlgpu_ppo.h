@@ -112,7 +112,8 @@ typedef struct rlgpu_ppo rlgpu_ppo;
 enum {
     RLGPU_M_ENTROPY = 0, RLGPU_M_KL, RLGPU_M_POLICY_LOSS, RLGPU_M_CRITIC_LOSS, RLGPU_M_RATIO,
     RLGPU_M_CLIP_FRACTION, RLGPU_M_COUNT, RLGPU_M_GRAD_NORM_POLICY, RLGPU_M_GRAD_NORM_CRITIC,
-    RLGPU_M_GRAD_NORM_SHARED, RLGPU_NUM_METRICS = 16
+    RLGPU_M_GRAD_NORM_SHARED, RLGPU_M_GUIDING_LOSS = 10 /* rlgpu_ppo_minibatch_guided: mean |guide probs - probs| */,
+    RLGPU_NUM_METRICS = 16
 };
 
 int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out);
@@ -173,6 +174,15 @@ int rlgpu_ppo_set_version(rlgpu_ppo* h, const float* d_policy_params, void* stre
 int rlgpu_ppo_infer_actions_mixed(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int32_t n,
                                   int32_t deterministic, uint64_t rng_step, const uint8_t* d_old_rows,
                                   int32_t* d_actions, float* d_logp, void* stream);
+/* Guiding policy (PPOLearnerConfig::useGuidingPolicy / guidingPolicyPath, PPOLearner.cpp:35-38): a frozen policy the
+ * loss pulls the trained one toward.  set_guide takes rlgpu_ppo_set_version's layout (the policy's flat fp32 parameters,
+ * then the shared head's) into a third 16-bit copy, allocated by the first call (an unguided handle's memory is what it
+ * was); RLGPU_ERR_UNSUPPORTED on an RLGPU_INFER_F32 handle.  infer_guide_logits: the guide's 16-bit inference forward
+ * (the arithmetic of an old version, = rlgpu_ppo_forward precision 1 on those parameters) over any n rows, written as
+ * [n, num_actions] logits in the handle's 16-bit format (bf16 / fp16; lossless: the forward's outputs are 16-bit
+ * values) -- the d_guide_logits of rlgpu_ppo_minibatch_guided. */
+int rlgpu_ppo_set_guide(rlgpu_ppo* h, const float* d_policy_params, void* stream);
+int rlgpu_ppo_infer_guide_logits(rlgpu_ppo* h, const float* d_obs, int64_t n, uint16_t* d_logits16, void* stream);
 /* rlgpu_ppo_infer_actions (d_old_rows NULL) or _mixed over n rows that are rows [row0, row0 + n) of this rank's
  * players (the sampler's Philox row index is row0 + i; d_obs / d_masks / d_actions / d_logp / d_old_rows point
  * at those rows).  Calls on disjoint rows may run concurrently on different streams (the C++ Learner's arena
@@ -216,6 +226,19 @@ int rlgpu_ppo_minibatch(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks
                         const float* d_old_logp, const float* d_adv, const float* d_target,
                         const int32_t* d_index, int64_t start, int32_t n, int64_t batch_size,
                         const float* d_adv_stats, float* d_metrics, void* stream);
+
+/* rlgpu_ppo_minibatch plus the guiding term (PPOLearner.cpp:458-468): with g = clamp(softmax(guide logit /
+ * cfg.policy_temperature + (-1e10)*!mask), 1e-11, 1) of d_guide_logits [*, A] (16-bit, the handle's inference format,
+ * gathered by the sample index like d_masks) and c the policy's clamped probabilities,
+ *   loss += guiding_strength * mean over all n*A elements of |g - c|
+ * added after the n/batch_size scaling (so not multiplied by it, as in the reference); the mean is summed into
+ * d_metrics[RLGPU_M_GUIDING_LOSS].  guiding_strength finite and >= 0.  d_guide_logits NULL: rlgpu_ppo_minibatch itself
+ * (the same launches); non-NULL on an RLGPU_INFER_F32 handle: RLGPU_ERR_UNSUPPORTED. */
+int rlgpu_ppo_minibatch_guided(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, const int32_t* d_actions,
+                               const float* d_old_logp, const float* d_adv, const float* d_target,
+                               const int32_t* d_index, int64_t start, int32_t n, int64_t batch_size,
+                               const float* d_adv_stats, const uint16_t* d_guide_logits, float guiding_strength,
+                               float* d_metrics, void* stream);
 
 /* clip_grad_norm_(model, max_grad_norm) per model (policy, critic, shared head: PPOLearner.cpp:521-526),
  * AdamW step (libtorch semantics), zero grads, refresh the bf16 copy.  Grad norms written to

@@ -160,6 +160,11 @@ struct rlgpu_ppo {
     uint16_t *frag = nullptr, *frag_ver = nullptr;  // the weights of half / half_ver in MFMA fragment order
     int64_t nfrag = 0;
     bool has_ver = false;
+    // the guiding policy (rlgpu_ppo_set_guide): a third 16-bit copy + its fragment-order copy, and the f32 logits of one
+    // chunk of the fused guide pass [max_rows][A]; all allocated by the first set_guide, none on an unguided handle
+    uint16_t *half_guide = nullptr, *frag_guide = nullptr;
+    float* guide_f = nullptr;
+    bool has_guide = false;
     // the training GEMMs' split weight planes are stale (parameters changed since the last split):
     // set by init / refresh_half / the optimizer step, cleared when forward_train re-splits.  With
     // the whole iteration as one batch the planes are rebuilt once per optimizer step, not per
@@ -768,18 +773,28 @@ struct Draw {
     Draw sub(int64_t b) const { return {det, step, act + b, logp ? logp + b : nullptr, row_sel ? row_sel + b : nullptr, sel}; }
 };
 
-// One fused forward of model mi over a block with the 16-bit copy of the current parameters or (ver) of the old
-// version's: writes f32 outputs to out_f (d null, the kernel's mode 0) or samples actions (d, mode 1).  fused_args:
+// which 16-bit copy of the weights an inference pass reads: the current parameters', the old version's
+// (rlgpu_ppo_set_version) or the guiding policy's (rlgpu_ppo_set_guide)
+enum class Weights { Current, Version, Guide };
+inline const uint16_t* half_of(const rlgpu_ppo* h, Weights w) {
+    return w == Weights::Guide ? h->half_guide : (w == Weights::Version ? h->half_ver : h->half);
+}
+inline const uint16_t* frag_of(const rlgpu_ppo* h, Weights w) {
+    return w == Weights::Guide ? h->frag_guide : (w == Weights::Version ? h->frag_ver : h->frag);
+}
+inline Weights version_if(bool ver) { return ver ? Weights::Version : Weights::Current; }
+
+// One fused forward of model mi over a block with the 16-bit copy `w` names: writes f32 outputs to out_f (d null, the kernel's mode 0) or samples actions (d, mode 1).  fused_args:
 // its launch arguments (the one-wave form takes the same); infer_fused: the launch.
-infer::InferArgs fused_args(const rlgpu_ppo* h, int mi, bool ver, const Rows& r, float* out_f, const Draw* d) {
+infer::InferArgs fused_args(const rlgpu_ppo* h, int mi, Weights w, const Rows& r, float* out_f, const Draw* d) {
     const auto& c = h->chain[mi];
     const int n = (int)r.n;
     infer::InferArgs a{};
     a.X = r.X;
     a.n = n;
     a.in = h->cfg.obs_size;
-    a.P = ver ? h->half_ver : h->half;
-    a.F = ver ? h->frag_ver : h->frag;
+    a.P = half_of(h, w);
+    a.F = frag_of(h, w);
     a.nl = (int)c.size();
     a.width[0] = a.in;
     for (int l = 0; l < a.nl; l++) {
@@ -814,9 +829,9 @@ infer::InferArgs fused_args(const rlgpu_ppo* h, int mi, bool ver, const Rows& r,
 bool wave_ok(const rlgpu_ppo* h, int mi) { return fused_ok(h, mi) && h->cfg.activation == mlp::ACT_LEAKY; }
 
 // wave: on infer::mlp_infer_wave (the caller has checked wave_ok)
-void infer_fused(rlgpu_ppo* h, int mi, bool ver, const Rows& r, float* out_f, const Draw* d, hipStream_t s, bool wave = false) {
+void infer_fused(rlgpu_ppo* h, int mi, Weights w, const Rows& r, float* out_f, const Draw* d, hipStream_t s, bool wave = false) {
     const int n = (int)r.n;
-    infer::InferArgs a = fused_args(h, mi, ver, r, out_f, d);
+    infer::InferArgs a = fused_args(h, mi, w, r, out_f, d);
     if (wave) {
         rlgpu::launch_mlp_infer_wave(f16(h), ceil_div(n, infer::WR), s, &a, sizeof(a));
         RLGPU_CHECK_HIP(hipGetLastError());
@@ -838,7 +853,7 @@ void infer_fused(rlgpu_ppo* h, int mi, bool ver, const Rows& r, float* out_f, co
 // (useHalfPrecision = false) or 16-bit.  half: 16-bit on an fp32 handle too (rlgpu_ppo_forward's precision 1).
 void infer_values(rlgpu_ppo* h, int mi, const Rows& r, float* out, hipStream_t s, bool half = false) {
     if (infer_f32(h) && !half) return forward_f32(h, mi, r.X, (int)r.n, out, s);
-    if (fused_ok(h, mi)) return infer_fused(h, mi, false, r, out, nullptr, s);
+    if (fused_ok(h, mi)) return infer_fused(h, mi, Weights::Current, r, out, nullptr, s);
     const uint16_t* y = forward_half(h, mi, r.X, (int)r.n, s);
     const int64_t e = r.n * h->M[mi].out;
     RLGPU_H16_LAUNCH(f16(h), ppo::bf16_to_f32, dim3(ceil_div(e, 256)), dim3(256), 0, s, y, out, e);
@@ -848,7 +863,7 @@ void infer_values(rlgpu_ppo* h, int mi, const Rows& r, float* out, hipStream_t s
 // one policy forward over a block (n <= max_rows off the fused kernel) and its draw, with the current parameters
 // or (ver) the old version's: the fused kernel, or fp32 logits / forward_half and the sampler
 void sample_pass(rlgpu_ppo* h, bool ver, const Rows& r, const Draw& d, hipStream_t s) {
-    if (fused_ok(h, 0)) return infer_fused(h, 0, ver, r, nullptr, &d, s);
+    if (fused_ok(h, 0)) return infer_fused(h, 0, version_if(ver), r, nullptr, &d, s);
     const int n = (int)r.n;
     const auto sample = [&](auto kern, const auto* logits) {
         hipLaunchKernelGGL(kern, dim3(ceil_div(n, 4)), dim3(256), 0, s, logits, r.masks, n, h->cfg.num_actions,
@@ -1242,6 +1257,53 @@ extern "C" int rlgpu_ppo_set_version(rlgpu_ppo* h, const float* d_policy_params,
     });
 }
 
+static_assert(ppo::kGuidingLossSlot == RLGPU_M_GUIDING_LOSS, "the guided loss kernel's metric slot");
+
+extern "C" int rlgpu_ppo_set_guide(rlgpu_ppo* h, const float* d_policy_params, void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && d_policy_params, "rlgpu_ppo_set_guide: null argument");
+        if (infer_f32(h))
+            throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "rlgpu_ppo_set_guide: fp32 inference (RLGPU_INFER_F32) keeps no 16-bit "
+                                                      "copies (a guiding policy needs 16-bit inference)");
+        hipStream_t s = rlgpu::as_stream(stream);
+        if (!h->half_guide) {  // the first guide: its copies and the fused pass's f32 chunk
+            h->half_guide = h->alloc<uint16_t>(h->nhalf + 8);
+            h->frag_guide = h->alloc<uint16_t>(h->nfrag);
+            h->guide_f = h->alloc<float>((int64_t)h->cfg.max_rows * h->cfg.num_actions);
+        }
+        half_from(h, 0, d_policy_params, h->half_guide, h->frag_guide, s);
+        // the guide's shared head follows its policy, as an old version's does
+        if (h->shared()) half_from(h, 2, d_policy_params + h->M[0].count, h->half_guide, h->frag_guide, s);
+        h->has_guide = true;
+    });
+}
+
+extern "C" int rlgpu_ppo_infer_guide_logits(rlgpu_ppo* h, const float* d_obs, int64_t n, uint16_t* d_logits16, void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && d_obs && d_logits16 && n >= 0, "rlgpu_ppo_infer_guide_logits: bad argument");
+        RLGPU_REQUIRE(h->has_guide, "rlgpu_ppo_infer_guide_logits: no guide set (rlgpu_ppo_set_guide)");
+        hipStream_t s = rlgpu::as_stream(stream);
+        const int A = h->cfg.num_actions;
+        const Rows rows{d_obs, n, 0, nullptr};
+        // chunks of max_rows on both paths: the fused kernel's f32 outputs go through guide_f, the layered kernels
+        // work in the per-handle row buffers
+        for (int64_t b = 0; b < n; b += h->cfg.max_rows) {
+            const Rows r = rows.sub(h->cfg, b, std::min<int64_t>(h->cfg.max_rows, n - b));
+            const int64_t e = r.n * A;
+            uint16_t* out = d_logits16 + b * A;
+            if (fused_ok(h, 0)) {
+                infer_fused(h, 0, Weights::Guide, r, h->guide_f, nullptr, s);
+                // exact: the kernel's f32 outputs are 16-bit-rounded values
+                RLGPU_H16_LAUNCH(f16(h), ppo::to_half, dim3(ceil_div(e, 256)), dim3(256), 0, s, h->guide_f, out, e);
+                RLGPU_CHECK_HIP(hipGetLastError());
+            } else {
+                const uint16_t* y = forward_half(h, 0, r.X, (int)r.n, s, h->half_guide);
+                RLGPU_CHECK_HIP(hipMemcpyAsync(out, y, e * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
+            }
+        }
+    });
+}
+
 extern "C" int rlgpu_ppo_infer_actions_mixed(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int32_t n,
                                              int32_t deterministic, uint64_t rng_step, const uint8_t* d_old_rows,
                                              int32_t* d_actions, float* d_logp, void* stream) {
@@ -1279,7 +1341,7 @@ void rlgpu::ppo_wave_args(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_mas
                           uint64_t rng_step, int32_t* d_actions, float* d_logp, void* blob, size_t cap, bool* f16_out) {
     RLGPU_REQUIRE(h && wave_ok(h, 0), "ppo_wave_args: the policy is not on the one-wave kernel");
     const Draw d{deterministic, rng_step, d_actions, d_logp};
-    const infer::InferArgs a = fused_args(h, 0, false, Rows{d_obs, n, h->cfg.sample_row_offset, d_masks}, nullptr, &d);
+    const infer::InferArgs a = fused_args(h, 0, Weights::Current, Rows{d_obs, n, h->cfg.sample_row_offset, d_masks}, nullptr, &d);
     RLGPU_REQUIRE(sizeof(a) <= cap, "ppo_wave_args: InferArgs do not fit the blob");
     std::memcpy(blob, &a, sizeof(a));
     *f16_out = f16(h);
@@ -1302,7 +1364,7 @@ extern "C" int rlgpu_ppo_infer_actions_wave(rlgpu_ppo* h, const float* d_obs, co
         Draw d{deterministic, rng_step, d_actions, d_logp, d_old_rows, 0};
         for (d.sel = 0; d.sel < (d_old_rows ? 2 : 1); d.sel++) {  // infer_policy's passes, unchunked
             if (d.sel) d.logp = nullptr;
-            infer_fused(h, 0, d.sel != 0, rows, nullptr, &d, rlgpu::as_stream(stream), true);
+            infer_fused(h, 0, version_if(d.sel != 0), rows, nullptr, &d, rlgpu::as_stream(stream), true);
         }
     });
 }
@@ -1315,7 +1377,7 @@ extern "C" int rlgpu_ppo_infer_values_wave(rlgpu_ppo* h, int32_t model, const fl
             throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "rlgpu_ppo_infer_values_wave: the model is not eligible for the one-wave "
                                                       "kernel (the fused kernel's conditions and LeakyReLU / ReLU)");
         if (n == 0) return;
-        infer_fused(h, model, false, Rows{d_obs, n, 0, nullptr}, d_out, nullptr, rlgpu::as_stream(stream), true);
+        infer_fused(h, model, Weights::Current, Rows{d_obs, n, 0, nullptr}, d_out, nullptr, rlgpu::as_stream(stream), true);
     });
 }
 
@@ -1349,11 +1411,24 @@ extern "C" int rlgpu_ppo_minibatch(rlgpu_ppo* h, const float* d_obs, const uint8
                                    const float* d_old_logp, const float* d_adv, const float* d_target, const int32_t* d_index,
                                    int64_t start, int32_t n, int64_t batch_size, const float* d_adv_stats, float* d_metrics,
                                    void* stream) {
+    return rlgpu_ppo_minibatch_guided(h, d_obs, d_masks, d_actions, d_old_logp, d_adv, d_target, d_index, start, n, batch_size,
+                                      d_adv_stats, nullptr, 0.f, d_metrics, stream);
+}
+
+extern "C" int rlgpu_ppo_minibatch_guided(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, const int32_t* d_actions,
+                                          const float* d_old_logp, const float* d_adv, const float* d_target,
+                                          const int32_t* d_index, int64_t start, int32_t n, int64_t batch_size,
+                                          const float* d_adv_stats, const uint16_t* d_guide_logits, float guiding_strength,
+                                          float* d_metrics, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(h && d_obs && d_masks && d_actions && d_old_logp && d_adv && d_target && d_adv_stats,
                       "rlgpu_ppo_minibatch: null argument");
         RLGPU_REQUIRE(n > 0 && n <= h->cfg.max_rows, "minibatch rows must be in [1, max_rows]");
         RLGPU_REQUIRE(batch_size > 0, "batch_size must be > 0");
+        RLGPU_REQUIRE(std::isfinite(guiding_strength) && guiding_strength >= 0.f, "guiding_strength must be finite and >= 0");
+        if (d_guide_logits && infer_f32(h))
+            throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "rlgpu_ppo_minibatch_guided: guide logits on an fp32-inference handle "
+                                                      "(RLGPU_INFER_F32 has no 16-bit logit format)");
         hipStream_t s = rlgpu::as_stream(stream);
         float bsr = (float)n / (float)batch_size;  // PPOLearner.cpp:374
         int A = h->cfg.num_actions;
@@ -1380,10 +1455,17 @@ extern "C" int rlgpu_ppo_minibatch(rlgpu_ppo* h, const float* d_obs, const uint8
         // the kernel that knows policy_temperature / mask_entropy only when one of them is set: the defaults run the
         // kernel without them (see policy_loss on why x / 1 alone does not keep the bits)
         const bool pl_opt = h->cfg.policy_temperature != 1.f || h->cfg.mask_entropy != 0;
-        hipLaunchKernelGGL(ppo::policy_loss_any(A, pl_opt), dim3(pl_blocks), dim3(256), 0, s, pm.y, d_masks, d_actions, d_old_logp, d_adv,
-                           d_index, start, n, A, d_adv_stats, bsr, h->cfg.clip_range, h->cfg.entropy_scale,
-                           1.f / std::log((float)A), h->cfg.policy_temperature, h->cfg.mask_entropy, pm.dy, dout_ld(A), d_metrics,
-                           pm.lpart, amax_slot(pm, kAmaxOut));
+        if (d_guide_logits)  // the guided instance (always with the options' semantics); d loss / d c = strength / (n A) sign
+            hipLaunchKernelGGL(ppo::policy_loss_guided_any(A, f16(h)), dim3(pl_blocks), dim3(256), 0, s, pm.y, d_masks, d_actions,
+                               d_old_logp, d_adv, d_index, start, n, A, d_adv_stats, bsr, h->cfg.clip_range, h->cfg.entropy_scale,
+                               1.f / std::log((float)A), h->cfg.policy_temperature, h->cfg.mask_entropy, pm.dy, dout_ld(A),
+                               d_metrics, pm.lpart, amax_slot(pm, kAmaxOut), d_guide_logits,
+                               guiding_strength / ((float)n * (float)A));
+        else
+            hipLaunchKernelGGL(ppo::policy_loss_any(A, pl_opt), dim3(pl_blocks), dim3(256), 0, s, pm.y, d_masks, d_actions, d_old_logp,
+                               d_adv, d_index, start, n, A, d_adv_stats, bsr, h->cfg.clip_range, h->cfg.entropy_scale,
+                               1.f / std::log((float)A), h->cfg.policy_temperature, h->cfg.mask_entropy, pm.dy, dout_ld(A),
+                               d_metrics, pm.lpart, amax_slot(pm, kAmaxOut));
         RLGPU_CHECK_HIP(hipGetLastError());
         backward(h, 0, xin, n, pm.dy, s, pm.lpart, pl_blocks);
         RLGPU_CHECK_HIP(hipStreamWaitEvent(s, h->ev_join, 0));

@@ -18,6 +18,7 @@ using mlp::wave_sum;
 constexpr float kMinProb = 1e-11f;        // ACTION_MIN_PROB
 constexpr float kDisabledLogit = -1e10f;  // ACTION_DISABLED_LOGIT
 constexpr int kMaxA = 128;                // actions per row: 2 per lane
+constexpr int kGuidingLossSlot = 10;      // RLGPU_M_GUIDING_LOSS (include/rlgpu_ppo.h; ppo.hip asserts the match)
 
 // The sampler's Philox key for a draw step: the seed, with the step's high 32 bits folded in (the counter carries its
 // low 32), so streams on separate step ranges -- the skill matches' 2^40 + k (rlgpu/skill.py) against the rollout's
@@ -351,6 +352,15 @@ __device__ __forceinline__ float grp_max(float v) {
     for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// GUIDE (PPOLearnerConfig::useGuidingPolicy, PPOLearner.cpp:458-468,551-552): 0 = none; 1 / 2 = the loss adds
+// g_guide n A mean |gp - c| with gp the guide's clamped probabilities, softmax(guide logit / temp + (-1e10) * !mask)
+// of the frozen policy's 16-bit logits (1: bf16, 2: fp16; rows [*, A] addressed by the sample index like the masks),
+// and g_guide = guidingStrength / (n A) -- the term is added after the batch-size-ratio scaling, so bsr is not in it.
+// Its gradient g_guide sign(c - gp) (sign(0) = 0, torch's abs backward) joins d[k] before the clamp gate, so the
+// softmax backward, the 1 / temp factor, dlogits, the bias partials and the H3 amax all see it; the metric
+// (RLGPU_M_GUIDING_LOSS) is the block's sum of |gp - c| over n A.  Masked columns hold 1e-11 on both sides: exactly 0.
+// GUIDE != 0 always has the OPT = true semantics.  The two kernels share their statements as policy_loss_body.inc, every
+// guided one behind if constexpr: the unguided instances keep their instruction streams.
 template <int K, bool OPT>
 __global__ void __launch_bounds__(256) policy_loss(const float* logits, const uint8_t* masks, const int32_t* actions,
                                                   const float* old_logp, const float* adv, const int32_t* idx, int64_t start,
@@ -358,146 +368,22 @@ __global__ void __launch_bounds__(256) policy_loss(const float* logits, const ui
                                                   float ent_scale, float inv_log_a, float temp, int mask_entropy,
                                                   float* dlogits, int ldd, float* metrics, float* bias_part,
                                                   float* amax) {
-    __shared__ float red[16][5];
-    __shared__ float colred[16][16 * K];  // per (wave, lane group) column sums of dlogits
-    uint32_t vmax = 0;  // max |dlogits| (H3 operand scale, when amax is given)
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, grp = lane >> 4, i = lane & 15;
-    const float mean = adv_stats[0], sd = adv_stats[1];
-    float m_ent = 0.f, m_kl = 0.f, m_pl = 0.f, m_ratio = 0.f, m_clip = 0.f;
-    float col[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) col[k] = 0.f;
-    const float g_pl = -bsr / (float)n;
-    const float g_ent_a = -ent_scale * bsr * inv_log_a / (float)n;  // d loss / d H_i (H_i unnormalised)
-    const float inv_temp = 1.f / temp;  // d z / d logit (OPT)
-#pragma unroll
-    for (int pass = 0; pass < PL_PASSES; pass++) {
-        const int row = blockIdx.x * PL_ROWS + (w * PL_PASSES + pass) * 4 + grp;
-        const bool valid = row < n;
-        const int rowc = valid ? row : n - 1;
-        const int64_t sidx = idx ? (int64_t)idx[start + rowc] : start + rowc;
-        const float* lg = logits + (int64_t)rowc * A;
-        const uint8_t* mk = masks + sidx * A;
-        float z[K], legal_l = 0.f;
-        bool in[K];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const int a = i + 16 * k;
-            in[k] = a < A;
-            if constexpr (OPT) {
-                const bool on = in[k] && mk[a] != 0;
-                z[k] = in[k] ? lg[a] / temp + (on ? 0.f : kDisabledLogit) : -INFINITY;
-                legal_l += on ? 1.f : 0.f;
-            } else {
-                z[k] = in[k] ? lg[a] + (mk[a] ? 0.f : kDisabledLogit) : -INFINITY;
-            }
-        }
-        // maskEntropy: the row's entropy over log(its legal actions) (PPOLearner.cpp:426-428), one legal action
-        // dividing by log 1 = 0 as the reference does; otherwise the launch constant 1 / log A
-        float inv_log = inv_log_a, g_ent = g_ent_a;
-        if constexpr (OPT)
-            if (mask_entropy) {
-                inv_log = 1.f / logf(grp_sum(legal_l));
-                g_ent = -ent_scale * bsr * inv_log / (float)n;
-            }
-        const int a_raw = actions[sidx];
-        const float old = old_logp[sidx], advr = adv[sidx];
-        float m = z[0];
-#pragma unroll
-        for (int k = 1; k < K; k++) m = fmaxf(m, z[k]);
-        m = grp_max(m);
-        float e[K], esum = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            e[k] = in[k] ? expf(z[k] - m) : 0.f;
-            esum += e[k];
-        }
-        const float sum = grp_sum(esum);
-        float p[K], c[K], lgc[K], ent_l = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            p[k] = e[k] / sum;
-            c[k] = fminf(fmaxf(p[k], kMinProb), 1.f);
-            lgc[k] = in[k] ? logf(c[k]) : 0.f;
-            ent_l += in[k] ? lgc[k] * c[k] : 0.f;
-        }
-        const float ent = -grp_sum(ent_l);
-        const int a = a_raw < 0 ? 0 : (a_raw > A - 1 ? A - 1 : a_raw);
-        // the action's clamped probability: lane a % 16 of the group holds it in slot a / 16
-        float mine = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; k++)
-            if (a == i + 16 * k) mine = c[k];
-        const float pa = __shfl(mine, (lane & ~15) | (a & 15), 64);
-        const float lp = logf(pa);
-        const float ratio = expf(lp - old);
-        const float advn = (advr - mean) / (sd + 1e-8f);
-        const float clipped = fminf(fmaxf(ratio, 1.f - clip_range), 1.f + clip_range);
-        const float s1 = ratio * advn, s2 = clipped * advn;
-        const float pl = fminf(s1, s2);
-        // ---- backward (torch semantics: min() ties split the gradient, clamp passes inside [lo, hi])
-        const float g_s1 = s1 < s2 ? g_pl : (s1 == s2 ? g_pl * 0.5f : 0.f);
-        const float g_s2 = s2 < s1 ? g_pl : (s1 == s2 ? g_pl * 0.5f : 0.f);
-        const float in_rng = (ratio >= 1.f - clip_range && ratio <= 1.f + clip_range) ? 1.f : 0.f;
-        const float g_ratio = g_s1 * advn + g_s2 * advn * in_rng;
-        const float g_lp = g_ratio * ratio;
-        float d[K], dot_l = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            d[k] = in[k] ? -g_ent * (lgc[k] + 1.f) : 0.f;
-            if (a == i + 16 * k) d[k] += g_lp / c[k];
-            d[k] = (p[k] >= kMinProb && p[k] <= 1.f) ? d[k] : 0.f;
-            dot_l += in[k] ? d[k] * p[k] : 0.f;
-        }
-        const float dot = grp_sum(dot_l);
-        if (valid) {
-            // dlogits rows of ldd >= A floats: the columns [A, ldd) are written as zeros, so the
-            // output layer's GEMMs read 16-byte vectors across the row end
-            float* dl = dlogits + (int64_t)row * ldd;
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                if (!in[k]) {
-                    if (i + 16 * k < ldd) dl[i + 16 * k] = 0.f;
-                    continue;
-                }
-                const float gk = OPT ? p[k] * (d[k] - dot) * inv_temp : p[k] * (d[k] - dot);
-                dl[i + 16 * k] = gk;
-                col[k] += gk;
-                const uint32_t b = mlp::abs_bits(gk);
-                vmax = b > vmax ? b : vmax;
-            }
-            const float lr = lp - old;
-            m_ent += ent * inv_log;
-            m_kl += expf(lr) - 1.f - lr;
-            m_pl += -pl;
-            m_ratio += ratio;
-            m_clip += fabsf(ratio - 1.f) > clip_range ? 1.f : 0.f;
-        }
-    }
-    const int slot = w * 4 + grp;
-#pragma unroll
-    for (int k = 0; k < K; k++) colred[slot][i + 16 * k] = col[k];
-    if (i == 0) {
-        red[slot][0] = m_ent;
-        red[slot][1] = m_kl;
-        red[slot][2] = m_pl;
-        red[slot][3] = m_ratio;
-        red[slot][4] = m_clip;
-    }
-    __syncthreads();
-    if (bias_part)  // output-bias gradient partials of this block's rows: part[blk][A]
-        for (int c2 = threadIdx.x; c2 < A; c2 += 256) {
-            float t = 0.f;
-            for (int q = 0; q < 16; q++) t += colred[q][c2];
-            bias_part[(int64_t)blockIdx.x * A + c2] = t;
-        }
-    if (threadIdx.x < 5 && metrics) {
-        const int mslot[5] = {0, 1, 2, 4, 5};  // entropy, KL, policy loss, ratio, clip fraction
-        float v = 0.f;
-        for (int q = 0; q < 16; q++) v += red[q][threadIdx.x];
-        atomicAdd(&metrics[mslot[threadIdx.x]], v / (float)n);
-    }
-    if (amax) mlp::h3_amax_commit(amax, vmax);
+    constexpr int GUIDE = 0;
+    [[maybe_unused]] const uint16_t* const guide = nullptr;  // named by the body's discarded guided statements
+    [[maybe_unused]] const float g_guide = 0.f;
+#include "policy_loss_body.inc"
+}
+// the guided loss: policy_loss<K, true> plus the guide term on `guide`, 16-bit logits [*, A] in the format F16 names
+template <int K, bool F16>
+__global__ void __launch_bounds__(256) policy_loss_guided(const float* logits, const uint8_t* masks, const int32_t* actions,
+                                                         const float* old_logp, const float* adv, const int32_t* idx,
+                                                         int64_t start, int n, int A, const float* adv_stats, float bsr,
+                                                         float clip_range, float ent_scale, float inv_log_a, float temp,
+                                                         int mask_entropy, float* dlogits, int ldd, float* metrics,
+                                                         float* bias_part, float* amax, const uint16_t* guide, float g_guide) {
+    constexpr bool OPT = true;
+    constexpr int GUIDE = F16 ? 2 : 1;
+#include "policy_loss_body.inc"
 }
 
 // the instantiation with ceil(A / 16) actions per lane (A = 90: 6 of the 8 slots PL_K allows), with the policy
@@ -517,6 +403,22 @@ inline decltype(&policy_loss<PL_K, OPT>) policy_loss_any(int A) {
 }
 inline decltype(&policy_loss<PL_K, false>) policy_loss_any(int A, bool opt) {
     return opt ? policy_loss_any<true>(A) : policy_loss_any<false>(A);
+}
+template <bool F16>
+inline decltype(&policy_loss_guided<PL_K, F16>) policy_loss_guided_any(int A) {
+    switch ((A + 15) / 16) {
+        case 1: return &policy_loss_guided<1, F16>;
+        case 2: return &policy_loss_guided<2, F16>;
+        case 3: return &policy_loss_guided<3, F16>;
+        case 4: return &policy_loss_guided<4, F16>;
+        case 5: return &policy_loss_guided<5, F16>;
+        case 6: return &policy_loss_guided<6, F16>;
+        case 7: return &policy_loss_guided<7, F16>;
+        default: return &policy_loss_guided<PL_K, F16>;
+    }
+}
+inline decltype(&policy_loss_guided<PL_K, false>) policy_loss_guided_any(int A, bool f16) {
+    return f16 ? policy_loss_guided_any<true>(A) : policy_loss_guided_any<false>(A);
 }
 
 // Critic MSE: loss = mean((v - t)^2) * bsr ; dv = 2 (v - t) / n * bsr.

@@ -678,6 +678,8 @@ class Learner {
     void SyncStats();
     void PushStats();
     void LoadMeshes();
+    void LoadGuidingPolicy();
+    float* guideParams_ = nullptr;  // device: the guiding policy's flat parameters (policy, then shared head)
     void SaveModels(const std::filesystem::path& folder, bool saveOptim, const float* flatParams,
                     const std::vector<int>& which) const;
     friend class PolicyVersionManager;
@@ -692,7 +694,11 @@ inline void Learner::ValidateConfig(const LearnerConfig& c) {
     if (c.standardizeObs) bad("standardizeObs is not supported (obs standardisation is not on the device path)");
     if (!std::isfinite(c.ppo.policyTemperature) || !(c.ppo.policyTemperature > 0))
         bad("ppo.policyTemperature must be finite and > 0");
-    if (c.ppo.useGuidingPolicy) bad("ppo.useGuidingPolicy is not supported");
+    if (c.ppo.useGuidingPolicy && !c.ppo.useHalfPrecision)
+        bad("ppo.useGuidingPolicy with ppo.useHalfPrecision = false: the guiding policy runs on a 16-bit inference copy "
+            "only (set useHalfPrecision = true)");
+    if (c.ppo.useGuidingPolicy && !(std::isfinite(c.ppo.guidingStrength) && c.ppo.guidingStrength >= 0))
+        bad("ppo.guidingStrength must be finite and >= 0");
     if (!c.ppo.useHalfPrecision && (c.trainAgainstOldVersions || c.skillTracker.enabled))
         bad("ppo.useHalfPrecision = false with trainAgainstOldVersions or skillTracker: old policy versions run on "
             "16-bit inference copies only (set useHalfPrecision = true, or turn self-play / skill matches off)");
@@ -833,8 +839,39 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
         versionMgr = new PolicyVersionManager(this, config.checkpointFolder / "policy_versions", config.maxOldVersions,
                                               config.tsPerVersion, config.skillTracker);
     }
+    if (config.ppo.useGuidingPolicy) LoadGuidingPolicy();  // PPOLearner ctor (PPOLearner.cpp:35-38)
     if (!config.checkpointFolder.empty()) Load();
     if (versionMgr) versionMgr->LoadVersions((int64_t)totalTimesteps);
+}
+
+// The guiding policy (PPOLearner.cpp:35-38: MakeModels without a critic, then Load with allowNotExist = false):
+// <guidingPolicyPath>/POLICY.lt and, with a shared head, SHARED_HEAD.lt, of the trained models' sizes; a missing
+// file or another size is an error naming the file.
+inline void Learner::LoadGuidingPolicy() {
+    const std::filesystem::path d = config.ppo.guidingPolicyPath;
+    int64_t poff = 0, pc = 0, soff = 0, sc = 0;
+    RLGC::RlgpuCheck(rlgpu_ppo_model_range(ppo_, 0, &poff, &pc), "model range");
+    RLGC::RlgpuCheck(rlgpu_ppo_model_range(ppo_, 2, &soff, &sc), "model range");
+    std::vector<float> flat((size_t)(pc + sc));
+    for (const ModelSpec& m : models) {
+        if (m.index == 1) continue;
+        const std::filesystem::path p = d / m.FileName();
+        if (!std::filesystem::exists(p)) throw std::runtime_error("guiding policy: " + p.string() + " does not exist");
+        const auto tmp = detail::TempFile("guide.f32");
+        std::vector<std::string> a{"model-load", p.string(), tmp.string()};
+        for (auto& s : m.HelperShape()) a.push_back(s);
+        detail::RunHelper(a);
+        const std::string raw = detail::ReadFile(tmp);
+        std::filesystem::remove(tmp);
+        const int64_t cnt = m.index == 0 ? pc : sc;
+        if ((int64_t)raw.size() != cnt * 4)
+            throw std::runtime_error("guiding policy: " + p.string() + " has different size than the current model");
+        std::memcpy(flat.data() + (m.index == 0 ? 0 : pc), raw.data(), raw.size());
+    }
+    detail::HipOk(hipMalloc((void**)&guideParams_, flat.size() * 4), "guide params");
+    detail::HipOk(hipMemcpy(guideParams_, flat.data(), flat.size() * 4, hipMemcpyHostToDevice), "guide params");
+    RLGC::RlgpuCheck(rlgpu_learner_set_guide(h_, guideParams_, config.ppo.guidingStrength), "guiding policy");
+    std::printf("\tGuiding policy: %s (strength %g)\n", d.string().c_str(), (double)config.ppo.guidingStrength);
 }
 
 inline Learner::~Learner() {
@@ -842,6 +879,7 @@ inline Learner::~Learner() {
     delete versionMgr;
     delete envSet;
     if (h_) rlgpu_learner_destroy(h_);
+    if (guideParams_) (void)hipFree(guideParams_);
     if (stream_ && !options.stream) (void)hipStreamDestroy(stream_);
 }
 
@@ -940,6 +978,7 @@ inline int64_t Learner::Iterate(Report& report) {
         report["Policy Entropy"] = m[RLGPU_M_ENTROPY] / cnt;
         report["Mean KL Divergence"] = m[RLGPU_M_KL] / cnt;
         report["Policy Loss"] = m[RLGPU_M_POLICY_LOSS] / cnt;
+        if (config.ppo.useGuidingPolicy) report["Guiding Loss"] = m[RLGPU_M_GUIDING_LOSS] / cnt;
         report["Critic Loss"] = m[RLGPU_M_CRITIC_LOSS] / cnt;
         report["SB3 Clip Fraction"] = m[RLGPU_M_CLIP_FRACTION] / cnt;
     }

@@ -22,6 +22,7 @@
 //   rlgpu_train [--iterations N] [--arenas A] [--rollout T] [--trajectories] [--f32-gemm] [--c2-model] [--seed S]
 //               [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] [--self-play] [--fp32-inference]
 //               [--policy-temperature X] [--mask-entropy] [--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm]
+//               [--guiding-policy DIR [--guiding-strength X]]
 //               [--rank r --world N --rccl-id FILE [--rccl-nonce STR]]
 #include <execinfo.h>
 #include <signal.h>
@@ -171,6 +172,10 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(argv[i], "--fp32-inference")) cfg.ppo.useHalfPrecision = false;
             else if (!std::strcmp(argv[i], "--policy-temperature")) cfg.ppo.policyTemperature = std::strtof(next(), nullptr);
             else if (!std::strcmp(argv[i], "--mask-entropy")) cfg.ppo.maskEntropy = true;
+            else if (!std::strcmp(argv[i], "--guiding-policy")) {  // PPOLearnerConfig::useGuidingPolicy / guidingPolicyPath
+                cfg.ppo.useGuidingPolicy = true;
+                cfg.ppo.guidingPolicyPath = next();
+            } else if (!std::strcmp(argv[i], "--guiding-strength")) cfg.ppo.guidingStrength = std::strtof(next(), nullptr);
             else if (!std::strcmp(argv[i], "--activation")) {  // ModelConfig::activationType of every model
                 const std::string a = next();
                 ModelActivationType t;
@@ -197,7 +202,8 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "%s\nusage: %s [--iterations N] [--arenas A] [--rollout T] [--trajectories] [--f32-gemm] "
                                  "[--c2-model] [--seed S] [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] "
                                  "[--self-play] [--fp32-inference] [--policy-temperature X] [--mask-entropy] "
-                                 "[--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm] [--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);
+                                 "[--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm] [--guiding-policy DIR "
+                                 "[--guiding-strength X]] [--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);
             return 2;
         }
     }
@@ -245,6 +251,7 @@ int main(int argc, char** argv) {
                                 (long long)it + 1, report["Collected Timesteps"] / t, envSteps / t, report["Collection Time"],
                                 report["Consumption Time"] - report["PPO Learn Time"], report["PPO Learn Time"],
                                 (unsigned long long)learner.totalTimesteps);
+                    if (cfg.ppo.useGuidingPolicy) std::printf("  Guiding Loss: %.6g\n", report["Guiding Loss"]);
                     // the StepCallback's report (ExampleMain.cpp:233-283) over this iteration, from the device
                     double tot[RLGPU_NUM_STEP_METRICS];
                     uint64_t cnt[RLGPU_NUM_STEP_METRICS];

@@ -186,9 +186,10 @@ void PPOLearnerGPU::AdvantageStats(const float* d_adv, int64_t n) {
 }
 void PPOLearnerGPU::Minibatch(const float* d_obs, const uint8_t* d_masks, const int32_t* d_actions, const float* d_logp,
                               const float* d_adv, const float* d_target, const int32_t* d_index, int64_t start, int n,
-                              int64_t batch) {
-    RlgpuCheck(rlgpu_ppo_minibatch(h_, d_obs, d_masks, d_actions, d_logp, d_adv, d_target, d_index, start, n, batch,
-                                   adv_stats_, metrics_, stream_),
+                              int64_t batch, const uint16_t* d_guide_logits, float guiding_strength) {
+    // a null guide is rlgpu_ppo_minibatch itself
+    RlgpuCheck(rlgpu_ppo_minibatch_guided(h_, d_obs, d_masks, d_actions, d_logp, d_adv, d_target, d_index, start, n, batch,
+                                          adv_stats_, d_guide_logits, guiding_strength, metrics_, stream_),
                "Learn minibatch");
     minibatches++;
 }
@@ -769,6 +770,26 @@ void Learner::ReserveLearnRows(int64_t M) {
     permCap_ = cap;
 }
 
+// the guide-logit buffer for `rows` rows (T * P in the rollout mode, set once; the trajectory mode's combined batch
+// grows it like the learn scratch)
+void Learner::ReserveGuideRows(int64_t rows) {
+    if (rows <= guideCap_) return;
+    const int64_t cap = std::max<int64_t>(rows, guideCap_ + guideCap_ / 2);
+    hipCheck(hipStreamSynchronize(s_), "sync");
+    if (guideLogits_) Release(guideLogits_);
+    guideLogits_ = Alloc<uint16_t>((size_t)cap * ACT);
+    guideCap_ = cap;
+}
+
+void Learner::SetGuide(const float* d_policy_params, float strength) {
+    RLGPU_REQUIRE(d_policy_params, "Learner::SetGuide: null parameters");
+    RLGPU_REQUIRE(std::isfinite(strength) && strength >= 0.f, "Learner::SetGuide: guiding_strength must be finite and >= 0");
+    RlgpuCheck(rlgpu_ppo_set_guide(ppo_->handle(), d_policy_params, s_), "set guide");
+    if (!trajMode()) ReserveGuideRows((int64_t)exp_.T * exp_.P);
+    guideStrength_ = strength;
+    hasGuide_ = true;
+}
+
 void Learner::Learn() {
     const int T = exp_.T, P = exp_.P;
     rlgpu_rollout_view v = exp_.v;
@@ -807,6 +828,16 @@ void Learner::Learn() {
         if (trajRanges.empty()) trajRanges.emplace_back(0, 0);
     }
     if (rows) lk::train_rows(T, P, 1 - oldTeam_, trainRows_, s_);
+    // the guide's logits of every row the minibatches can address, once: the guide and the obs are frozen during
+    // Learn, so the reference's per-minibatch guide forward (PPOLearner.cpp:458-462) computes these same numbers
+    const uint16_t* guide = nullptr;
+    if (hasGuide_) {
+        guideRows_ = trajMode() ? M : (int64_t)T * P;
+        ReserveGuideRows(guideRows_);
+        if (guideRows_ > 0)
+            RlgpuCheck(rlgpu_ppo_infer_guide_logits(ppo_->handle(), v.obs, guideRows_, guideLogits_, s_), "guide logits");
+        guide = guideLogits_;
+    }
     for (int epoch = 0; epoch < cfg_.epochs; epoch++) {
         NeedLearnRows(M, "the shuffle");
         RlgpuCheck(rlgpu_permutation(M, cfg_.seed + (uint64_t)cfg_.rank, (uint64_t)(stats.iteration * cfg_.epochs + epoch),
@@ -826,7 +857,7 @@ void Learner::Learn() {
             BatchAdvantageStats(v.adv, whole ? nullptr : order + b0, b1 - b0);
             for (int64_t s0 = b0; s0 < b1; s0 += cfg_.mini_batch_size) {
                 const int n = (int)std::min<int64_t>(cfg_.mini_batch_size, b1 - s0);
-                ppo_->Minibatch(v.obs, v.masks, v.actions, v.logp, v.adv, v.target, order, s0, n, batch);
+                ppo_->Minibatch(v.obs, v.masks, v.actions, v.logp, v.adv, v.target, order, s0, n, batch, guide, guideStrength_);
             }
             AllReduceGrads(epoch, bi++);  // RCCL over xGMI (via the collective), before clip_grad_norm_
             ppo_->OptimizerStep();
@@ -1137,6 +1168,20 @@ extern "C" int rlgpu_learner_set_old_team(rlgpu_learner* h, int32_t team) {
         h->L->SetOldTeam(team);
     });
 }
+extern "C" int rlgpu_learner_set_guide(rlgpu_learner* h, const float* d_policy_params, float guiding_strength) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h, "null learner");
+        h->L->SetGuide(d_policy_params, guiding_strength);
+    });
+}
+extern "C" int rlgpu_learner_guide_logits(rlgpu_learner* h, const uint16_t** d_logits, int64_t* rows) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && d_logits && rows, "rlgpu_learner_guide_logits: null argument");
+        *d_logits = h->L->guideLogits();
+        *rows = h->L->guideRows();
+    });
+}
+
 extern "C" int rlgpu_learner_get_stats(rlgpu_learner* h, rlgpu_learner_stats* out) {
     return rlgpu::guarded([&] {
         RLGPU_LEARNER(h);

@@ -141,7 +141,7 @@ public:
     void AdvantageStats(const float* d_adv, int64_t n);  // (mean, unbiased std) -> adv_stats
     void Minibatch(const float* d_obs, const uint8_t* d_masks, const int32_t* d_actions, const float* d_logp,
                    const float* d_adv, const float* d_target, const int32_t* d_index, int64_t start, int n,
-                   int64_t batch);
+                   int64_t batch, const uint16_t* d_guide_logits = nullptr, float guiding_strength = 0.f);
     void OptimizerStep();
     int64_t minibatches = 0;  // summed into metrics() since the last reset
 
@@ -176,6 +176,11 @@ public:
     void Start(int64_t iterations);  // Learner::Start loop (Learner.cpp:482-1056), a fixed count
 
     void SetOldTeam(int team) { oldTeam_ = team; }
+    // PPOLearnerConfig::useGuidingPolicy: the guide's flat fp32 parameters (rlgpu_ppo_set_guide's layout) and
+    // guidingStrength; every later Learn adds the guiding term
+    void SetGuide(const float* d_policy_params, float strength);
+    const uint16_t* guideLogits() const { return guideLogits_; }
+    int64_t guideRows() const { return guideRows_; }
     void SetGradHook(rlgpu_grad_hook_fn fn, void* user) {
         gradHook_ = fn;
         gradHookUser_ = user;
@@ -242,6 +247,13 @@ private:
     int32_t* permRows_ = nullptr; // permCap_ rows each (T * P; grown to the combined batch in the
     float* badv_ = nullptr;       // trajectory mode, whose row count has no fixed bound)
     int64_t permCap_ = 0;
+    // the guiding policy's 16-bit logits of the rows Learn trains on ([T * P][ACT], or the combined batch's rows in
+    // the trajectory mode), written once per Learn before the epoch loop; null without a guide
+    uint16_t* guideLogits_ = nullptr;
+    int64_t guideCap_ = 0, guideRows_ = 0;
+    float guideStrength_ = 0.f;
+    bool hasGuide_ = false;
+    void ReserveGuideRows(int64_t rows);
     void NeedLearnRows(int64_t n, const char* what) const;
     void ReserveLearnRows(int64_t M);
     int32_t* truncRows_ = nullptr;

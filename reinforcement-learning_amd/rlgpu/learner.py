@@ -159,6 +159,29 @@ def sync_from_rank0(learner, group=None, error=None):
                 learner.versions.add_version(int(ts[k]), t)
 
 
+def load_guiding_policy(ppo, folder):
+    """The guiding policy's flat parameters from <folder>/POLICY.lt (and SHARED_HEAD.lt when ppo has a shared head),
+    in parameters() order, on ppo's device.  A missing file or a model of another size is an error naming the file
+    (the reference loads the guide with allowNotExist = false)."""
+    import os
+    import torch
+    from . import checkpoint as _ckpt
+    parts = []
+    for mi in ppo.models:
+        if mi == 1:
+            continue
+        p = _ckpt.model_path(folder, _ckpt.MODEL_NAMES[mi])
+        if not os.path.exists(p):
+            raise FileNotFoundError(f"guiding policy: {p} does not exist")
+        tensors = _ckpt.read_model_state(p)
+        want, got = ppo.model_sizes(mi), [t.numel() for t in tensors]
+        if got != want:
+            raise ValueError(f"guiding policy: {p} has different sizes than the current model:\n"
+                             f" > Current model: {want},\n > Saved model:   {got}")
+        parts += [t.reshape(-1) for t in tensors]
+    return torch.cat(parts).to(ppo.device)
+
+
 # ------------------------------------------------------------------ config
 class LearnerConfig:
     """The subset of GGL::LearnerConfig / PPOLearnerConfig on the hot path (ExampleMain values)."""
@@ -204,6 +227,11 @@ class LearnerConfig:
         self.collect_groups = 0           # rollout collection in arena groups on their own streams and CU partitions
                                           # (0 = automatic: 2 groups from 4096 arenas on; 1 = one launch per step;
                                           # -1 = the collection loop, the whole rollout in one launch, where eligible)
+        # PPOLearnerConfig::useGuidingPolicy / guidingPolicyPath / guidingStrength: every minibatch's loss gains
+        # guiding_strength * mean |guide probs - probs|, the guide read from <path>/POLICY.lt (+ SHARED_HEAD.lt)
+        self.use_guiding_policy = False
+        self.guiding_policy_path = "guiding_policy/"
+        self.guiding_strength = 0.03
         # checkpoints (LearnerConfig.h:31-38): None = no save / load
         self.checkpoint_folder = None
         self.ts_per_save = 10_000_000     # 0 = every iteration (Learner.cpp:44-45)
@@ -295,6 +323,8 @@ def _bind():
     L.rlgpu_learner_metrics.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]
     L.rlgpu_learner_set_env_timing.argtypes = [vp, ctypes.c_int32]
     L.rlgpu_learner_step_metrics.argtypes = [vp, vp, vp, ctypes.c_int32]
+    L.rlgpu_learner_set_guide.argtypes = [vp, vp, ctypes.c_float]
+    L.rlgpu_learner_guide_logits.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64)]
     return L
 
 
@@ -397,7 +427,7 @@ class Learner:
         self.ppo = PPO.wrap(ph.value, self.device, cfg.policy_layers, cfg.critic_layers, max_rows,
                             obs_size=OBS * max(1, cfg.frame_stack), metrics_source=self._metrics, owner=self,
                             shared_layers=cfg.shared_layers, layer_norm=bool(cfg.layer_norm), activation=cfg.activation,
-                            leaky_slope=0.0 if cfg.activation == "relu" else 0.01,
+                            leaky_slope=0.0 if cfg.activation == "relu" else 0.01, infer_fp16=int(cfg.infer_fp16),
                             optim_options={"lr": (cfg.policy_lr, cfg.critic_lr, min(cfg.policy_lr, cfg.critic_lr)),
                                            "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 1e-2})
         r = _CRollout()
@@ -437,6 +467,8 @@ class Learner:
             from .versions import PolicyVersionManager
             vf = os.path.join(cfg.checkpoint_folder, "policy_versions") if cfg.checkpoint_folder else None
             self.versions = PolicyVersionManager(self.ppo, vf, cfg.max_old_versions, cfg.ts_per_version, self.skill)
+        if cfg.use_guiding_policy:  # PPOLearner ctor (PPOLearner.cpp:35-38): the files must exist
+            self.set_guide(load_guiding_policy(self.ppo, cfg.guiding_policy_path), cfg.guiding_strength)
         self.last_checkpoint = None
         if cfg.checkpoint_folder:  # Learner ctor: load the most recent checkpoint (Learner.cpp:145-153)
             from . import checkpoint as _ckpt
@@ -555,6 +587,26 @@ class Learner:
         self._ghook = self._GRAD_HOOK(thunk)
         L.rlgpu_learner_set_grad_hook.argtypes = [ctypes.c_void_p, self._GRAD_HOOK, ctypes.c_void_p]
         _lib.check(L.rlgpu_learner_set_grad_hook(self._h, self._ghook, None), "rlgpu_learner_set_grad_hook")
+
+    def set_guide(self, params, strength):
+        """rlgpu_learner_set_guide: the guiding policy's flat fp32 parameters (PPO.set_guide's layout, on the device)
+        and guidingStrength; every later learn phase adds the guiding term."""
+        cnt = sum(self.ppo.model_range(m)[1] for m in self.ppo.models if m != 1)
+        if params.numel() != cnt:
+            raise _lib.RLGPUError("guiding policy has the wrong parameter count")
+        self._guide_params = params.to(self.device).float().contiguous()
+        _lib.check(_lib.lib().rlgpu_learner_set_guide(self._h, _lib.ptr(self._guide_params), float(strength)),
+                   "rlgpu_learner_set_guide")
+        self.ppo._guided = True
+
+    def guide_logits_view(self):
+        """The last learn phase's guide logits [rows, ACTIONS] (16-bit inference format), or None before the first."""
+        p, n = ctypes.c_void_p(), ctypes.c_int64()
+        _lib.check(_lib.lib().rlgpu_learner_guide_logits(self._h, ctypes.byref(p), ctypes.byref(n)), "rlgpu_learner_guide_logits")
+        if not p.value or n.value == 0:
+            return None
+        import torch
+        return _lib.alias(p.value, (n.value, 2 * ACTIONS), torch.uint8, self.device).view(self.ppo.logit_dtype)
 
     def set_env_timing(self, on=True):
         _lib.check(_lib.lib().rlgpu_learner_set_env_timing(self._h, int(on)), "rlgpu_learner_set_env_timing")

@@ -20,7 +20,8 @@ from ._lib import alias
 MAX_LAYERS = 8
 NUM_METRICS = 16
 METRICS = ("entropy", "kl", "policy_loss", "critic_loss", "ratio", "clip_fraction", "count",
-           "grad_norm_policy", "grad_norm_critic", "grad_norm_shared")
+           "grad_norm_policy", "grad_norm_critic", "grad_norm_shared", "guiding_loss")
+M_GUIDING_LOSS = 10  # RLGPU_M_GUIDING_LOSS
 MODEL_NAMES = ("policy", "critic", "shared_head")  # GGL::Model::modelName (PPOLearner.cpp:66-72)
 
 
@@ -71,6 +72,9 @@ def _bind():
     L.rlgpu_ppo_infer_critic.argtypes = [vp, vp, i64, vp, vp]
     L.rlgpu_mean_std.argtypes = [vp, i64, vp, vp]
     L.rlgpu_ppo_minibatch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp, vp]
+    L.rlgpu_ppo_minibatch_guided.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp, f32, vp, vp]
+    L.rlgpu_ppo_set_guide.argtypes = [vp, vp, vp]
+    L.rlgpu_ppo_infer_guide_logits.argtypes = [vp, vp, i64, vp, vp]
     L.rlgpu_ppo_optimizer_step.argtypes = [vp, vp, vp]
     L.rlgpu_ppo_zero_grad.argtypes = [vp, vp]
     L.rlgpu_ppo_optimizer_state.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp)]
@@ -84,7 +88,6 @@ def _bind():
     L.rlgpu_permutation.argtypes = [i64, u64, u64, vp, vp]
     L.rlgpu_kernel_timing.argtypes = [i32]
     L.rlgpu_kernel_timing_read.argtypes = [vp, vp, vp, i32]
-    _ = f32
     _bound = True
     return L
 
@@ -136,7 +139,7 @@ class PPO:
         c.clip_range, c.entropy_scale, c.max_grad_norm = clip_range, entropy_scale, max_grad_norm
         c.max_rows, c.seed = max_rows, seed
         c.train_gemm = train_gemm
-        c.infer_fp16 = int(infer_fp16)
+        c.infer_fp16 = self.infer_fp16 = int(infer_fp16)
         c.policy_temperature, c.mask_entropy = policy_temperature, int(mask_entropy)
         h = ctypes.c_void_p()
         _lib.check(L.rlgpu_ppo_create(ctypes.byref(c), ctypes.byref(h)), "rlgpu_ppo_create")
@@ -162,7 +165,7 @@ class PPO:
     @classmethod
     def wrap(cls, handle, device, policy_layers, critic_layers, max_rows, obs_size=167, num_actions=90,
              layer_norm=True, leaky_slope=0.01, metrics_source=None, owner=None, shared_layers=(), optim_options=None,
-             activation="leaky_relu"):
+             activation="leaky_relu", infer_fp16=False):
         """A PPO view of a handle owned elsewhere (the C++ Learner's PPOLearner): not destroyed
         by this object.  metrics_source(reset) -> (sums, count) replaces the own metric buffer."""
         import torch
@@ -174,6 +177,7 @@ class PPO:
         self.policy_layers, self.critic_layers, self.layer_norm = tuple(policy_layers), tuple(critic_layers), layer_norm
         self.shared_layers = tuple(shared_layers)
         self.leaky_slope, self.max_rows = leaky_slope, max_rows
+        self.infer_fp16 = int(infer_fp16)
         activation_id(activation)
         self.activation = activation
         self.optim_options = optim_options
@@ -189,6 +193,8 @@ class PPO:
 
     _owned = True
     _metrics_source = None
+    _guided = False  # a guide was used since the metrics were last reset: read_metrics reports "Guiding Loss"
+    infer_fp16 = 0
     optim_options = None
 
     def close(self):
@@ -301,6 +307,31 @@ class PPO:
         _lib.check(_lib.lib().rlgpu_ppo_set_version(self._h, _lib.ptr(policy_params.contiguous()), _lib.stream_ptr()),
                    "rlgpu_ppo_set_version")
 
+    def set_guide(self, policy_params):
+        """The guiding policy (PPOLearnerConfig::useGuidingPolicy): a frozen 16-bit copy of a policy given as
+        set_version takes one (flat fp32 parameters on the device: the policy's, then the shared head's)."""
+        cnt = sum(self.model_range(m)[1] for m in self.models if m != 1)
+        if policy_params.numel() != cnt:
+            raise _lib.RLGPUError("guiding policy has the wrong parameter count")
+        _lib.check(_lib.lib().rlgpu_ppo_set_guide(self._h, _lib.ptr(policy_params.contiguous()), _lib.stream_ptr()),
+                   "rlgpu_ppo_set_guide")
+
+    @property
+    def logit_dtype(self):
+        """torch dtype of the 16-bit inference format (guide logits)."""
+        import torch
+        return torch.float16 if self.infer_fp16 == 1 else torch.bfloat16
+
+    def guide_logits(self, obs, out=None):
+        """The guide's 16-bit inference forward over any number of rows: [n, num_actions] in the handle's 16-bit
+        format (the guide_logits of minibatch)."""
+        import torch
+        n = obs.shape[0]
+        out = torch.empty((n, self.num_actions), dtype=self.logit_dtype, device=self.device) if out is None else out
+        _lib.check(_lib.lib().rlgpu_ppo_infer_guide_logits(self._h, _lib.ptr(obs.contiguous()), n, _lib.ptr(out),
+                                                           _lib.stream_ptr()), "rlgpu_ppo_infer_guide_logits")
+        return out
+
     def infer_actions_mixed(self, obs, masks, old_rows, step=0, deterministic=False, actions=None, logp=None):
         """Rows with old_rows != 0 act with the version of set_version (their logp is not written)."""
         import torch
@@ -358,11 +389,34 @@ class PPO:
                    "rlgpu_mean_std")
         return self.adv_stats
 
-    def minibatch(self, obs, masks, actions, old_logp, adv, target, index, start, n, batch_size):
-        _lib.check(_lib.lib().rlgpu_ppo_minibatch(
+    def minibatch(self, obs, masks, actions, old_logp, adv, target, index, start, n, batch_size, guide_logits=None,
+                  guiding_strength=0.0):
+        """guide_logits (16-bit, the handle's inference format, one row of num_actions per row of the batch, addressed
+        like masks): adds guiding_strength * mean |guide probs - probs| to the loss (rlgpu_ppo_minibatch_guided)."""
+        if guide_logits is None:
+            _lib.check(_lib.lib().rlgpu_ppo_minibatch(
+                self._h, _lib.ptr(obs), _lib.ptr(masks), _lib.ptr(actions), _lib.ptr(old_logp), _lib.ptr(adv),
+                _lib.ptr(target), _lib.ptr(index), start, n, batch_size, _lib.ptr(self.adv_stats), _lib.ptr(self.metrics),
+                _lib.stream_ptr()), "rlgpu_ppo_minibatch")
+        else:
+            self.minibatch_guided(obs, masks, actions, old_logp, adv, target, index, start, n, batch_size, guide_logits,
+                                  guiding_strength)
+            return
+        self._count += 1
+
+    def minibatch_guided(self, obs, masks, actions, old_logp, adv, target, index, start, n, batch_size, guide_logits,
+                         guiding_strength):
+        """rlgpu_ppo_minibatch_guided; guide_logits None is the unguided minibatch through the same entry point."""
+        if guide_logits is not None:
+            if guide_logits.element_size() != 2 or guide_logits.shape[-1] != self.num_actions or \
+                    guide_logits.shape[0] != masks.shape[0] or not guide_logits.is_contiguous():
+                raise _lib.RLGPUError("guide_logits must be contiguous 16-bit [rows of masks, num_actions]")
+            self._guided = True
+        _lib.check(_lib.lib().rlgpu_ppo_minibatch_guided(
             self._h, _lib.ptr(obs), _lib.ptr(masks), _lib.ptr(actions), _lib.ptr(old_logp), _lib.ptr(adv),
-            _lib.ptr(target), _lib.ptr(index), start, n, batch_size, _lib.ptr(self.adv_stats), _lib.ptr(self.metrics),
-            _lib.stream_ptr()), "rlgpu_ppo_minibatch")
+            _lib.ptr(target), _lib.ptr(index), start, n, batch_size, _lib.ptr(self.adv_stats),
+            _lib.ptr(guide_logits) if guide_logits is not None else None, guiding_strength, _lib.ptr(self.metrics),
+            _lib.stream_ptr()), "rlgpu_ppo_minibatch_guided")
         self._count += 1
 
     _count = 0
@@ -379,17 +433,23 @@ class PPO:
         if self._metrics_source is not None:
             m, cnt = self._metrics_source(reset)
             cnt = max(cnt, 1)
-            return {"Policy Entropy": m[0] / cnt, "Mean KL Divergence": m[1] / cnt, "Policy Loss": m[2] / cnt,
-                    "Critic Loss": m[3] / cnt, "Ratio": m[4] / cnt, "SB3 Clip Fraction": m[5] / cnt,
-                    "Policy Grad Norm": m[7], "Critic Grad Norm": m[8], "Shared Head Grad Norm": m[9]}
+            rep = {"Policy Entropy": m[0] / cnt, "Mean KL Divergence": m[1] / cnt, "Policy Loss": m[2] / cnt,
+                   "Critic Loss": m[3] / cnt, "Ratio": m[4] / cnt, "SB3 Clip Fraction": m[5] / cnt,
+                   "Policy Grad Norm": m[7], "Critic Grad Norm": m[8], "Shared Head Grad Norm": m[9]}
+            if self._guided:
+                rep["Guiding Loss"] = m[M_GUIDING_LOSS] / cnt
+            return rep
         m = self.metrics.cpu().tolist()
         cnt = max(self._count, 1)
         rep = {"Policy Entropy": m[0] / cnt, "Mean KL Divergence": m[1] / cnt, "Policy Loss": m[2] / cnt,
                "Critic Loss": m[3] / cnt, "Ratio": m[4] / cnt, "SB3 Clip Fraction": m[5] / cnt,
                "Policy Grad Norm": m[7], "Critic Grad Norm": m[8], "Shared Head Grad Norm": m[9]}
+        if self._guided:
+            rep["Guiding Loss"] = m[M_GUIDING_LOSS] / cnt
         if reset:
             self.metrics.zero_()
             self._count = 0
+            self._guided = False
         return rep
 
     def optimizer_state(self):

@@ -5,8 +5,9 @@ without the env.  Prints ms per minibatch (HIP events); run under rocprofv3 --ke
 for per-kernel durations.
 
 usage: python tools/learn_bench.py [minibatches=24] [train_gemm=h3|x6|f32] [width=512] [depth=2]
-       [activation=leaky_relu|relu|sigmoid|tanh]
-(width 2048, depth 4 = the C5 leg's model)
+       [activation=leaky_relu|relu|sigmoid|tanh] [guide=0|1]
+(width 2048, depth 4 = the C5 leg's model; guide 1: every minibatch carries the guiding term (rlgpu_ppo_minibatch_guided,
+strength 0.03) on the logits of a guide of another seed, and the guide pass over 128 x 16,384 rows is timed too)
 """
 import os
 import sys
@@ -37,13 +38,32 @@ activation = sys.argv[5] if len(sys.argv) > 5 else "leaky_relu"
 p = PPO(max_rows=MB, seed=123, train_gemm=mode, policy_layers=layers, critic_layers=layers, activation=activation)
 p.adv_normalizer(adv)
 idx = permutation(N, 7, 0)
+guide = len(sys.argv) > 6 and sys.argv[6] == "1"
+glog, gkw = None, {}
+if guide:
+    q = PPO(max_rows=64, seed=321, policy_layers=layers, critic_layers=layers, activation=activation)
+    p.set_guide(q.policy_version())
+    q.close()
+    glog = p.guide_logits(obs)
+    gkw = dict(guide_logits=glog, guiding_strength=0.03)
+    # the learn phase's guide pass at C2: the rows of one rollout (128 steps x 16,384 players), in chunks of the buffer
+    rows, out = 128 * 16384, torch.empty((N, 90), dtype=glog.dtype, device=dev)
+    for _ in range(2):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for b in range(0, rows, N):
+            n = min(N, rows - b)
+            p.guide_logits(obs[:n], out=out[:n])
+        t1.record()
+        torch.cuda.synchronize()
+        print(f"guide pass over {rows} rows: {t0.elapsed_time(t1):.3f} ms", flush=True)
 
 
 def run(k):
     for i in range(k):
         if i % (N // MB) == 0:
             p.zero_grad()
-        p.minibatch(obs, masks, acts, old, adv, tgt, idx, (i % (N // MB)) * MB, MB, MB)
+        p.minibatch(obs, masks, acts, old, adv, tgt, idx, (i % (N // MB)) * MB, MB, MB, **gkw)
         if i % (N // MB) == N // MB - 1:
             p.optimizer_step()
 
@@ -56,7 +76,7 @@ run(nmb)
 e1.record()
 torch.cuda.synchronize()
 print(f"learn_bench {layers}: {e0.elapsed_time(e1) / nmb:.3f} ms per 50k minibatch (+ optimizer step every {N // MB}), "
-      f"mode {sys.argv[2] if len(sys.argv) > 2 else 'h3'}, {activation}, {nmb} minibatches", flush=True)
+      f"mode {sys.argv[2] if len(sys.argv) > 2 else 'h3'}, {activation}, {'guided, ' if guide else ''}{nmb} minibatches", flush=True)
 print("metrics finite:", bool(np.isfinite(p.metrics.cpu().numpy()).all()))
 kernel_timing(True)
 run(8)
