@@ -37,6 +37,12 @@ int rlgpu_abi_version(void);
 /* Number of visible HIP devices (0 if no GPU); never fails. */
 int rlgpu_device_count(void);
 
+/* Diagnostics: the persistent device allocations this process holds through the library right now -- the buffers
+ * of its env sets, PPO handles and host Learners (not the stream-ordered temporaries of a single call, nor the
+ * per-device scratch created once and kept).  Exact per process, which free device memory on a shared card is
+ * not: a handle that is created and destroyed, or whose creation fails, leaves the count where it was. */
+int64_t rlgpu_live_device_allocations(void);
+
 /* Compute-unit partitions (host/cu_partition.cpp): `groups` CU masks of `words` = 8 uint32 each (bit k of a mask
  * is bit k % 32 of word k / 32), pairwise disjoint, covering every CU, each with the same number of CUs in every
  * XCD under either plausible bit-to-CU mapping.  Host only.  RLGPU_ERR_UNSUPPORTED for a cu_count other than 256

@@ -51,6 +51,13 @@ inline int guarded(F&& f) {
     }
 }
 
+// The one place that allocates and frees persistent device memory (the env set's, the PPO handle's and the host
+// Learner's buffers): hipMalloc / hipFree, counted for rlgpu_live_device_allocations.  dev_alloc throws an Error
+// on failure; dev_free takes null.  Stream-ordered temporaries of a single call and per-device static scratch are
+// not persistent in this sense and stay outside.
+void* dev_alloc(size_t bytes);
+void dev_free(void* p);
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline unsigned ceil_div(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }

@@ -238,7 +238,7 @@ struct rlgpu_envset {
     template <class T>
     T* alloc(size_t count) {
         allocs.push_back(nullptr);  // the slot first: a buffer never exists outside the list
-        RLGPU_CHECK_HIP(hipMalloc(&allocs.back(), count * sizeof(T)));
+        allocs.back() = rlgpu::dev_alloc(count * sizeof(T));
         return (T*)allocs.back();
     }
     template <class T>
@@ -385,7 +385,7 @@ void device_init(int arith) {
     if (rsqrt) {
         int bits = 0;
         const std::vector<uint32_t>& t = rlgpu::x86_rsqrt_table_or_throw(&bits);
-        uint32_t* d = nullptr;
+        uint32_t* d = nullptr;  // per-device static, kept for the process: no set owns it, so no rlgpu::dev_alloc
         RLGPU_CHECK_HIP(hipMalloc(&d, t.size() * sizeof(uint32_t)));
         RLGPU_CHECK_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         L = rl::RsqrtLut{d, bits};
@@ -520,9 +520,9 @@ void download_metric_slots(const rlgpu_envset* e, double* h_out, hipStream_t s) 
 }
 
 void free_set(rlgpu_envset* e) {
-    for (void* p : e->allocs) (void)hipFree(p);
-    (void)hipFree(e->d_metrics);
-    (void)hipFree(e->d_reward_values);
+    for (void* p : e->allocs) rlgpu::dev_free(p);
+    rlgpu::dev_free(e->d_metrics);
+    rlgpu::dev_free(e->d_reward_values);
     delete e;
 }
 
@@ -646,10 +646,10 @@ extern "C" int rlgpu_envset_enable_step_metrics(rlgpu_envset* e, int32_t enable)
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e, "null envset");
         const size_t bytes = (size_t)e->cfg.num_arenas * RLGPU_STEP_METRIC_SLOTS * sizeof(double);
-        if (enable && !e->d_metrics) RLGPU_CHECK_HIP(hipMalloc(&e->d_metrics, bytes));
+        if (enable && !e->d_metrics) e->d_metrics = (double*)rlgpu::dev_alloc(bytes);
         if (!enable && e->d_metrics) {
             RLGPU_CHECK_HIP(hipDeviceSynchronize());
-            (void)hipFree(e->d_metrics);
+            rlgpu::dev_free(e->d_metrics);
             e->d_metrics = nullptr;
         }
         if (enable) RLGPU_CHECK_HIP(hipMemset(e->d_metrics, 0, bytes));
@@ -703,11 +703,11 @@ extern "C" int rlgpu_envset_enable_reward_values(rlgpu_envset* e, int32_t enable
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e, "null envset");
         RLGPU_CHECK_HIP(hipDeviceSynchronize());
-        if (e->d_reward_values) (void)hipFree(e->d_reward_values);
+        rlgpu::dev_free(e->d_reward_values);
         e->d_reward_values = nullptr;
         if (enable) {
             const size_t n = (size_t)e->num_players * std::max(e->plug.nr, 1);
-            RLGPU_CHECK_HIP(hipMalloc(&e->d_reward_values, n * sizeof(float)));
+            e->d_reward_values = (float*)rlgpu::dev_alloc(n * sizeof(float));
             RLGPU_CHECK_HIP(hipMemset(e->d_reward_values, 0, n * sizeof(float)));
         }
     });

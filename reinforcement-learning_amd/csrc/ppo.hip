@@ -194,10 +194,9 @@ struct rlgpu_ppo {
 
     template <class T>
     T* alloc(size_t count) {
-        void* p = nullptr;
-        RLGPU_CHECK_HIP(hipMalloc(&p, count * sizeof(T) + 16));
-        allocs.push_back(p);
-        return (T*)p;
+        allocs.push_back(nullptr);  // the slot first: a buffer never exists outside the list
+        allocs.back() = rlgpu::dev_alloc(count * sizeof(T) + 16);
+        return (T*)allocs.back();
     }
 };
 
@@ -1140,7 +1139,7 @@ extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
             build_chains(h);
             *out = h;
         } catch (...) {
-            for (void* p : h->allocs) (void)hipFree(p);
+            for (void* p : h->allocs) rlgpu::dev_free(p);
             delete h;
             throw;
         }
@@ -1154,7 +1153,7 @@ extern "C" int rlgpu_ppo_destroy(rlgpu_ppo* h) {
         if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
         if (h->ev_join) (void)hipEventDestroy(h->ev_join);
         if (h->aux) (void)hipStreamDestroy(h->aux);
-        for (void* p : h->allocs) (void)hipFree(p);
+        for (void* p : h->allocs) rlgpu::dev_free(p);
         delete h;
     });
 }

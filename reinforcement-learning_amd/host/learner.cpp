@@ -39,24 +39,23 @@ inline uint64_t splitmix64(uint64_t x) {
 namespace RLGC {
 
 EnvSetGPU::EnvSetGPU(const rlgpu_envset_config& cfg, hipStream_t stream) : stream_(stream) {
-    RlgpuCheck(rlgpu_envset_create(&cfg, &h_), "EnvSet");
-    RlgpuCheck(rlgpu_envset_buffers_get(h_, &state_), "EnvSet buffers");
+    rlgpu_envset* h = nullptr;
+    RlgpuCheck(rlgpu_envset_create(&cfg, &h), "EnvSet");
+    h_.reset(h);
+    RlgpuCheck(rlgpu_envset_buffers_get(h, &state_), "EnvSet buffers");
 }
-EnvSetGPU::~EnvSetGPU() {
-    if (h_) rlgpu_envset_destroy(h_);
-}
-void EnvSetGPU::StepFirstHalf(bool) { RlgpuCheck(rlgpu_envset_step_first_half(h_, stream_), "StepFirstHalf"); }
+void EnvSetGPU::StepFirstHalf(bool) { RlgpuCheck(rlgpu_envset_step_first_half(handle(), stream_), "StepFirstHalf"); }
 void EnvSetGPU::StepSecondHalf(const int32_t* d_actions, bool async) {
-    RlgpuCheck(rlgpu_envset_step_second_half(h_, d_actions, stream_), "StepSecondHalf");
+    RlgpuCheck(rlgpu_envset_step_second_half(handle(), d_actions, stream_), "StepSecondHalf");
     if (!async) Sync();
 }
 void EnvSetGPU::Step(const int32_t* d_actions, const rlgpu_step_outputs* out) {
-    RlgpuCheck(rlgpu_envset_step(h_, d_actions, 1, out, stream_), "EnvSet step");
+    RlgpuCheck(rlgpu_envset_step(handle(), d_actions, 1, out, stream_), "EnvSet step");
 }
-void EnvSetGPU::Sync() { RlgpuCheck(rlgpu_envset_sync(h_, stream_), "Sync"); }
-void EnvSetGPU::Reset() { RlgpuCheck(rlgpu_envset_reset(h_, stream_), "Reset"); }
+void EnvSetGPU::Sync() { RlgpuCheck(rlgpu_envset_sync(handle(), stream_), "Sync"); }
+void EnvSetGPU::Reset() { RlgpuCheck(rlgpu_envset_reset(handle(), stream_), "Reset"); }
 void EnvSetGPU::ResetArenas(const uint8_t* d_mask) {
-    RlgpuCheck(rlgpu_envset_reset_arenas(h_, d_mask, stream_), "ResetArena");
+    RlgpuCheck(rlgpu_envset_reset_arenas(handle(), d_mask, stream_), "ResetArena");
 }
 
 }  // namespace RLGC
@@ -102,115 +101,92 @@ std::vector<std::pair<int64_t, int64_t>> BatchRanges(int64_t expSize, int64_t ba
 }
 
 template <class T>
-void DevArray<T>::Reserve(int64_t n, hipStream_t s, bool keep) {
+DevArray<T>::~DevArray() {
+    rlgpu::dev_free(p);
+}
+template <class T>
+void DevArray<T>::Reserve(int64_t n, hipStream_t s, bool keep, bool zero) {
     if (n <= cap) return;
     const int64_t ncap = std::max<int64_t>(n, cap + cap / 2);
-    T* q = nullptr;
-    hipCheck(hipMalloc((void**)&q, (size_t)ncap * sizeof(T) + 16), "DevArray alloc");
-    if (keep && p && cap > 0) hipCheck(hipMemcpyAsync(q, p, (size_t)cap * sizeof(T), hipMemcpyDeviceToDevice, s), "DevArray copy");
-    if (p) {
-        hipCheck(hipStreamSynchronize(s), "sync");
-        (void)hipFree(p);
+    const size_t bytes = (size_t)ncap * sizeof(T) + 16;  // the padding every Learner-side buffer carries
+    T* q = (T*)rlgpu::dev_alloc(bytes);
+    try {
+        if (zero) hipCheck(hipMemsetAsync(q, 0, bytes, s), "DevArray fill");
+        if (keep && p && cap > 0)
+            hipCheck(hipMemcpyAsync(q, p, (size_t)cap * sizeof(T), hipMemcpyDeviceToDevice, s), "DevArray copy");
+        if (p) hipCheck(hipStreamSynchronize(s), "sync");  // work queued on the old block, the copy included
+    } catch (...) {
+        rlgpu::dev_free(q);
+        throw;
     }
+    rlgpu::dev_free(p);
     p = q;
     cap = ncap;
 }
-template <class T>
-void DevArray<T>::Free() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-}
 
-void ExperienceBuffer::Allocate(int T_, int P_, int W_, bool rollout_outputs) {
+void PinnedFree::operator()(void* p) const { (void)hipHostFree(p); }
+
+void ExperienceBuffer::Allocate(int T_, int P_, int W_, hipStream_t s, bool rollout_outputs) {
     T = T_;
     P = P_;
     W = W_;
-    auto A = [&](size_t bytes) {
-        void* p = nullptr;
-        hipCheck(hipMalloc(&p, bytes + 16), "ExperienceBuffer alloc");
-        hipCheck(hipMemset(p, 0, bytes + 16), "ExperienceBuffer memset");
-        allocs.push_back(p);
-        return p;
+    const int64_t TP = (int64_t)T * P, T1P = (int64_t)(T + 1) * P;
+    const int64_t OP = rollout_outputs ? TP : (int64_t)P, O1P = rollout_outputs ? T1P : (int64_t)P;
+    auto Z = [&](auto& a, int64_t n) {
+        a.Reserve(n, s, false, true);
+        return a.p;
     };
-    const size_t TP = (size_t)T * P, T1P = (size_t)(T + 1) * P;
-    const size_t OP = rollout_outputs ? TP : (size_t)P, O1P = rollout_outputs ? T1P : (size_t)P;
-    v.obs = (float*)A(T1P * W * 4);
-    v.masks = (uint8_t*)A(T1P * ACT);
-    v.actions = (int32_t*)A(TP * 4);
-    v.logp = (float*)A(TP * 4);
-    v.rewards = (float*)A(TP * 4);
-    v.terms = (int8_t*)A(TP);
-    v.trunc_obs = (float*)A(OP * W * 4);
-    v.values = (float*)A(O1P * 4);
-    v.trunc_vals = (float*)A(OP * 4);
-    v.adv = (float*)A(OP * 4);
-    v.target = (float*)A(OP * 4);
-    v.ret = (float*)A(OP * 4);
+    v.obs = Z(obs, T1P * W);
+    v.masks = Z(masks, T1P * ACT);
+    v.actions = Z(actions, TP);
+    v.logp = Z(logp, TP);
+    v.rewards = Z(rewards, TP);
+    v.terms = Z(terms, TP);
+    v.trunc_obs = Z(truncObs, OP * W);
+    v.values = Z(values, O1P);
+    v.trunc_vals = Z(truncVals, OP);
+    v.adv = Z(adv, OP);
+    v.target = Z(target, OP);
+    v.ret = Z(ret, OP);
     v.T = T;
     v.P = P;
     v.obs_width = W;
 }
-void ExperienceBuffer::Free() {
-    for (void* p : allocs) (void)hipFree(p);
-    allocs.clear();
-}
 
 PPOLearnerGPU::PPOLearnerGPU(const rlgpu_ppo_config& cfg, hipStream_t stream) : stream_(stream) {
-    RlgpuCheck(rlgpu_ppo_create(&cfg, &h_), "PPOLearner");
+    rlgpu_ppo* h = nullptr;
+    RlgpuCheck(rlgpu_ppo_create(&cfg, &h), "PPOLearner");
+    h_.reset(h);
     float* params = nullptr;
-    RlgpuCheck(rlgpu_ppo_buffers(h_, &params, &grads_, &nparams_), "PPOLearner buffers");
-    hipCheck(hipMalloc((void**)&adv_stats_, 2 * sizeof(float)), "adv stats");
-    hipCheck(hipMalloc((void**)&metrics_, RLGPU_NUM_METRICS * sizeof(float)), "metrics");
-    hipCheck(hipMemset(metrics_, 0, RLGPU_NUM_METRICS * sizeof(float)), "metrics");
-    RlgpuCheck(rlgpu_ppo_init_params(h_, cfg.seed, stream_), "init params");
-}
-PPOLearnerGPU::~PPOLearnerGPU() {
-    if (adv_stats_) (void)hipFree(adv_stats_);
-    if (metrics_) (void)hipFree(metrics_);
-    if (h_) rlgpu_ppo_destroy(h_);
+    RlgpuCheck(rlgpu_ppo_buffers(h, &params, &grads_, &nparams_), "PPOLearner buffers");
+    adv_stats_.Reserve(2, stream_);
+    metrics_.Reserve(RLGPU_NUM_METRICS, stream_, false, true);
+    RlgpuCheck(rlgpu_ppo_init_params(h, cfg.seed, stream_), "init params");
 }
 void PPOLearnerGPU::InferActions(const float* d_obs, const uint8_t* d_masks, int n, bool det, uint64_t step,
                                  int32_t* d_actions, float* d_logp, const uint8_t* d_old_rows) {
     if (d_old_rows)
-        RlgpuCheck(rlgpu_ppo_infer_actions_mixed(h_, d_obs, d_masks, n, det, step, d_old_rows, d_actions, d_logp, stream_),
+        RlgpuCheck(rlgpu_ppo_infer_actions_mixed(handle(), d_obs, d_masks, n, det, step, d_old_rows, d_actions, d_logp, stream_),
                    "InferActions (old version)");
     else
-        RlgpuCheck(rlgpu_ppo_infer_actions(h_, d_obs, d_masks, n, det, step, d_actions, d_logp, stream_), "InferActions");
+        RlgpuCheck(rlgpu_ppo_infer_actions(handle(), d_obs, d_masks, n, det, step, d_actions, d_logp, stream_), "InferActions");
 }
 void PPOLearnerGPU::InferCritic(const float* d_obs, int64_t n, float* d_values) {
-    RlgpuCheck(rlgpu_ppo_infer_critic(h_, d_obs, n, d_values, stream_), "InferCritic");
+    RlgpuCheck(rlgpu_ppo_infer_critic(handle(), d_obs, n, d_values, stream_), "InferCritic");
 }
 void PPOLearnerGPU::AdvantageStats(const float* d_adv, int64_t n) {
-    RlgpuCheck(rlgpu_mean_std(d_adv, n, adv_stats_, stream_), "advantage stats");
+    RlgpuCheck(rlgpu_mean_std(d_adv, n, adv_stats_.p, stream_), "advantage stats");
 }
 void PPOLearnerGPU::Minibatch(const float* d_obs, const uint8_t* d_masks, const int32_t* d_actions, const float* d_logp,
                               const float* d_adv, const float* d_target, const int32_t* d_index, int64_t start, int n,
                               int64_t batch, const uint16_t* d_guide_logits, float guiding_strength) {
     // a null guide is rlgpu_ppo_minibatch itself
-    RlgpuCheck(rlgpu_ppo_minibatch_guided(h_, d_obs, d_masks, d_actions, d_logp, d_adv, d_target, d_index, start, n, batch,
-                                          adv_stats_, d_guide_logits, guiding_strength, metrics_, stream_),
+    RlgpuCheck(rlgpu_ppo_minibatch_guided(handle(), d_obs, d_masks, d_actions, d_logp, d_adv, d_target, d_index, start, n, batch,
+                                          adv_stats_.p, d_guide_logits, guiding_strength, metrics_.p, stream_),
                "Learn minibatch");
     minibatches++;
 }
-void PPOLearnerGPU::OptimizerStep() { RlgpuCheck(rlgpu_ppo_optimizer_step(h_, metrics_, stream_), "optimizer step"); }
-
-template <class T>
-T* Learner::Alloc(size_t count) {
-    void* p = nullptr;
-    hipCheck(hipMalloc(&p, count * sizeof(T) + 16), "Learner alloc");
-    allocs_.push_back(p);
-    return (T*)p;
-}
-void Learner::Release(void* p) {  // an Alloc'd buffer, freed before the destructor
-    for (auto& q : allocs_)
-        if (q == p) {
-            (void)hipFree(q);
-            q = allocs_.back();
-            allocs_.pop_back();
-            return;
-        }
-}
+void PPOLearnerGPU::OptimizerStep() { RlgpuCheck(rlgpu_ppo_optimizer_step(handle(), metrics_.p, stream_), "optimizer step"); }
 
 Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, hipStream_t stream)
     : s_(stream), cfg_(cfg) {
@@ -244,7 +220,7 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     ec.terminals = cfg.terminals;
     ec.n_terminals = cfg.n_terminals;
     ec.arith = cfg.arith;
-    env_ = new RLGC::EnvSetGPU(ec, s_);
+    env_ = std::make_unique<RLGC::EnvSetGPU>(ec, s_);
     // ExampleMain registers its StepCallback (ExampleMain.cpp:233-283, 592): restated on the device
     RlgpuCheck(rlgpu_envset_enable_step_metrics(env_->handle(), 1), "step metrics");
     // the rollout rows are the only obs / masks the Learner reads after a fused step (the stacked-frame and
@@ -289,7 +265,7 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     pc.infer_fp16 = cfg.infer_fp16;
     pc.policy_temperature = cfg.policy_temperature;  // validated by rlgpu_ppo_create (0 = 1)
     pc.mask_entropy = cfg.mask_entropy;
-    ppo_ = new PPOLearnerGPU(pc, s_);
+    ppo_ = std::make_unique<PPOLearnerGPU>(pc, s_);
     if (hasColl_) {  // identical initial weights on every rank: rank 0's (sum of zeros elsewhere)
         float* params = nullptr;
         float* g = nullptr;
@@ -312,27 +288,27 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
         J.Tmax = cfg.experience_capacity > 0 ? cfg.experience_capacity
                                               : (int)(J.maxLen + 2 * ((J.tsPerItr + perStep - 1) / perStep) + 64);
         RLGPU_REQUIRE(J.Tmax > J.maxLen + 1, "Learner: experience_capacity must exceed the max episode length + 1");
-        exp_.Allocate(J.Tmax, P, W, false);
-        J.start = Alloc<int32_t>(P);
-        J.len = Alloc<int32_t>(P);
-        J.trnew = Alloc<int32_t>(P);
-        J.counters = Alloc<int64_t>(lk::kTcCount);
-        hipCheck(hipMemset(J.start, 0, (size_t)P * 4), "traj start");
-        hipCheck(hipMemset(J.len, 0, (size_t)P * 4), "traj len");
-        hipCheck(hipHostMalloc((void**)&J.hcounters, lk::kTcCount * sizeof(int64_t)), "pinned counters");
-        if (K_ > 1) J.truncStage = Alloc<float>((size_t)P * W);
+        exp_.Allocate(J.Tmax, P, W, s_, false);
+        J.start.Reserve(P, s_, false, true);
+        J.len.Reserve(P, s_, false, true);
+        J.trnew.Reserve(P, s_);
+        J.counters.Reserve(lk::kTcCount, s_);
+        int64_t* hc = nullptr;
+        hipCheck(hipHostMalloc((void**)&hc, lk::kTcCount * sizeof(int64_t)), "pinned counters");
+        J.hcounters.reset(hc);
+        if (K_ > 1) J.truncStage.Reserve((int64_t)P * W, s_);
         const int64_t rc = 4 * (int64_t)P;
         for (auto* a : {&J.rp, &J.rstart, &J.rlen, &J.rcode, &J.rtidx}) a->Reserve(rc, s_);
         J.roff.Reserve(rc, s_);
         J.truncObs.Reserve(4 * (int64_t)P * W, s_);
     } else {
-        exp_.Allocate(T, P, W);
+        exp_.Allocate(T, P, W, s_);
     }
     // rollout row 0 = the env's initial obs (stacked: the first frame repeated) / masks
     const rlgpu_envset_buffers& st = env_->state();
     if (K_ > 1) {
-        hist_ = Alloc<float>((size_t)(K_ - 1) * P * OBS);
-        lk::stack_frames(st.obs, nullptr, nullptr, hist_, K_, P, OBS, exp_.v.obs, nullptr, s_);
+        hist_.Reserve((int64_t)(K_ - 1) * P * OBS, s_);
+        lk::stack_frames(st.obs, nullptr, nullptr, hist_.p, K_, P, OBS, exp_.v.obs, nullptr, s_);
     } else {
         hipCheck(hipMemcpyAsync(exp_.v.obs, st.obs, (size_t)P * OBS * 4, hipMemcpyDeviceToDevice, s_), "obs0");
     }
@@ -340,28 +316,28 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     // self-play team masks (team of player p is p % 2)
     std::vector<uint8_t> team(P);
     for (int k = 0; k < 2; k++) {
-        oldRows_[k] = Alloc<uint8_t>(P);
+        oldRows_[k].Reserve(P, s_);
         for (int p = 0; p < P; p++) team[p] = (uint8_t)(p % 2 == k);
-        hipCheck(hipMemcpy(oldRows_[k], team.data(), P, hipMemcpyHostToDevice), "old rows");
+        hipCheck(hipMemcpy(oldRows_[k].p, team.data(), P, hipMemcpyHostToDevice), "old rows");
     }
-    trainRows_ = Alloc<int32_t>((size_t)TP / 2 + 1);
-    perm_ = Alloc<int32_t>(TP);
-    permRows_ = Alloc<int32_t>(TP);
-    badv_ = Alloc<float>(TP);
-    permCap_ = TP;
-    truncRows_ = Alloc<int32_t>(TP);
-    truncCount_ = Alloc<int32_t>(1);
+    trainRows_.Reserve(TP / 2 + 1, s_);
+    perm_.Reserve(TP, s_);
+    permRows_.Reserve(TP, s_);
+    badv_.Reserve(TP, s_);
+    truncRows_.Reserve(TP, s_);
+    truncCount_.Reserve(1, s_);
     selBytes_ = lk::select_trunc_scratch_bytes(TP);
-    selScratch_ = Alloc<char>(selBytes_);
-    sampleIdx_ = Alloc<int64_t>((size_t)std::max(1, cfg.return_samples));
-    samples_ = Alloc<float>((size_t)std::max(1, cfg.return_samples));
-    ends_ = Alloc<int32_t>(P);
+    selScratch_.Reserve((int64_t)std::max<size_t>(selBytes_, 1), s_);
+    sampleIdx_.Reserve(std::max(1, cfg.return_samples), s_);
+    samples_.Reserve(std::max(1, cfg.return_samples), s_);
+    ends_.Reserve(P, s_);
     hostEnds_.assign(P, -1);
-    mom_ = (double*)Alloc<char>(4 * sizeof(double) + lk::moments_scratch_bytes());
-    clipSums_ = Alloc<float>(2);
+    mom_.Reserve(4 + (int64_t)(lk::moments_scratch_bytes() / sizeof(double)), s_);
+    clipSums_.Reserve(2, s_);
     hipCheck(hipStreamSynchronize(s_), "Learner init");
 }
 
+// The streams and events only; the members free themselves, the buffers before the env set and the PPO handle.
 Learner::~Learner() {
     if (s_) (void)hipStreamSynchronize(s_);
     for (auto s : gs_) {
@@ -371,20 +347,6 @@ Learner::~Learner() {
     for (auto e : gsEnd_) (void)hipEventDestroy(e);
     if (gsStart_) (void)hipEventDestroy(gsStart_);
     for (auto e : ev_) (void)hipEventDestroy(e);
-    for (void* p : allocs_) (void)hipFree(p);
-    if (truncObsC_) (void)hipFree(truncObsC_);
-    if (truncValC_) (void)hipFree(truncValC_);
-    if (traj.hcounters) (void)hipHostFree(traj.hcounters);
-    for (auto* a : {&traj.rp, &traj.rstart, &traj.rlen, &traj.rcode, &traj.rtidx, &traj.cActs}) a->Free();
-    traj.roff.Free();
-    for (auto* a : {&traj.truncObs, &traj.truncVals, &traj.cObs, &traj.cLogp, &traj.cRews, &traj.cVals, &traj.cAdv,
-                    &traj.cTarget, &traj.cRet})
-        a->Free();
-    traj.cMasks.Free();
-    traj.cTerms.Free();
-    exp_.Free();
-    delete ppo_;
-    delete env_;
 }
 
 // Arena groups for the rollout collection: a launch lasts as long as its slowest workgroup, so with the
@@ -558,7 +520,7 @@ void Learner::ActAndStep(size_t row, size_t next, float* trunc, float* truncStac
     if (timing) hipCheck(hipEventRecord(timing[0], s_), "event");
     StepEnv(v.actions + row, o);
     if (timing) hipCheck(hipEventRecord(timing[1], s_), "event");
-    if (K_ > 1) lk::stack_frames(st.obs, st.trunc_obs, v.terms + row, hist_, K_, P, OBS, v.obs + next * W, truncStacked, s_);
+    if (K_ > 1) lk::stack_frames(st.obs, st.trunc_obs, v.terms + row, hist_.p, K_, P, OBS, v.obs + next * W, truncStacked, s_);
 }
 
 // at least `count` timing events in ev_ (recreated when it grows)
@@ -608,21 +570,16 @@ void Learner::Consume() {
     const rlgpu_rollout_view& v = exp_.v;
     ppo_->InferCritic(v.obs, TP + P, v.values);  // InferCriticBatched over obs[0..T]
     // truncation values only where a trajectory was truncated (code 2): Learner.cpp:944
-    lk::select_trunc(v.terms, TP, selScratch_, selBytes_, truncRows_, truncCount_, s_);
+    lk::select_trunc(v.terms, TP, selScratch_.p, selBytes_, truncRows_.p, truncCount_.p, s_);
     int32_t ntr = 0;
-    hipCheck(hipMemcpyAsync(&ntr, truncCount_, sizeof(int32_t), hipMemcpyDeviceToHost, s_), "trunc count");
+    hipCheck(hipMemcpyAsync(&ntr, truncCount_.p, sizeof(int32_t), hipMemcpyDeviceToHost, s_), "trunc count");
     hipCheck(hipStreamSynchronize(s_), "sync");
     if (ntr > 0) {
-        if (ntr > truncCap_) {
-            if (truncObsC_) (void)hipFree(truncObsC_);
-            if (truncValC_) (void)hipFree(truncValC_);
-            truncCap_ = std::max<int64_t>(ntr, 2 * truncCap_);
-            hipCheck(hipMalloc((void**)&truncObsC_, (size_t)truncCap_ * exp_.W * 4), "trunc obs");
-            hipCheck(hipMalloc((void**)&truncValC_, (size_t)truncCap_ * 4), "trunc vals");
-        }
-        lk::gather_rows(v.trunc_obs, exp_.W, truncRows_, ntr, truncObsC_, s_);
-        ppo_->InferCritic(truncObsC_, ntr, truncValC_);
-        lk::scatter_f32(truncValC_, truncRows_, ntr, v.trunc_vals, s_);
+        truncObsC_.Reserve((int64_t)ntr * exp_.W, s_);
+        truncValC_.Reserve(ntr, s_);
+        lk::gather_rows(v.trunc_obs, exp_.W, truncRows_.p, ntr, truncObsC_.p, s_);
+        ppo_->InferCritic(truncObsC_.p, ntr, truncValC_.p);
+        lk::scatter_f32(truncValC_.p, truncRows_.p, ntr, v.trunc_vals, s_);
     }
     const float std_ = (float)returnStat.GetSTD();
     RlgpuCheck(rlgpu_gae_rollout(v.rewards, v.terms, v.values, v.trunc_vals, v.values + TP, T, P, cfg_.gamma,
@@ -635,8 +592,8 @@ void Learner::Consume() {
     // players have trajectories.
     const int k = cfg_.return_samples;
     if (k <= 0) return;
-    lk::last_ends(v.terms, T, P, ends_, s_);
-    hipCheck(hipMemcpyAsync(hostEnds_.data(), ends_, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, s_), "ends");
+    lk::last_ends(v.terms, T, P, ends_.p, s_);
+    hipCheck(hipMemcpyAsync(hostEnds_.data(), ends_.p, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, s_), "ends");
     hipCheck(hipStreamSynchronize(s_), "sync");
     if (oldTeam_ >= 0)
         for (int p = oldTeam_; p < P; p += 2) hostEnds_[p] = -1;  // team of player p is p % 2
@@ -673,14 +630,7 @@ void Learner::Consume() {
             slot.push_back(i);
         }
     }
-    std::vector<float> hs(std::max<size_t>(idx.size(), 1));
-    if (!idx.empty()) {
-        hipCheck(hipMemcpyAsync(sampleIdx_, idx.data(), idx.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_),
-                 "sample idx");
-        lk::gather_samples(v.ret, sampleIdx_, (int32_t)idx.size(), samples_, s_);
-        hipCheck(hipMemcpyAsync(hs.data(), samples_, idx.size() * sizeof(float), hipMemcpyDeviceToHost, s_), "samples");
-        hipCheck(hipStreamSynchronize(s_), "sync");
-    }
+    const std::vector<float> hs = GatherReturns(v.ret, idx.data(), idx.size());
     std::vector<double> draw((size_t)std::max(m, 1), 0.0);
     for (size_t j = 0; j < idx.size(); j++) draw[slot[j]] = (double)hs[j];
     if (m > 0 && coll_.allreduce_sum_f64(coll_.user, draw.data(), m) != 0)
@@ -690,17 +640,22 @@ void Learner::Consume() {
     returnStat.Increment(got.data(), m);
 }
 
+// d_ret[idx[0 .. m)] on the host (m <= return_samples; one element, unset, when m = 0)
+std::vector<float> Learner::GatherReturns(const float* d_ret, const int64_t* idx, size_t m) {
+    std::vector<float> hs(std::max<size_t>(m, 1));
+    if (m == 0) return hs;
+    hipCheck(hipMemcpyAsync(sampleIdx_.p, idx, m * sizeof(int64_t), hipMemcpyHostToDevice, s_), "sample idx");
+    lk::gather_samples(d_ret, sampleIdx_.p, (int32_t)m, samples_.p, s_);
+    hipCheck(hipMemcpyAsync(hs.data(), samples_.p, m * sizeof(float), hipMemcpyDeviceToHost, s_), "samples");
+    hipCheck(hipStreamSynchronize(s_), "sync");
+    return hs;
+}
+
 // WelfordStat::Increment over the sampled returns (Learner.cpp:959-967); ranks may hold different
 // sample counts, so the samples are all-gathered as (count, k padded samples) and every rank adds all
 void Learner::FeedReturnStat(const float* d_ret, const std::vector<int64_t>& idx, int32_t m) {
     const int k = cfg_.return_samples;
-    std::vector<float> hs((size_t)std::max(m, 1));
-    if (m > 0) {
-        hipCheck(hipMemcpyAsync(sampleIdx_, idx.data(), m * sizeof(int64_t), hipMemcpyHostToDevice, s_), "sample idx");
-        lk::gather_samples(d_ret, sampleIdx_, m, samples_, s_);
-        hipCheck(hipMemcpyAsync(hs.data(), samples_, m * sizeof(float), hipMemcpyDeviceToHost, s_), "samples");
-        hipCheck(hipStreamSynchronize(s_), "sync");
-    }
+    const std::vector<float> hs = GatherReturns(d_ret, idx.data(), (size_t)std::max(m, 0));
     if (hasColl_) {  // ranks may hold different sample counts: gather (count, k padded samples)
         std::vector<float> mine((size_t)k + 1, 0.f), all((size_t)(k + 1) * cfg_.world);
         mine[0] = (float)m;
@@ -731,16 +686,16 @@ void Learner::BatchAdvantageStats(const float* d_adv, const int32_t* d_idx, int6
     if (!hasColl_) {
         if (d_idx) {
             NeedLearnRows(n, "the batch-advantage gather");
-            lk::gather_f32(d_adv, d_idx, n, badv_, s_);
-            ppo_->AdvantageStats(badv_, n);
+            lk::gather_f32(d_adv, d_idx, n, badv_.p, s_);
+            ppo_->AdvantageStats(badv_.p, n);
         } else {
             ppo_->AdvantageStats(d_adv, n);
         }
         return;
     }
-    lk::moments_f64(d_adv, d_idx, n, mom_ + 4, mom_, s_);
+    lk::moments_f64(d_adv, d_idx, n, mom_.p + 4, mom_.p, s_);
     double m[3];
-    hipCheck(hipMemcpyAsync(m, mom_, sizeof(m), hipMemcpyDeviceToHost, s_), "moments");
+    hipCheck(hipMemcpyAsync(m, mom_.p, sizeof(m), hipMemcpyDeviceToHost, s_), "moments");
     hipCheck(hipStreamSynchronize(s_), "sync");
     if (coll_.allreduce_sum_f64(coll_.user, m, 3) != 0)
         throw rlgpu::Error(RLGPU_ERR_STATE, "Learner: advantage-moment all-reduce failed");
@@ -750,42 +705,22 @@ void Learner::BatchAdvantageStats(const float* d_adv, const int32_t* d_idx, int6
     hipCheck(hipStreamSynchronize(s_), "sync");
 }
 
-// Every consumer of the per-row learn scratch checks its row count against the capacity first: an
-// undersized buffer is an RLGPU_ERR_INVALID_ARG naming the consumer, never a device fault.
+// Every consumer of the per-row learn scratch (shuffle, row selection, batch advantages) checks its row count
+// against the capacity first: an undersized buffer is an RLGPU_ERR_INVALID_ARG naming the consumer, never a
+// device fault.
 void Learner::NeedLearnRows(int64_t n, const char* what) const {
-    if (n > permCap_)
+    const int64_t cap = std::min({perm_.cap, permRows_.cap, badv_.cap});
+    if (n > cap)
         throw rlgpu::Error(RLGPU_ERR_INVALID_ARG, std::string("Learner: ") + what + " needs " + std::to_string(n) +
-                                                      " rows of learn scratch, " + std::to_string(permCap_) + " reserved");
-}
-
-// the per-row learn scratch (shuffle, row selection, batch advantages) for M rows
-void Learner::ReserveLearnRows(int64_t M) {
-    if (M <= permCap_) return;
-    const int64_t cap = std::max<int64_t>(M, permCap_ + permCap_ / 2);
-    hipCheck(hipStreamSynchronize(s_), "sync");
-    for (void* p : {(void*)perm_, (void*)permRows_, (void*)badv_}) Release(p);
-    perm_ = Alloc<int32_t>(cap);
-    permRows_ = Alloc<int32_t>(cap);
-    badv_ = Alloc<float>(cap);
-    permCap_ = cap;
-}
-
-// the guide-logit buffer for `rows` rows (T * P in the rollout mode, set once; the trajectory mode's combined batch
-// grows it like the learn scratch)
-void Learner::ReserveGuideRows(int64_t rows) {
-    if (rows <= guideCap_) return;
-    const int64_t cap = std::max<int64_t>(rows, guideCap_ + guideCap_ / 2);
-    hipCheck(hipStreamSynchronize(s_), "sync");
-    if (guideLogits_) Release(guideLogits_);
-    guideLogits_ = Alloc<uint16_t>((size_t)cap * ACT);
-    guideCap_ = cap;
+                                                      " rows of learn scratch, " + std::to_string(cap) + " reserved");
 }
 
 void Learner::SetGuide(const float* d_policy_params, float strength) {
     RLGPU_REQUIRE(d_policy_params, "Learner::SetGuide: null parameters");
     RLGPU_REQUIRE(std::isfinite(strength) && strength >= 0.f, "Learner::SetGuide: guiding_strength must be finite and >= 0");
     RlgpuCheck(rlgpu_ppo_set_guide(ppo_->handle(), d_policy_params, s_), "set guide");
-    if (!trajMode()) ReserveGuideRows((int64_t)exp_.T * exp_.P);
+    // T * P rows in the rollout mode, set once; the trajectory mode's combined batch sizes them in Learn
+    if (!trajMode()) guideLogits_.Reserve((int64_t)exp_.T * exp_.P * ACT, s_);
     guideStrength_ = strength;
     hasGuide_ = true;
 }
@@ -807,7 +742,9 @@ void Learner::Learn() {
         v.target = traj.cTarget.p;
         if (M <= 0 && !hasColl_) return;  // with ranks, an empty one still joins every collective
     }
-    ReserveLearnRows(M);
+    perm_.Reserve(M, s_);
+    permRows_.Reserve(M, s_);
+    badv_.Reserve(M, s_);
     int64_t globalM = M * cfg_.world;
     if (trajMode() && hasColl_) {  // ranks hold different complete-trajectory counts: the true total
         double m = (double)M;
@@ -827,28 +764,28 @@ void Learner::Learn() {
             trajRanges.emplace_back(globalM ? g0 * M / globalM : 0, globalM ? g1 * M / globalM : 0);
         if (trajRanges.empty()) trajRanges.emplace_back(0, 0);
     }
-    if (rows) lk::train_rows(T, P, 1 - oldTeam_, trainRows_, s_);
+    if (rows) lk::train_rows(T, P, 1 - oldTeam_, trainRows_.p, s_);
     // the guide's logits of every row the minibatches can address, once: the guide and the obs are frozen during
     // Learn, so the reference's per-minibatch guide forward (PPOLearner.cpp:458-462) computes these same numbers
     const uint16_t* guide = nullptr;
     if (hasGuide_) {
         guideRows_ = trajMode() ? M : (int64_t)T * P;
-        ReserveGuideRows(guideRows_);
+        guideLogits_.Reserve(guideRows_ * ACT, s_);
         if (guideRows_ > 0)
-            RlgpuCheck(rlgpu_ppo_infer_guide_logits(ppo_->handle(), v.obs, guideRows_, guideLogits_, s_), "guide logits");
-        guide = guideLogits_;
+            RlgpuCheck(rlgpu_ppo_infer_guide_logits(ppo_->handle(), v.obs, guideRows_, guideLogits_.p, s_), "guide logits");
+        guide = guideLogits_.p;
     }
     for (int epoch = 0; epoch < cfg_.epochs; epoch++) {
         NeedLearnRows(M, "the shuffle");
         RlgpuCheck(rlgpu_permutation(M, cfg_.seed + (uint64_t)cfg_.rank, (uint64_t)(stats.iteration * cfg_.epochs + epoch),
-                                     perm_, s_),
+                                     perm_.p, s_),
                    "shuffle");
-        const int32_t* order = perm_;
+        const int32_t* order = perm_.p;
         if (rows) {
             NeedLearnRows(M, "the team row selection");
             if (M > (int64_t)T * (P / 2)) throw rlgpu::Error(RLGPU_ERR_INVALID_ARG, "Learner: team rows exceed T * P / 2");
-            lk::compose(trainRows_, perm_, M, permRows_, s_);
-            order = permRows_;
+            lk::compose(trainRows_.p, perm_.p, M, permRows_.p, s_);
+            order = permRows_.p;
         }
         const auto ranges = trajMode() && hasColl_ ? trajRanges : BatchRanges(M, localBatch, cfg_.overbatching != 0);
         int bi = 0;
@@ -890,10 +827,10 @@ void Learner::CollectTrajectories() {
     const rlgpu_envset_buffers& st = env_->state();
     // the players of the current policy; a team that acted with an old version last iteration starts
     // fresh trajectories (the reference freezes them and resumes them later across the gap)
-    const uint8_t* track = oldTeam_ >= 0 ? oldRows_[1 - oldTeam_] : nullptr;
-    if (J.lastOldTeam >= 0) lk::traj_restart(oldRows_[J.lastOldTeam], P, (int)(J.step % Tm), J.start, J.len, s_);
+    const uint8_t* track = oldTeam_ >= 0 ? oldRows_[1 - oldTeam_].p : nullptr;
+    if (J.lastOldTeam >= 0) lk::traj_restart(oldRows_[J.lastOldTeam].p, P, (int)(J.step % Tm), J.start.p, J.len.p, s_);
     J.lastOldTeam = oldTeam_;
-    hipCheck(hipMemsetAsync(J.counters, 0, lk::kTcCount * sizeof(int64_t), s_), "traj counters");
+    hipCheck(hipMemsetAsync(J.counters.p, 0, lk::kTcCount * sizeof(int64_t), s_), "traj counters");
     J.firstStep = J.step;
     J.steps = 0;
     J.nrec = J.ntrunc = J.nrows = 0;
@@ -908,12 +845,12 @@ void Learner::CollectTrajectories() {
         const int r = (int)(J.step % Tm), rn = (int)((J.step + 1) % Tm);
         const size_t row = (size_t)r * P;
         // the pre-reset rows stay in the env's buffer (or, stacked, go to the stage) for traj_trunc_copy below
-        ActAndStep(row, (size_t)rn * P, nullptr, J.truncStage, nullptr);
-        lk::traj_step(v.terms + row, r, Tm, track, P, J.start, J.len, J.Records(), J.counters, J.trnew, s_);
-        lk::traj_trunc_copy(K_ > 1 ? J.truncStage : st.trunc_obs, W, J.counters, J.trnew, J.truncObs.p, s_);
+        ActAndStep(row, (size_t)rn * P, nullptr, J.truncStage.p, nullptr);
+        lk::traj_step(v.terms + row, r, Tm, track, P, J.start.p, J.len.p, J.Records(), J.counters.p, J.trnew.p, s_);
+        lk::traj_trunc_copy(K_ > 1 ? J.truncStage.p : st.trunc_obs, W, J.counters.p, J.trnew.p, J.truncObs.p, s_);
         J.step++;
         J.steps++;
-        hipCheck(hipMemcpyAsync(J.hcounters, J.counters, lk::kTcCount * sizeof(int64_t), hipMemcpyDeviceToHost, s_),
+        hipCheck(hipMemcpyAsync(J.hcounters.get(), J.counters.p, lk::kTcCount * sizeof(int64_t), hipMemcpyDeviceToHost, s_),
                  "traj counters");
         hipCheck(hipStreamSynchronize(s_), "sync");
         J.nrec = J.hcounters[lk::kTcRecs];
@@ -948,10 +885,10 @@ void Learner::ConsumeTrajectories() {
     ppo_->InferCritic(J.cObs.p, M, J.cVals.p);  // InferCriticBatched (Learner.cpp:936)
     if (ntr > 0) ppo_->InferCritic(J.truncObs.p, ntr, J.truncVals.p);  // nextTruncStates (:939-941)
     const float std_ = (float)returnStat.GetSTD();
-    hipCheck(hipMemsetAsync(clipSums_, 0, 2 * sizeof(float), s_), "clip sums");
+    hipCheck(hipMemsetAsync(clipSums_.p, 0, 2 * sizeof(float), s_), "clip sums");
     RlgpuCheck(rlgpu_gae_segments(J.cRews.p, J.cTerms.p, J.cVals.p, ntr > 0 ? J.truncVals.p : nullptr, J.roff.p, J.rlen.p,
                                   J.rtidx.p, K, cfg_.gamma, cfg_.gae_lambda, std_, cfg_.reward_clip_range, J.cAdv.p,
-                                  J.cTarget.p, J.cRet.p, clipSums_, s_),
+                                  J.cTarget.p, J.cRet.p, clipSums_.p, s_),
                "GAE");
     // return-std samples: torch::randint over every combined return (Learner.cpp:959-967)
     const int k = cfg_.return_samples;
@@ -1016,7 +953,7 @@ void Learner::Start(int64_t iterations) {
 
 // ------------------------------------------------------------------ C ABI
 struct rlgpu_learner {
-    GGL::Learner* L = nullptr;
+    std::unique_ptr<GGL::Learner> L;
 };
 
 extern "C" int rlgpu_learner_default_config(rlgpu_learner_config* c) {
@@ -1059,21 +996,14 @@ extern "C" int rlgpu_learner_create(const rlgpu_learner_config* cfg, const rlgpu
                                     rlgpu_learner** out) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(cfg && out, "rlgpu_learner_create: null argument");
-        auto* h = new rlgpu_learner();
-        try {
-            h->L = new GGL::Learner(*cfg, coll, rlgpu::as_stream(stream));
-        } catch (...) {
-            delete h;
-            throw;
-        }
-        *out = h;
+        auto h = std::make_unique<rlgpu_learner>();
+        h->L = std::make_unique<GGL::Learner>(*cfg, coll, rlgpu::as_stream(stream));
+        *out = h.release();
     });
 }
 
 extern "C" int rlgpu_learner_destroy(rlgpu_learner* h) {
     return rlgpu::guarded([&] {
-        if (!h) return;
-        delete h->L;
         delete h;
     });
 }
@@ -1170,13 +1100,14 @@ extern "C" int rlgpu_learner_set_old_team(rlgpu_learner* h, int32_t team) {
 }
 extern "C" int rlgpu_learner_set_guide(rlgpu_learner* h, const float* d_policy_params, float guiding_strength) {
     return rlgpu::guarded([&] {
-        RLGPU_REQUIRE(h, "null learner");
+        RLGPU_LEARNER(h);
         h->L->SetGuide(d_policy_params, guiding_strength);
     });
 }
 extern "C" int rlgpu_learner_guide_logits(rlgpu_learner* h, const uint16_t** d_logits, int64_t* rows) {
     return rlgpu::guarded([&] {
-        RLGPU_REQUIRE(h && d_logits && rows, "rlgpu_learner_guide_logits: null argument");
+        RLGPU_LEARNER(h);
+        RLGPU_REQUIRE(d_logits && rows, "rlgpu_learner_guide_logits: null argument");
         *d_logits = h->L->guideLogits();
         *rows = h->L->guideRows();
     });

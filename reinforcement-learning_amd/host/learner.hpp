@@ -5,6 +5,11 @@
 // mirrors it).  Every C-ABI status is turned back into std::runtime_error, so the reference's
 // try/catch (Learner.cpp:466-474, ExampleMain.cpp:603-612) keeps its behaviour.
 //
+// Ownership: every device buffer of this side is a DevArray member (of ExperienceBuffer, TrajectoryStore,
+// PPOLearnerGPU or the Learner), the pinned counters and the env / PPO handles are unique_ptrs.  Nothing is freed
+// by name: members go in reverse declaration order, the handles declared before (so destroyed after) the buffers
+// a kernel of theirs may still read, and a constructor that throws releases what it had acquired.
+//
 // Reference map (GigaLearnCPP/RLGymCPP, paths as SURVEY.md):
 //   RLGC::EnvSetGPU      RG/EnvSet/EnvSet.h:67-124        (EnvSet: StepFirstHalf / StepSecondHalf /
 //                                                           Sync / Reset / ResetArena / state)
@@ -16,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -36,9 +42,6 @@ inline void RlgpuCheck(int st, const char* what) {
 class EnvSetGPU {
 public:
     EnvSetGPU(const rlgpu_envset_config& cfg, hipStream_t stream);
-    ~EnvSetGPU();
-    EnvSetGPU(const EnvSetGPU&) = delete;
-    EnvSetGPU& operator=(const EnvSetGPU&) = delete;
 
     void StepFirstHalf(bool async = true);                        // EnvSet.cpp:113-130
     void StepSecondHalf(const int32_t* d_actions, bool async);    // EnvSet.cpp:132-273
@@ -47,11 +50,14 @@ public:
     void Reset();                                                 // EnvSet.cpp:331-354
     void ResetArenas(const uint8_t* d_mask);                      // EnvSet.cpp:275-329
 
-    rlgpu_envset* handle() const { return h_; }
+    rlgpu_envset* handle() const { return h_.get(); }
     const rlgpu_envset_buffers& state() const { return state_; }  // EnvSet::state (device views)
 
 private:
-    rlgpu_envset* h_ = nullptr;
+    struct Destroy {
+        void operator()(rlgpu_envset* h) const { rlgpu_envset_destroy(h); }
+    };
+    std::unique_ptr<rlgpu_envset, Destroy> h_;
     rlgpu_envset_buffers state_{};
     hipStream_t stream_;
 };
@@ -81,6 +87,31 @@ void MomentsMeanStd(const double* m3, float* out2);
 // ExperienceBuffer::GetAllBatchesShuffled boundaries (ExperienceBuffer.cpp:117-162).
 std::vector<std::pair<int64_t, int64_t>> BatchRanges(int64_t expSize, int64_t batchSize, bool overbatching);
 
+// The one owner of device memory on this side: an array that grows on demand and frees itself (move-only).
+// Allocation and release go through rlgpu::dev_alloc / dev_free (csrc/common.hpp), which count them.
+template <class T>
+struct DevArray {
+    T* p = nullptr;
+    int64_t cap = 0;  // elements (the block carries 16 bytes of padding beyond them)
+    DevArray() = default;
+    DevArray(DevArray&& o) noexcept { *this = std::move(o); }
+    DevArray& operator=(DevArray&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~DevArray();
+    // At least n elements: nothing when n <= cap, else a new block of max(n, 1.5 cap), zero-filled and / or holding
+    // the old contents on request (both on s), and the old block freed once s has drained.  A failure leaves the
+    // array as it was.
+    void Reserve(int64_t n, hipStream_t s, bool keep = false, bool zero = false);
+};
+
+// hipHostMalloc'd memory in a unique_ptr
+struct PinnedFree {
+    void operator()(void* p) const;
+};
+
 // The rollout ([T, P] time-major) in HBM; every collected step is trained in the iteration that
 // collected it (the unfinished tail bootstrapped from V(obs_T), DESIGN.md Deviations 5).
 // In RLGPU_EXP_TRAJECTORIES the same arrays are a circular per-player step store of T rows (obs row r
@@ -88,19 +119,12 @@ std::vector<std::pair<int64_t, int64_t>> BatchRanges(int64_t expSize, int64_t ba
 // combined batch instead (rollout_outputs = false).
 struct ExperienceBuffer {
     int T = 0, P = 0, W = 0;  // W: obs row width (RLGPU_OBS x frames)
-    rlgpu_rollout_view v{};
-    std::vector<void*> allocs;
-    void Allocate(int T, int P, int W, bool rollout_outputs = true);
-    void Free();
-};
-
-// Device arrays that grow on demand (kept across iterations).
-template <class T>
-struct DevArray {
-    T* p = nullptr;
-    int64_t cap = 0;
-    void Reserve(int64_t n, hipStream_t s, bool keep = false);
-    void Free();
+    rlgpu_rollout_view v{};  // views of the arrays below
+    DevArray<float> obs, logp, rewards, truncObs, values, truncVals, adv, target, ret;
+    DevArray<uint8_t> masks;
+    DevArray<int32_t> actions;
+    DevArray<int8_t> terms;
+    void Allocate(int T, int P, int W, hipStream_t s, bool rollout_outputs = true);  // zero-filled
 };
 
 // RLGPU_EXP_TRAJECTORIES state: per-player trajectories, this iteration's records, truncation list and
@@ -112,9 +136,9 @@ struct TrajectoryStore {
     int64_t firstStep = 0;      // this iteration's first step
     int steps = 0;              // steps collected this iteration
     int lastOldTeam = -1;
-    int32_t *start = nullptr, *len = nullptr, *trnew = nullptr;
-    int64_t* counters = nullptr;      // device lk::kTcCount
-    int64_t* hcounters = nullptr;     // pinned host copy
+    DevArray<int32_t> start, len, trnew;  // [P]
+    DevArray<int64_t> counters;           // lk::kTcCount
+    std::unique_ptr<int64_t[], PinnedFree> hcounters;  // pinned host copy
     DevArray<int32_t> rp, rstart, rlen, rcode, rtidx;
     DevArray<int64_t> roff;
     DevArray<float> truncObs, truncVals;
@@ -122,7 +146,7 @@ struct TrajectoryStore {
     DevArray<uint8_t> cMasks;
     DevArray<int32_t> cActs;
     DevArray<int8_t> cTerms;
-    float* truncStage = nullptr;  // [P][W] stacked pre-reset rows (frame stacking)
+    DevArray<float> truncStage;  // [P][W] stacked pre-reset rows (frame stacking), else empty
     int64_t nrec = 0, ntrunc = 0, nrows = 0;
     lk::TrajRecs Records() const;  // this iteration's records (rp .. roff) as the kernels take them
 };
@@ -131,9 +155,6 @@ struct TrajectoryStore {
 class PPOLearnerGPU {
 public:
     PPOLearnerGPU(const rlgpu_ppo_config& cfg, hipStream_t stream);
-    ~PPOLearnerGPU();
-    PPOLearnerGPU(const PPOLearnerGPU&) = delete;
-    PPOLearnerGPU& operator=(const PPOLearnerGPU&) = delete;
 
     void InferActions(const float* d_obs, const uint8_t* d_masks, int n, bool deterministic, uint64_t step,
                       int32_t* d_actions, float* d_logp, const uint8_t* d_old_rows = nullptr);
@@ -145,19 +166,22 @@ public:
     void OptimizerStep();
     int64_t minibatches = 0;  // summed into metrics() since the last reset
 
-    rlgpu_ppo* handle() const { return h_; }
+    rlgpu_ppo* handle() const { return h_.get(); }
     float* grads() const { return grads_; }
     int64_t num_params() const { return nparams_; }
-    float* adv_stats() const { return adv_stats_; }
-    float* metrics() const { return metrics_; }
+    float* adv_stats() const { return adv_stats_.p; }
+    float* metrics() const { return metrics_.p; }
 
 private:
-    rlgpu_ppo* h_ = nullptr;
+    struct Destroy {
+        void operator()(rlgpu_ppo* h) const { rlgpu_ppo_destroy(h); }
+    };
+    std::unique_ptr<rlgpu_ppo, Destroy> h_;  // before the arrays: a failed allocation unwinds it
     hipStream_t stream_;
     float* grads_ = nullptr;
     int64_t nparams_ = 0;
-    float* adv_stats_ = nullptr;  // device [2]
-    float* metrics_ = nullptr;    // device [RLGPU_NUM_METRICS]
+    DevArray<float> adv_stats_;  // [2]
+    DevArray<float> metrics_;    // [RLGPU_NUM_METRICS]
 };
 
 // GGL::Learner (Learner.h:11-45): one rank's training loop.
@@ -179,7 +203,7 @@ public:
     // PPOLearnerConfig::useGuidingPolicy: the guide's flat fp32 parameters (rlgpu_ppo_set_guide's layout) and
     // guidingStrength; every later Learn adds the guiding term
     void SetGuide(const float* d_policy_params, float strength);
-    const uint16_t* guideLogits() const { return guideLogits_; }
+    const uint16_t* guideLogits() const { return guideLogits_.p; }
     int64_t guideRows() const { return guideRows_; }
     void SetGradHook(rlgpu_grad_hook_fn fn, void* user) {
         gradHook_ = fn;
@@ -206,14 +230,17 @@ private:
     void BatchAdvantageStats(const float* d_adv, const int32_t* d_idx, int64_t n);
     void CollectTrajectories();
     void ConsumeTrajectories();
+    std::vector<float> GatherReturns(const float* d_ret, const int64_t* idx, size_t m);
     void FeedReturnStat(const float* d_ret, const std::vector<int64_t>& idx, int32_t m);
     bool trajMode() const { return cfg_.experience_mode == RLGPU_EXP_TRAJECTORIES; }
     hipStream_t s_;
     rlgpu_learner_config cfg_;
     rlgpu_collective coll_{};
     bool hasColl_ = false;
-    RLGC::EnvSetGPU* env_ = nullptr;
-    PPOLearnerGPU* ppo_ = nullptr;
+    // the env set and the PPO handle come before every buffer below, `traj` included: members go in reverse
+    // order, so the kernels of either that may still read a buffer are gone (hipFree synchronises) before it
+    std::unique_ptr<RLGC::EnvSetGPU> env_;
+    std::unique_ptr<PPOLearnerGPU> ppo_;
     ExperienceBuffer exp_;
     int oldTeam_ = -1;
     bool envTiming_ = false;
@@ -222,7 +249,7 @@ private:
     rlgpu_grad_hook_fn gradHook_ = nullptr;
     void* gradHookUser_ = nullptr;
     int K_ = 1;                 // frames stacked (config C4)
-    float* hist_ = nullptr;     // [K-1][P][OBS] frame history
+    DevArray<float> hist_;      // [K-1][P][OBS] frame history
     std::vector<hipEvent_t> ev_;
     // the rollout collection in arena groups (rlgpu_learner_config.collect_groups): one stream per group, each on
     // its own CU partition (host/cu_partition.hpp), joined to s_ by events at the phase's start and end
@@ -239,43 +266,33 @@ private:
     bool CollectLoopOk() const;
     void CollectLoop();
     // device scratch
-    uint8_t* oldRows_[2] = {nullptr, nullptr};
+    DevArray<uint8_t> oldRows_[2];
     // the rows that act with the old version this iteration (self-play), or null
-    const uint8_t* OldRows() const { return oldTeam_ >= 0 ? oldRows_[oldTeam_] : nullptr; }
-    int32_t* trainRows_ = nullptr;
-    int32_t* perm_ = nullptr;     // the shuffle, its row-selected form and the gathered batch advantages:
-    int32_t* permRows_ = nullptr; // permCap_ rows each (T * P; grown to the combined batch in the
-    float* badv_ = nullptr;       // trajectory mode, whose row count has no fixed bound)
-    int64_t permCap_ = 0;
+    const uint8_t* OldRows() const { return oldTeam_ >= 0 ? oldRows_[oldTeam_].p : nullptr; }
+    DevArray<int32_t> trainRows_;
+    // the shuffle, its row-selected form and the gathered batch advantages: the same row count each (T * P; Learn
+    // grows them to the combined batch in the trajectory mode, whose row count has no fixed bound)
+    DevArray<int32_t> perm_, permRows_;
+    DevArray<float> badv_;
     // the guiding policy's 16-bit logits of the rows Learn trains on ([T * P][ACT], or the combined batch's rows in
-    // the trajectory mode), written once per Learn before the epoch loop; null without a guide
-    uint16_t* guideLogits_ = nullptr;
-    int64_t guideCap_ = 0, guideRows_ = 0;
+    // the trajectory mode), written once per Learn before the epoch loop; empty without a guide
+    DevArray<uint16_t> guideLogits_;
+    int64_t guideRows_ = 0;
     float guideStrength_ = 0.f;
     bool hasGuide_ = false;
-    void ReserveGuideRows(int64_t rows);
     void NeedLearnRows(int64_t n, const char* what) const;
-    void ReserveLearnRows(int64_t M);
-    int32_t* truncRows_ = nullptr;
-    int32_t* truncCount_ = nullptr;
-    void* selScratch_ = nullptr;
+    DevArray<int32_t> truncRows_, truncCount_;
+    DevArray<char> selScratch_;
     size_t selBytes_ = 0;
-    float* truncObsC_ = nullptr;
-    float* truncValC_ = nullptr;
-    int64_t truncCap_ = 0;
-    int64_t* sampleIdx_ = nullptr;
-    float* samples_ = nullptr;
-    int32_t* ends_ = nullptr;          // [P] last trajectory end per column (return sampling)
+    DevArray<float> truncObsC_, truncValC_;  // the truncated rows' obs gathered for the critic, and their values
+    DevArray<int64_t> sampleIdx_;
+    DevArray<float> samples_;
+    DevArray<int32_t> ends_;  // [P] last trajectory end per column (return sampling)
     std::vector<int32_t> hostEnds_;
-    double* mom_ = nullptr;   // [3] + scratch
-    float* clipSums_ = nullptr;  // [2] GAE clip-portion partial sums
+    DevArray<double> mom_;       // [3] + scratch
+    DevArray<float> clipSums_;   // [2] GAE clip-portion partial sums
   public:
     TrajectoryStore traj;      // RLGPU_EXP_TRAJECTORIES
-  private:
-    std::vector<void*> allocs_;
-    template <class T>
-    T* Alloc(size_t count);
-    void Release(void* p);
 };
 
 }  // namespace GGL
