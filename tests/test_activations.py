@@ -3,9 +3,9 @@ and the training kernels against float64.
 
 The training cases are tests/test_ppo_variants.py's (same numpy parameter streams, same seeds, same batches) with
 every LeakyReLU module swapped for Sigmoid / Tanh and the cases' slope set to 1.0, which makes side_conditions skip
-its kink check (it reads LeakyReLU inputs; these activations have no kink).  The rules are that file's check_grads /
-check_metrics / check_forward, unchanged: error at most factor(mode, n) x torch fp32's own error against float64
-plus the floor, the 1e-4 normwise ceiling, the elementwise band.
+its kink check (it reads LeakyReLU inputs; these activations have no kink).  The rules are tests/ppo_reference.py's
+check_grads / check_metrics / check_forward, unchanged: error at most factor(mode, n) x torch fp32's own error against
+float64 plus the floor, the 1e-4 normwise ceiling, the elementwise band.
 
 Largest (err - floor) / (torch fp32 err) measured on an MI355X over test_training_kernels_against_float64 and
 test_fallback_from_full_row_kernels, gradients / forward outputs (metrics: largest err / allowed error):
@@ -14,17 +14,14 @@ The largest gradient error is 2.9e-6 of its tensor's norm, against the 1e-4 ceil
 one-row minibatch with sigmoid (rows1 / sigmoid / x6: every critic tensor, 4.2 .. 6.2; 1.78 on every other case of
 that mode), see CASE_FACTOR.
 """
-import copy
 import ctypes
-import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from test_ppo_variants import (CASES, MODE_IDS, MODES, Case, build_batch, build_modules, check_forward, check_grads,
-                               check_metrics, engine_minibatch, make_engine, run_refs, side_conditions)
+from ppo_reference import MODE_IDS, MODES, Case, build_case, check_golden, run_engine_case, side_conditions
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "reinforcement-learning_amd", "rlgpu", "rlgpu_optim_lt")
@@ -33,6 +30,22 @@ ACTS = ("sigmoid", "tanh")
 # kernels, one row and a ragged second block
 GPU_CASES = ("a2", "d64", "e100", "h90", "i16", "noln", "noln_wide", "rows1", "rows33")
 CPU_CASES = ("a2", "b17", "c16", "d64", "e100", "g128", "h90", "i16", "noln", "noln_wide", "rows1", "rows33")
+GOLDEN_CASES = ("a2", "h90", "noln")  # pinned in tests/golden/ppo_reference.npz for both activations
+# The entries of test_ppo_variants' SWEEP that the lists above name, restated (that table's comments name the kernels)
+CASES = {c.name: c for c in [
+    Case("a2", 167, 2, (33, 65), (130, 64), seed=0),
+    Case("b17", 168, 17, (64, 128), (65, 33), seed=1),
+    Case("c16", 167, 16, (130, 255), (33, 128), seed=1),
+    Case("d64", 168, 64, (256, 257), (128, 65), seed=0),
+    Case("e100", 167, 100, (510, 512), (257, 256), seed=8),
+    Case("g128", 168, 128, (516, 1024), (256, 512), seed=75),
+    Case("h90", 167, 90, (1028, 2048), (510, 257), seed=254),
+    Case("i16", 167, 16, (1023,), (2047, 1024), seed=350),
+    Case("noln", 167, 90, (65, 256), (130, 33), seed=7, ln=False),
+    Case("noln_wide", 167, 90, (516, 33), (1023,), seed=2, ln=False),
+    Case("rows1", 167, 90, (96, 33), (40, 64), seed=0, n=1),
+    Case("rows33", 167, 90, (96, 33), (40, 64), seed=0, n=33),
+]}
 # The fallback from the full-row H3 kernels: both models (512, 512), 65 rows (one row past the 64-row tile), obs 167
 FALLBACK = Case("fallback", 167, 90, (512, 512), (512, 512), seed=0, slope=1.0, n=65)
 
@@ -51,25 +64,11 @@ def case_of(name):
     return FALLBACK if name == "fallback" else CASES[name]._replace(slope=1.0)
 
 
-def swap_activation(seq, act):
-    """seq with every LeakyReLU replaced by Sigmoid / Tanh (the parameters untouched)."""
-    import torch
-    new = {"sigmoid": torch.nn.Sigmoid, "tanh": torch.nn.Tanh}[act]
-    return torch.nn.Sequential(*[new() if isinstance(m, torch.nn.LeakyReLU) else m for m in seq])
-
-
-@functools.lru_cache(maxsize=None)
 def act_case(name, act, ln=None):
     """Case `name` with the activation swapped (ln: override the case's LayerNorm setting): modules, batch, the
     float64 reference and the torch fp32 yardstick, computed once."""
     c = case_of(name)
-    if ln is not None:
-        c = c._replace(ln=ln)
-    mods = [swap_activation(m, act) for m in build_modules(c)]
-    b = build_batch(c, copy.deepcopy(mods[0]).double())
-    r64, r32 = run_refs(c, mods, b)
-    return {"case": c, "mods": mods, "batch": b, "r64": r64, "r32": r32,
-            "rows": b["index"][b["start"]:b["start"] + c.n]}
+    return build_case(c if ln is None else c._replace(ln=ln), act=act)
 
 
 def assert_inputs_hold(d, tag):
@@ -182,6 +181,14 @@ def test_side_conditions_hold(name, act, ln):
     assert_inputs_hold(act_case(name, act, ln), f"{name}/{act}/{'ln' if ln else 'noln'}")
 
 
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("name", GOLDEN_CASES)
+def test_reference_matches_golden(name, act):
+    """The float64 reference of three cases with both activations against tests/golden/ppo_reference.npz
+    (ppo_reference.check_golden)."""
+    check_golden(f"act/{name}/{act}", act_case(name, act))
+
+
 def _tool(*args):
     return subprocess.run([TOOL, *[str(a) for a in args]], capture_output=True, text=True, timeout=120)
 
@@ -220,37 +227,21 @@ def test_checkpoint_tools_without_layer_norm(tmp_path):
 
 # ------------------------------------------------------------------ GPU
 def run_act_case(gpu, d, act, mode, tag, after_minibatch=None, grad_factor=None):
-    """grad_factor: the gradient rule's factor for this case instead of test_ppo_variants.factor's (CASE_FACTOR)."""
-    import test_ppo_variants as tpv
+    """grad_factor: the gradient rule's factor for this case instead of ppo_reference.factor's (CASE_FACTOR)."""
     c = d["case"]
     assert_inputs_hold(d, tag)
-    p = make_engine(gpu, c, d["mods"], mode, activation=act)
-    for m in (0, 1):  # the engine's own restatement holds the swapped modules
-        kinds = {type(x).__name__ for x in p.torch_module(m)}
-        assert {"sigmoid": "Sigmoid", "tanh": "Tanh"}[act] in kinds and "LeakyReLU" not in kinds
-        assert ("LayerNorm" in kinds) == c.ln
-    p.zero_grad()
-    errs = []
-    if after_minibatch:
-        after_minibatch(p, "before")
-    engine_minibatch(gpu, p, c, d["batch"])
-    if after_minibatch:
-        after_minibatch(p, "after")
 
-    def grads():
-        with pytest.MonkeyPatch.context() as mp:
-            if grad_factor is not None:
-                mp.setattr(tpv, "factor", lambda mode_, n_: grad_factor)
-            check_grads(p.flat(grads=True).cpu(), d["r64"], d["r32"], d["mods"], mode, tag, c.n)
+    def around(p, when):
+        if when == "before":  # the engine's own restatement holds the swapped modules
+            for m in (0, 1):
+                kinds = {type(x).__name__ for x in p.torch_module(m)}
+                assert {"sigmoid": "Sigmoid", "tanh": "Tanh"}[act] in kinds and "LeakyReLU" not in kinds
+                assert ("LayerNorm" in kinds) == c.ln
+        if after_minibatch:
+            after_minibatch(p, when)
 
-    for fn in (grads, lambda: check_metrics(p, d["r64"], d["r32"], mode, tag, c.n),
-               lambda: check_forward(gpu, p, d, mode, tag)):
-        try:
-            fn()
-        except AssertionError as e:  # every failing part of the case, not the first
-            errs.append(str(e))
-    p.close()
-    assert not errs, "\n".join(errs)
+    run_engine_case(gpu, d, mode, tag, engine_kw=dict(activation=act), grad_factor=grad_factor,
+                    around_minibatch=around)
 
 
 @pytest.mark.gpu
@@ -259,7 +250,7 @@ def run_act_case(gpu, d, act, mode, tag, after_minibatch=None, grad_factor=None)
 @pytest.mark.parametrize("name", GPU_CASES)
 def test_training_kernels_against_float64(gpu, name, act, mode):
     """One minibatch from zero_grad per case, activation and GEMM mode: gradients, the six metrics and the fp32
-    forward of both models against float64, by test_ppo_variants' rules."""
+    forward of both models against float64, by ppo_reference's rules."""
     run_act_case(gpu, act_case(name, act), act, mode, f"{name}/{act}/{MODE_IDS[mode]}",
                  grad_factor=CASE_FACTOR.get((name, act, mode)))
 

@@ -6,13 +6,13 @@ masked softmax of (guide logits / temperature) and c the trained policy's clampe
 guidingLoss * guidingStrength after the batch-size-ratio scaling.  Here the guide logits are an explicit 16-bit input
 of the minibatch, so the term is checked against a float64 reference built entirely on the CPU:
 
-  * minibatch_ref_guide is test_policy_options.minibatch_ref_opt plus the guide term (at strength 0 it reproduces that
-    function's gradients and metrics exactly, asserted here).  The GPU cases are held to test_ppo_variants' rules and
-    constants unchanged (check_grads, check_metrics, check_forward); the guiding-loss metric is a one-element result
-    under that file's scalar rule with S = mean over (row, action) of c_k (1 + |z_k| + zmax) + g_k (1 + |zg_k| + zgmax).
+  * ppo_reference.minibatch_ref with guide_logits (at strength 0 it reproduces its own gradients and metrics without
+    a guide exactly, asserted here).  The GPU cases are held to ppo_reference's rules and constants unchanged
+    (check_grads, check_metrics, check_forward); the guiding-loss metric is a one-element result under that module's
+    scalar rule with S = mean over (row, action) of c_k (1 + |z_k| + zmax) + g_k (1 + |zg_k| + zgmax).
   * Guide logits per case: a numpy stream N(0, 1) * gscale (seed 4242 + the case's seed), rounded to bf16 with
     round-to-nearest-even (fp16 for the fp16 case), so they are exactly representable in the handle's format.
-  * Side conditions, decided by the float64 reference alone: test_ppo_variants.side_conditions, two legal actions per
+  * Side conditions, decided by the float64 reference alone: ppo_reference.side_conditions, two legal actions per
     row under mask_entropy, and the sign margin -- d |g - c| / d c = sign(c - g) is decided by float64 only where the
     gap is well above fp32's error: for every legal (row, action) either the row has a single legal action
     (c = g = 1 exactly in any precision) or |c - g| >= GUIDE_DELTA * max(c, g).  GUIDE_DELTA is 10 x the largest
@@ -35,83 +35,19 @@ of the minibatch, so the term is checked against a float64 reference built entir
     asserts 1 % where A = 2 and at least 2e-4 (twice the ceiling: the engine's own error, bounded by the ceiling,
     cannot cancel it) everywhere.
 """
-import copy
-import functools
-import math
-
 import numpy as np
 import pytest
 
-from test_policy_options import build_option_batch, minibatch_ref_opt
-from test_ppo_variants import (CLIP, EDGE, ENT_SCALE, MODE_IDS, MODES, Case, build_batch, build_modules, check_forward,
-                               check_grads, check_metrics, factor, make_engine, masked_probs, ratio_of, run_seq,
-                               scalar_floor, side_conditions)
+from ppo_reference import (MODE_IDS, MODES, Case, build_case, check_golden, check_metrics, engine_minibatch,
+                           guide_stream, make_engine, one_element, run_engine_case, run_refs, side_conditions)
 
+# loss-kernel edge rows on a default-width policy, logits spanning about +-60: test_ppo_variants' EDGE
+EDGE = Case("edge", 167, 90, (512, 512), (64,), seed=20, n=64, out_scale=50.0, edge=True)
 STRENGTH = 0.5      # guiding_strength of the gradient cases (the reference's default is 0.03)
 GUIDE_DELTA = 2e-5  # sign margin, see the module docstring
 EDGE_DELTA = 5e-4   # the edge case's (logits over about +-60)
 CLAMP, CLAMP_MARGIN = 1e-11, 1e-3  # ACTION_MIN_PROB and side_conditions' 0.1 % distance from it
 M_GUIDE = 10        # RLGPU_M_GUIDING_LOSS
-
-
-# ------------------------------------------------------------------ the reference
-def minibatch_ref_guide(pol, crit, obs, masks, acts, old_logp, adv, target, batch_size, guide_logits, strength,
-                        temperature=1.0, mask_entropy=False, clip=CLIP, ent_scale=ENT_SCALE):
-    """test_policy_options.minibatch_ref_opt plus strength * mean |g - c| (PPOLearner.cpp:458-468), generic in the
-    dtype; guide_logits [n, A] in the dtype of obs.  The same return values, and: the guiding loss and its rounding
-    scale, the clamped probabilities c and g."""
-    import torch
-    for m in (pol, crit):
-        m.zero_grad(set_to_none=True)
-    n = obs.shape[0]
-    bsr = n / float(batch_size)
-    logits, pre_p = run_seq(pol, obs)
-    tl = logits / temperature
-    raw, probs = masked_probs(tl, masks)
-    logp = probs.gather(-1, acts.long().unsqueeze(-1)).squeeze(-1).log()
-    log_cnt = masks.to(obs.dtype).sum(-1).log() if mask_entropy else math.log(probs.shape[1])
-    ent = (-(probs.log() * probs).sum(-1) / log_cnt).mean()
-    lr = logp - old_logp
-    ratio = lr.exp()
-    clipped = ratio.clamp(1 - clip, 1 + clip)
-    terms = torch.min(ratio * adv, clipped * adv)
-    pl = -terms.mean()
-    vals, pre_c = run_seq(crit, obs)
-    vals = vals.flatten()
-    closs = torch.nn.functional.mse_loss(vals, target) * bsr
-    with torch.no_grad():  # the guide: no gradient (PPOLearner.cpp:459 runs it under NoGradGuard)
-        gl = guide_logits / temperature
-        graw, gprobs = masked_probs(gl, masks)
-    guiding = (gprobs - probs).abs().mean()
-    # ppoLoss += guidingLoss * guidingStrength after the batch-size-ratio scaling (PPOLearner.cpp:466-468)
-    ((pl - ent * ent_scale) * bsr + guiding * strength + closs).backward()
-    kl = (lr.exp() - 1 - lr).mean()
-    frac = ((ratio - 1).abs() > clip).to(obs.dtype).mean()
-    f = lambda t: float(t.detach().double())  # noqa: E731
-    with torch.no_grad():
-        tl = tl.detach()
-        legal = masks.bool()
-        z = tl + -1e10 * legal.logical_not()
-        zm = z.max(-1).values.abs()
-        ai = acts.long().unsqueeze(-1)
-        legal_a = legal.gather(-1, ai).squeeze(-1)
-        lcond = 1 + (tl.gather(-1, ai).squeeze(-1).abs() + zm) * legal_a + old_logp.abs()
-        zc = 1 + tl.abs() * legal + zm.unsqueeze(-1)
-        s_ent = ((probs * (probs.log().abs() + 1) * zc).sum(-1) / log_cnt).mean()
-        s_crit = ((2 * (vals - target).abs() * (vals.abs() + target.abs()) + (vals - target) ** 2).mean()) * bsr
-        s_head = 2 * bsr / n * (vals.abs() + target.abs()).sum()
-        zgm = (gl + -1e10 * legal.logical_not()).max(-1).values.abs()
-        zgc = 1 + gl.abs() * legal + zgm.unsqueeze(-1)
-        s_guide = (probs * zc + gprobs * zgc).mean()
-    return {"grads": torch.cat([p.grad.reshape(-1) for m in (pol, crit) for p in m.parameters()]).clone(),
-            "metrics": np.array([f(ent), f(kl), f(pl), f(closs), f(ratio.mean()), f(frac)]),
-            "scales": np.array([f(s_ent), f(((ratio + 1) * lcond).mean()), f((adv.abs() * ratio * lcond).mean()),
-                                f(s_crit), f((ratio * lcond).mean()), 1.0]),
-            "head_bias_scale": f(s_head),
-            "pre": pre_p + pre_c, "logits": logits.detach(), "values": vals.detach(), "raw_probs": raw.detach(),
-            "ratio": ratio.detach(),
-            "guiding": f(guiding), "guide_scale": f(s_guide), "probs": probs.detach(), "gprobs": gprobs.detach(),
-            "graw": graw.detach()}
 
 
 # ------------------------------------------------------------------ the cases
@@ -145,52 +81,10 @@ GUIDE_CASES = {
 MANY = GuideCase(Case("rows8161", 167, 90, (64, 36), (64, 36), seed=0, slope=1.0, n=8161, extra=100), 1.5, True, 1.0)
 
 
-def guide_stream(c, gscale, fp16, seed_offset=0):
-    """(bits uint16 [B, A], values f32 [B, A]) of the case's guide logits: N(0, 1) * gscale from the stream
-    4242 + c.seed, rounded to nearest even into bf16 (fp16: numpy's own rounding)."""
-    rng = np.random.default_rng(4242 + c.seed + seed_offset)
-    x = (rng.standard_normal((c.n + c.extra, c.A)) * gscale).astype(np.float32)
-    if fp16:
-        h = x.astype(np.float16)
-        return h.view(np.uint16).copy(), h.astype(np.float32)
-    u = x.view(np.uint32)
-    bits = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
-    return bits, (bits.astype(np.uint32) << np.uint32(16)).view(np.float32)
-
-
-def run_guide_refs(g, mods, b, gvals, strength):
-    """(float64 reference, torch fp32 yardstick) of the guided minibatch."""
-    import torch
-    c = g.case
-    rows = b["index"][b["start"]:b["start"] + c.n].astype(np.int64)
-    adv64 = b["adv"].astype(np.float64)
-    advn64 = (adv64 - adv64.mean()) / (adv64.std(ddof=1) + 1e-8)
-    advn32 = ((b["adv"] - b["adv"].mean()) / (b["adv"].std(ddof=1) + np.float32(1e-8))).astype(np.float32)
-    T = torch.from_numpy
-    out = []
-    for dt, advn in ((torch.float64, advn64), (torch.float32, advn32)):
-        pol, crit = (copy.deepcopy(m).to(dt) for m in mods)
-        out.append(minibatch_ref_guide(pol, crit, T(b["obs"][rows]).to(dt), T(b["masks"][rows]), T(b["acts"][rows]),
-                                       T(b["old"][rows]).to(dt), T(advn[rows]).to(dt), T(b["tgt"][rows]).to(dt),
-                                       b["batch_size"], T(gvals[rows]).to(dt), strength, g.temperature, g.mask_entropy))
-    return out[0], out[1]
-
-
-@functools.lru_cache(maxsize=None)
 def guide_data(name):
     g = MANY if name == "rows8161" else GUIDE_CASES[name]
-    c = g.case
-    mods = build_modules(c)
-    pol64 = copy.deepcopy(mods[0]).double()
-    # without the options (a2, d64, edge) the batch keeps its rows with a single legal action; with them every row gets
-    # a second one (mask_entropy divides by log(legal)) and the old log probs are the tempered ones
-    plain = g.temperature == 1.0 and not g.mask_entropy
-    b = build_batch(c, pol64) if plain else build_option_batch(c, pol64, g.temperature)
-    bits, gvals = guide_stream(c, g.gscale, g.fp16)
-    r64, r32 = run_guide_refs(g, mods, b, gvals, STRENGTH)
-    rows = b["index"][b["start"]:b["start"] + c.n]
-    return {"g": g, "case": c, "mods": mods, "batch": b, "bits": bits, "gvals": gvals, "r64": r64, "r32": r32,
-            "rows": rows}
+    d = build_case(g.case, temperature=g.temperature, mask_entropy=g.mask_entropy, guide=(g.gscale, g.fp16, STRENGTH))
+    return dict(d, g=g)
 
 
 def sign_margin(r64, masks, delta=GUIDE_DELTA):
@@ -230,28 +124,27 @@ def assert_guide_side_conditions(d):
 
 
 # ------------------------------------------------------------------ CPU tests
+@pytest.mark.parametrize("name", list(GUIDE_CASES) + ["rows8161"])
+def test_reference_matches_golden(name):
+    """The float64 reference of every guided case against tests/golden/ppo_reference.npz (ppo_reference.check_golden)."""
+    check_golden(f"guide/{name}", guide_data(name))
+
+
 def test_guide_reference_reduces():
-    """minibatch_ref_guide at strength 0 gives minibatch_ref_opt's gradients and six metrics exactly, in float64 and
-    in fp32, with and without the options."""
+    """minibatch_ref with a guide at strength 0 gives its gradients, six metrics and scales without a guide exactly, in
+    float64 and in fp32, with and without the options: the guide branch does not perturb the rest."""
     import torch
-    for name in ("b17", "rows37"):
-        g = GUIDE_CASES[name]
-        c = g.case
-        mods = build_modules(c)
-        b = build_option_batch(c, copy.deepcopy(mods[0]).double(), g.temperature)
-        _, gvals = guide_stream(c, g.gscale, g.fp16)
-        rows = b["index"][b["start"]:b["start"] + c.n].astype(np.int64)
-        T = torch.from_numpy
-        for dt in (torch.float64, torch.float32):
-            args = lambda: [copy.deepcopy(mods[0]).to(dt), copy.deepcopy(mods[1]).to(dt), T(b["obs"][rows]).to(dt),  # noqa: E731
-                            T(b["masks"][rows]), T(b["acts"][rows]), T(b["old"][rows]).to(dt), T(b["adv"][rows]).to(dt),
-                            T(b["tgt"][rows]).to(dt), b["batch_size"]]
-            want = minibatch_ref_opt(*args(), g.temperature, g.mask_entropy)
-            got = minibatch_ref_guide(*args(), T(gvals[rows]).to(dt), 0.0, g.temperature, g.mask_entropy)
+    for name in ("b17", "rows37", "d64"):
+        d = guide_data(name)
+        options = dict(temperature=d["temperature"], mask_entropy=d["mask_entropy"])
+        wants = run_refs(d["case"], d["mods"], d["batch"], **options)
+        gots = run_refs(d["case"], d["mods"], d["batch"], guide_logits=d["gvals"], strength=0.0, **options)
+        for want, got in zip(wants, gots):
             assert torch.equal(got["grads"], want["grads"])
             for k in ("metrics", "scales"):
                 np.testing.assert_array_equal(got[k], want[k])
-            assert got["guiding"] > 0
+            assert got["head_bias_scale"] == want["head_bias_scale"]
+            assert got["guiding"] > 0 and "guiding" not in want
 
 
 def test_guide_stream_is_exact():
@@ -273,7 +166,7 @@ def test_guide_stream_is_exact():
 
 @pytest.mark.parametrize("name", list(GUIDE_CASES) + ["rows8161"])
 def test_guide_side_conditions_hold(name):
-    """test_ppo_variants' side conditions and the sign margin (0 violating elements; rows8161 is held to the first only:
+    """ppo_reference's side conditions and the sign margin (0 violating elements; rows8161 is held to the first only:
     its gradients are not checked), by the float64 reference alone."""
     import torch
     d = guide_data(name)
@@ -317,15 +210,8 @@ def test_guide_term_is_a_real_share(name):
     not hold for more actions): a kernel that ignores the guide cannot pass check_grads' normwise ceiling of 1e-4."""
     import torch
     d = guide_data(name)
-    g, c, b = d["g"], d["case"], d["batch"]
-    rows = b["index"][b["start"]:b["start"] + c.n].astype(np.int64)
-    adv64 = b["adv"].astype(np.float64)
-    advn = (adv64 - adv64.mean()) / (adv64.std(ddof=1) + 1e-8)
-    T = torch.from_numpy
-    dt = torch.float64
-    base = minibatch_ref_opt(copy.deepcopy(d["mods"][0]).to(dt), copy.deepcopy(d["mods"][1]).to(dt), T(b["obs"][rows]).to(dt),
-                             T(b["masks"][rows]), T(b["acts"][rows]), T(b["old"][rows]).to(dt), T(advn[rows]).to(dt),
-                             T(b["tgt"][rows]).to(dt), b["batch_size"], g.temperature, g.mask_entropy)
+    c = d["case"]
+    base, _ = run_refs(c, d["mods"], d["batch"], temperature=d["temperature"], mask_entropy=d["mask_entropy"])
     o = 0
     for pname, prm in d["mods"][0].named_parameters():
         k = prm.numel()
@@ -343,30 +229,20 @@ def guide_tensor(gpu, bits, fp16):
     return t.view(torch.float16 if fp16 else torch.bfloat16)
 
 
-def engine_minibatch_guided(gpu, p, c, b, guide, strength):
-    import torch
-    D = {k: torch.from_numpy(b[k]).to(gpu) for k in ("obs", "masks", "acts", "old", "adv", "tgt", "index")}
-    p.adv_normalizer(D["adv"])
-    p.minibatch(D["obs"], D["masks"], D["acts"], D["old"], D["adv"], D["tgt"], D["index"], b["start"], c.n,
-                b["batch_size"], guide_logits=guide, guiding_strength=strength)
-    torch.cuda.synchronize()
-    return D
-
-
 def check_guiding_metric(p, r64, r32, mode, tag, n):
     got = float(p.metrics.cpu().double().numpy()[M_GUIDE])
-    err, yard = abs(got - r64["guiding"]), abs(r32["guiding"] - r64["guiding"])
-    floor = scalar_floor(n, r64["guide_scale"])
-    print(f"{tag}: guiding loss {got:.9g} vs {r64['guiding']:.9g}, err {err:.2e}, torch fp32 {yard:.2e}, floor {floor:.2e}")
-    assert err <= factor(mode, n) * yard + floor, (
-        f"{tag}: guiding_loss: {got:.9g} vs {r64['guiding']:.9g}, err {err:.2e}, torch fp32 {yard:.2e}, floor "
-        f"{floor:.2e}, ratio {ratio_of(err, floor, yard):.2f}")
+    ok, figures = one_element("guiding_loss", got, r64["guiding"], r32["guiding"], r64["guide_scale"], mode, n)
+    print(f"{tag}: {figures}")
+    assert ok, f"{tag}: {figures}"
+
+
+def guided_engine_kw(d):
+    g = d["g"]
+    return dict(policy_temperature=g.temperature, mask_entropy=g.mask_entropy, infer_fp16=g.fp16)
 
 
 def make_guided_engine(gpu, d, mode):
-    g = d["g"]
-    return make_engine(gpu, d["case"], d["mods"], mode, policy_temperature=g.temperature, mask_entropy=g.mask_entropy,
-                       infer_fp16=g.fp16)
+    return make_engine(gpu, d["case"], d["mods"], mode, **guided_engine_kw(d))
 
 
 PAIRS = [(False, ()), (False, (64,)), (True, ()), (True, (64,))]
@@ -411,27 +287,19 @@ def _fused(p):
 @pytest.mark.parametrize("name", list(GUIDE_CASES))
 def test_minibatch_guided(gpu, name, mode):
     """One guided minibatch from zero_grad per case of GUIDE_CASES and GEMM mode at guiding_strength 0.5: gradients, the
-    six metrics and the fp32 forward against minibatch_ref_guide in float64 under test_ppo_variants' rules, and the
+    six metrics and the fp32 forward against minibatch_ref in float64 under ppo_reference's rules, and the
     guiding-loss metric under its one-element rule."""
     d = guide_data(name)
-    c, g = d["case"], d["g"]
     assert_guide_side_conditions(d)
-    p = make_guided_engine(gpu, d, mode)
-    p.zero_grad()
-    engine_minibatch_guided(gpu, p, c, d["batch"], guide_tensor(gpu, d["bits"], g.fp16), STRENGTH)
     tag = f"{name}/{MODE_IDS[mode]}"
-    errs = []
-    for fn in (lambda: check_grads(p.flat(grads=True).cpu(), d["r64"], d["r32"], d["mods"], mode, tag, c.n),
-               lambda: check_metrics(p, d["r64"], d["r32"], mode, tag, c.n),
-               lambda: check_guiding_metric(p, d["r64"], d["r32"], mode, tag, c.n),
-               lambda: check_forward(gpu, p, d, mode, tag)):
-        try:
-            fn()
-        except AssertionError as e:  # report every failing part of the case, not the first
-            errs.append(str(e))
-    assert "Guiding Loss" in p.read_metrics(reset=False)
-    p.close()
-    assert not errs, "\n".join(errs)
+
+    def named_metric(p):
+        assert "Guiding Loss" in p.read_metrics(reset=False), f"{tag}: no Guiding Loss among the named metrics"
+
+    run_engine_case(gpu, d, mode, tag, engine_kw=guided_engine_kw(d),
+                    guide=(guide_tensor(gpu, d["bits"], d["g"].fp16), STRENGTH),
+                    extra_checks=(lambda p: check_guiding_metric(p, d["r64"], d["r32"], mode, tag, d["case"].n),
+                                  named_metric))
 
 
 @pytest.mark.gpu
@@ -496,7 +364,7 @@ def test_guided_metrics_many_rows(gpu):
     assert why is None, why
     p = make_guided_engine(gpu, d, 2)
     p.zero_grad()
-    engine_minibatch_guided(gpu, p, c, d["batch"], guide_tensor(gpu, d["bits"], g.fp16), STRENGTH)
+    engine_minibatch(gpu, p, c, d["batch"], guide_tensor(gpu, d["bits"], g.fp16), STRENGTH)
     check_metrics(p, d["r64"], d["r32"], 2, "rows8161/h3", c.n)
     check_guiding_metric(p, d["r64"], d["r32"], 2, "rows8161/h3", c.n)
     p.close()

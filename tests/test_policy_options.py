@@ -5,8 +5,7 @@ The reference (PPOLearner.cpp): InferPolicyProbsFromModels (:97-102) and Learn (
 logits / temperature + (-1e10) * !mask -- an fp32 division of the fp32-converted logits, the mask term added after it;
 with maskEntropy (:426-438) each row's entropy is divided by log(the row's legal actions) instead of log(A).
 
-  * Learn: minibatch_ref_opt is test_ppo_variants.minibatch_ref with the two options (at (1.0, False) it reproduces
-    that function's gradients and metrics exactly, asserted here).  The GPU cases are held to that file's rules and
+  * Learn: ppo_reference.minibatch_ref with the two options.  The GPU cases are held to that module's rules and
     constants unchanged (check_grads, check_metrics, check_forward): the only differences come in through the
     reference's return values -- the entropy's rounding scale divides by log(legal count) per row when masked, and
     the z terms of every scale are the tempered logits.  Side conditions (the float64 reference alone decides them,
@@ -17,68 +16,13 @@ with maskEntropy (:426-438) each row's entropy is divided by log(the row's legal
     numpy rounds as the IEEE fp32 division it is.  The test first shows on the CPU that a multiply by the reciprocal
     would not pass it.
 """
-import copy
 import ctypes
-import functools
-import math
 
 import numpy as np
 import pytest
 
 import oracle
-from test_ppo_variants import (CLIP, ENT_SCALE, MODE_IDS, MODES, Case, build_batch, build_modules, check_forward,
-                               check_grads, check_metrics, engine_minibatch, make_engine, masked_probs, minibatch_ref,
-                               run_seq, side_conditions)
-
-
-# ------------------------------------------------------------------ the reference
-def minibatch_ref_opt(pol, crit, obs, masks, acts, old_logp, adv, target, batch_size, temperature=1.0,
-                      mask_entropy=False, clip=CLIP, ent_scale=ENT_SCALE):
-    """test_ppo_variants.minibatch_ref with PPOLearnerConfig::policyTemperature (PPOLearner.cpp:411-415) and
-    maskEntropy (:426-438); the same return values, the scales' z terms on the tempered logits and the entropy's
-    scale over log(legal count) per row when masked."""
-    import torch
-    for m in (pol, crit):
-        m.zero_grad(set_to_none=True)
-    n = obs.shape[0]
-    bsr = n / float(batch_size)
-    logits, pre_p = run_seq(pol, obs)
-    tl = logits / temperature
-    raw, probs = masked_probs(tl, masks)
-    logp = probs.gather(-1, acts.long().unsqueeze(-1)).squeeze(-1).log()
-    # the entropy's divisor: log A, or per row log(legal actions) (no guard: log 1 = 0 as in the reference)
-    log_cnt = masks.to(obs.dtype).sum(-1).log() if mask_entropy else math.log(probs.shape[1])
-    ent = (-(probs.log() * probs).sum(-1) / log_cnt).mean()
-    lr = logp - old_logp
-    ratio = lr.exp()
-    clipped = ratio.clamp(1 - clip, 1 + clip)
-    terms = torch.min(ratio * adv, clipped * adv)
-    pl = -terms.mean()
-    vals, pre_c = run_seq(crit, obs)
-    vals = vals.flatten()
-    closs = torch.nn.functional.mse_loss(vals, target) * bsr
-    ((pl - ent * ent_scale) * bsr + closs).backward()
-    kl = (lr.exp() - 1 - lr).mean()
-    frac = ((ratio - 1).abs() > clip).to(obs.dtype).mean()
-    f = lambda t: float(t.detach().double())  # noqa: E731
-    with torch.no_grad():
-        tl = tl.detach()
-        z = tl + -1e10 * masks.bool().logical_not()
-        zm = z.max(-1).values.abs()
-        ai = acts.long().unsqueeze(-1)
-        legal_a = masks.bool().gather(-1, ai).squeeze(-1)
-        lcond = 1 + (tl.gather(-1, ai).squeeze(-1).abs() + zm) * legal_a + old_logp.abs()
-        zc = 1 + tl.abs() * masks.bool() + zm.unsqueeze(-1)
-        s_ent = ((probs * (probs.log().abs() + 1) * zc).sum(-1) / log_cnt).mean()
-        s_crit = ((2 * (vals - target).abs() * (vals.abs() + target.abs()) + (vals - target) ** 2).mean()) * bsr
-        s_head = 2 * bsr / n * (vals.abs() + target.abs()).sum()
-    return {"grads": torch.cat([p.grad.reshape(-1) for m in (pol, crit) for p in m.parameters()]).clone(),
-            "metrics": np.array([f(ent), f(kl), f(pl), f(closs), f(ratio.mean()), f(frac)]),
-            "scales": np.array([f(s_ent), f(((ratio + 1) * lcond).mean()), f((adv.abs() * ratio * lcond).mean()),
-                                f(s_crit), f((ratio * lcond).mean()), 1.0]),
-            "head_bias_scale": f(s_head),
-            "pre": pre_p + pre_c, "logits": logits.detach(), "values": vals.detach(), "raw_probs": raw.detach(),
-            "ratio": ratio.detach()}
+from ppo_reference import MODE_IDS, MODES, Case, build_case, check_golden, run_engine_case, run_refs, side_conditions
 
 
 # ------------------------------------------------------------------ the cases
@@ -103,51 +47,9 @@ OPTION_CASES = {
 }
 
 
-def build_option_batch(c, pol64, temperature):
-    """build_batch, then (1) every row with a single legal action gets a second one (the next column), and (2) the
-    old log probs are rebuilt as the tempered float64 log prob plus build_batch's noise (recovered as its old log
-    prob minus its float64 log prob), so the ratios still straddle the clip range."""
-    import torch
-    b = build_batch(c, pol64)
-    with torch.no_grad():
-        logits = pol64(torch.from_numpy(b["obs"]).double())
-        ai = torch.from_numpy(b["acts"]).long().unsqueeze(-1)
-        _, probs = masked_probs(logits, torch.from_numpy(b["masks"]))
-        noise = b["old"].astype(np.float64) - probs.gather(-1, ai).squeeze(-1).log().numpy()
-        one = np.nonzero(b["masks"].sum(1) == 1)[0]
-        b["masks"][one, (b["masks"][one].argmax(1) + 1) % c.A] = 1
-        _, probs = masked_probs(logits / temperature, torch.from_numpy(b["masks"]))
-        lp = probs.gather(-1, ai).squeeze(-1).log().numpy()
-    b["old"] = (lp + noise).astype(np.float32)
-    return b
-
-
-def run_option_refs(c, mods, b, temperature, mask_entropy):
-    """test_ppo_variants.run_refs on minibatch_ref_opt: (float64 reference, torch fp32 yardstick)."""
-    import torch
-    rows = b["index"][b["start"]:b["start"] + c.n].astype(np.int64)
-    adv64 = b["adv"].astype(np.float64)
-    advn64 = (adv64 - adv64.mean()) / (adv64.std(ddof=1) + 1e-8)
-    advn32 = ((b["adv"] - b["adv"].mean()) / (b["adv"].std(ddof=1) + np.float32(1e-8))).astype(np.float32)
-    T = torch.from_numpy
-    out = []
-    for dt, advn in ((torch.float64, advn64), (torch.float32, advn32)):
-        pol, crit = (copy.deepcopy(m).to(dt) for m in mods)
-        out.append(minibatch_ref_opt(pol, crit, T(b["obs"][rows]).to(dt), T(b["masks"][rows]), T(b["acts"][rows]),
-                                     T(b["old"][rows]).to(dt), T(advn[rows]).to(dt), T(b["tgt"][rows]).to(dt),
-                                     b["batch_size"], temperature, mask_entropy))
-    return out[0], out[1]
-
-
-@functools.lru_cache(maxsize=None)
 def option_data(name):
     c, temperature, mask_entropy = OPTION_CASES[name]
-    mods = build_modules(c)
-    b = build_option_batch(c, copy.deepcopy(mods[0]).double(), temperature)
-    r64, r32 = run_option_refs(c, mods, b, temperature, mask_entropy)
-    rows = b["index"][b["start"]:b["start"] + c.n]
-    return {"case": c, "mods": mods, "batch": b, "r64": r64, "r32": r32, "rows": rows, "temperature": temperature,
-            "mask_entropy": mask_entropy}
+    return build_case(c, temperature=temperature, mask_entropy=mask_entropy)
 
 
 def assert_option_side_conditions(d):
@@ -223,24 +125,10 @@ def test_learner_default_config_options():
     assert learner.LearnerConfig().policy_temperature == 1.0 and learner.LearnerConfig().mask_entropy is False
 
 
-def test_reference_defaults_reproduce_minibatch_ref():
-    """minibatch_ref_opt at (1.0, False) gives minibatch_ref's gradients, metrics and scales exactly, in float64 and
-    in fp32."""
-    import torch
-    c = Case("b17", 168, 17, (64, 128), (65, 33), seed=1)
-    mods = build_modules(c)
-    b = build_batch(c, copy.deepcopy(mods[0]).double())
-    rows = b["index"][b["start"]:b["start"] + c.n].astype(np.int64)
-    T = torch.from_numpy
-    for dt in (torch.float64, torch.float32):
-        args = lambda: [copy.deepcopy(mods[0]).to(dt), copy.deepcopy(mods[1]).to(dt), T(b["obs"][rows]).to(dt),  # noqa: E731
-                        T(b["masks"][rows]), T(b["acts"][rows]), T(b["old"][rows]).to(dt), T(b["adv"][rows]).to(dt),
-                        T(b["tgt"][rows]).to(dt), b["batch_size"]]
-        want, got = minibatch_ref(*args()), minibatch_ref_opt(*args(), 1.0, False)
-        assert torch.equal(got["grads"], want["grads"])
-        for k in ("metrics", "scales"):
-            np.testing.assert_array_equal(got[k], want[k])
-        assert got["head_bias_scale"] == want["head_bias_scale"]
+@pytest.mark.parametrize("name", list(OPTION_CASES))
+def test_reference_matches_golden(name):
+    """The float64 reference of every option case against tests/golden/ppo_reference.npz (ppo_reference.check_golden)."""
+    check_golden(f"option/{name}", option_data(name))
 
 
 def test_reference_options_change_the_result():
@@ -249,8 +137,8 @@ def test_reference_options_change_the_result():
     d = option_data("rows37_t2.5_me")
     c, b = d["case"], d["batch"]
     assert (b["masks"][d["rows"]].sum(1) < c.A).all()
-    r_t, _ = run_option_refs(c, d["mods"], b, 2.5, False)
-    base, _ = run_option_refs(c, d["mods"], b, 1.0, False)
+    r_t, _ = run_refs(c, d["mods"], b, temperature=2.5, mask_entropy=False)
+    base, _ = run_refs(c, d["mods"], b, temperature=1.0, mask_entropy=False)
     assert d["r64"]["metrics"][0] > r_t["metrics"][0] > 0
     npol = sum(q.numel() for q in d["mods"][0].parameters())
     for a, w in ((d["r64"], r_t), (r_t, base)):
@@ -277,25 +165,12 @@ def test_option_side_conditions_hold(name):
 @pytest.mark.parametrize("name", list(OPTION_CASES))
 def test_minibatch_with_options(gpu, name, mode):
     """One minibatch from zero_grad per case of OPTION_CASES and GEMM mode on an engine built with the case's
-    policy_temperature / mask_entropy: gradients and the six metrics against minibatch_ref_opt in float64 under
-    test_ppo_variants' rules, the fp32 forward (raw logits: rlgpu_ppo_forward applies no temperature) as there."""
+    policy_temperature / mask_entropy: gradients and the six metrics against minibatch_ref in float64 under
+    ppo_reference's rules, the fp32 forward (raw logits: rlgpu_ppo_forward applies no temperature) as there."""
     d = option_data(name)
-    c = d["case"]
     assert_option_side_conditions(d)
-    p = make_engine(gpu, c, d["mods"], mode, policy_temperature=d["temperature"], mask_entropy=d["mask_entropy"])
-    p.zero_grad()
-    engine_minibatch(gpu, p, c, d["batch"])
-    tag = f"{name}/{MODE_IDS[mode]}"
-    errs = []
-    for fn in (lambda: check_grads(p.flat(grads=True).cpu(), d["r64"], d["r32"], d["mods"], mode, tag, c.n),
-               lambda: check_metrics(p, d["r64"], d["r32"], mode, tag, c.n),
-               lambda: check_forward(gpu, p, d, mode, tag)):
-        try:
-            fn()
-        except AssertionError as e:  # report every failing part of the case, not the first
-            errs.append(str(e))
-    p.close()
-    assert not errs, "\n".join(errs)
+    run_engine_case(gpu, d, mode, f"{name}/{MODE_IDS[mode]}",
+                    engine_kw=dict(policy_temperature=d["temperature"], mask_entropy=d["mask_entropy"]))
 
 
 # ------------------------------------------------------------------ GPU: the sampler

@@ -32,11 +32,15 @@ def torch_models(ppo):
     return ppo.torch_module(0), ppo.torch_module(1)
 
 
-def ref_minibatch(pol, crit, obs, masks, acts, old_logp, adv, target, batch_size, clip=0.2, ent_scale=0.035):
-    """PPOLearner::Learn minibatch body (PPOLearner.cpp:341-475), fp32 torch."""
+def ref_minibatch(pol, crit, obs, masks, acts, old_logp, adv, target, batch_size, clip=0.2, ent_scale=0.035,
+                  shared=None):
+    """PPOLearner::Learn minibatch body (PPOLearner.cpp:341-475), fp32 torch; shared: the shared head both models
+    read (:395-398 one shared forward per minibatch, :403/:474 both heads read it, :498 one backward)."""
     import torch
     n = obs.shape[0]
     bsr = n / float(batch_size)
+    if shared is not None:
+        obs = shared(obs)
     logits = pol(obs)
     logits = logits + -1e10 * masks.bool().logical_not()
     probs = torch.softmax(logits, -1).clamp(1e-11, 1.0)

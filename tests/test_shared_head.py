@@ -15,28 +15,10 @@ tolerances as tests/test_ppo.py.
 import numpy as np
 import pytest
 
-from test_ppo import assert_grads_close, make_batch
+from test_ppo import assert_grads_close, make_batch, ref_minibatch
 
 EXAMPLE = dict(shared_layers=(384, 384), policy_layers=(384, 384, 384), critic_layers=(384, 384, 384))
 SMALL = dict(shared_layers=(96, 64), policy_layers=(80,), critic_layers=(48, 40))
-
-
-def _ref_minibatch(shared, pol, crit, obs, masks, acts, old_logp, adv, target, batch_size, clip=0.2, ent_scale=0.035):
-    """PPOLearner::Learn minibatch body with a shared head (PPOLearner.cpp:395-498), fp32 torch."""
-    import math
-
-    import torch
-    n = obs.shape[0]
-    bsr = n / float(batch_size)
-    feats = shared(obs)
-    logits = pol(feats) + -1e10 * masks.bool().logical_not()
-    probs = torch.softmax(logits, -1).clamp(1e-11, 1.0)
-    logp = probs.gather(-1, acts.long().unsqueeze(-1)).squeeze(-1).log()
-    ent = (-(probs.log() * probs).sum(-1) / math.log(probs.shape[1])).mean()
-    ratio = (logp - old_logp).exp()
-    pl = -torch.min(ratio * adv, ratio.clamp(1 - clip, 1 + clip) * adv).mean()
-    closs = torch.nn.functional.mse_loss(crit(feats).flatten(), target) * bsr
-    ((pl - ent * ent_scale) * bsr + closs).backward()
 
 
 def test_shared_param_counts_known_answer_cpu():
@@ -87,7 +69,7 @@ def test_shared_minibatch_grads_match_torch(gpu, mode, arch, n, slope):
     obs, masks, acts, old, adv, tgt = make_batch(rng, n)
     T = lambda a: torch.from_numpy(a)  # noqa: E731
     advn = ((adv - adv.mean()) / (adv.std(ddof=1) + 1e-8)).astype(np.float32)
-    _ref_minibatch(sh, pol, crit, T(obs), T(masks), T(acts), T(old), T(advn), T(tgt), n)
+    ref_minibatch(pol, crit, T(obs), T(masks), T(acts), T(old), T(advn), T(tgt), n, shared=sh)
     d = [T(v).to(gpu) for v in (obs, masks, acts, old, adv, tgt)]
     p.adv_normalizer(d[4])
     p.zero_grad()
@@ -116,7 +98,7 @@ def test_shared_optimizer_step_matches_torch_adamw(gpu):
         advn = ((adv - adv.mean()) / (adv.std(ddof=1) + 1e-8)).astype(np.float32)
         for o in opts:
             o.zero_grad(set_to_none=True)
-        _ref_minibatch(sh, pol, crit, T(obs), T(masks), T(acts), T(old), T(advn), T(tgt), 400)
+        ref_minibatch(pol, crit, T(obs), T(masks), T(acts), T(old), T(advn), T(tgt), 400, shared=sh)
         for m in (pol, crit, sh):
             torch.nn.utils.clip_grad_norm_(m.parameters(), 0.5)
         for o in opts:
