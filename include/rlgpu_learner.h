@@ -118,7 +118,9 @@ typedef struct {
                                       mode or old version playing, and the entry's own conditions -- and the
                                       automatic choice's path otherwise.  The report then has env_launch_arenas =
                                       num_arenas and env_kernel_ms (min / median / max alike) = the launch's time /
-                                      rollout_len, the in-workgroup inference included */
+                                      rollout_len, the in-workgroup inference included.  With obs standardisation
+                                      on (rlgpu_learner_set_obs_standardization) every value takes one launch per
+                                      step: each step's statistic draws rows of all arenas */
     float policy_temperature;      /* rlgpu_ppo_config.policy_temperature (PPOLearnerConfig::policyTemperature):
                                       collection, old versions and Learn alike; 0 = 1 */
     int32_t mask_entropy;          /* rlgpu_ppo_config.mask_entropy (PPOLearnerConfig::maskEntropy) */
@@ -254,6 +256,41 @@ int rlgpu_learner_set_old_team(rlgpu_learner* h, int32_t team);
  * logits, [rows][RLGPU_ACTIONS] in the 16-bit inference format (NULL / 0 before the first guided learn). */
 int rlgpu_learner_set_guide(rlgpu_learner* h, const float* d_policy_params, float guiding_strength);
 int rlgpu_learner_guide_logits(rlgpu_learner* h, const uint16_t** d_logits, int64_t* rows);
+
+/* Obs standardisation (LearnerConfig::standardizeObs / minObsSTD / maxObsMeanRange / maxObsSamples; Learner.cpp:679-693,
+ * Util/WelfordStat.h:69-243).  Every obs set the policy is about to see -- row 0, then each step's appended row -- takes
+ * one rlgpu_obs_stat_step on the learner's stream: a BatchedWelfordStat over the obs columns (int64 count, fp64 means and
+ * m2) is incremented from S = min(players, max_samples) rows drawn with replacement, then every row becomes
+ * x * inv[j] + shift[j] in fp32 (untouched while count < 2).  The rewritten rows feed the policy (an old version too)
+ * and are what the critic and the learn phase train on; the truncation rows (trunc_obs) and the skill matches stay raw,
+ * as in the reference.  The collection then runs one launch per step (rlgpu_learner_config.collect_groups).
+ * min_std finite and > 0, max_mean_range finite and >= 0, max_samples >= 1 (RLGPU_ERR_INVALID_ARG); RLGPU_ERR_UNSUPPORTED
+ * with frame_stack > 1 or world > 1; RLGPU_ERR_STATE, like set_obs_stat, once the first collection has started (row 0 has
+ * then been taken with the state there was).  enable = 0 turns it off (the other arguments are ignored).
+ * get / set_obs_stat: the statistic ([RLGPU_OBS] doubles each; RUNNING_STATS.json "obs_stat": means, vars = m2, count);
+ * RLGPU_ERR_STATE while the feature is off.  get synchronises the learner's stream. */
+int rlgpu_learner_set_obs_standardization(rlgpu_learner* h, int32_t enable, float min_std, float max_mean_range,
+                                          int32_t max_samples);
+int rlgpu_learner_get_obs_stat(rlgpu_learner* h, int64_t* count, double* means, double* m2s);
+int rlgpu_learner_set_obs_stat(rlgpu_learner* h, int64_t count, const double* means, const double* m2s);
+
+/* The building blocks of the above.  A state of `width` columns is one device block of rlgpu_obs_stat_bytes(width)
+ * bytes, 8-byte aligned: int64 count, double mean[width], double m2[width], then scratch every step rewrites (the fp32
+ * coefficient table and its "active" word); zero-filled it is a fresh BatchedWelfordStat, and the first 8 + 16 * width
+ * bytes are all a resumed run needs.
+ * rlgpu_obs_stat_step: one reference step on d_obs [rows][width] (4-byte aligned), in place, two launches on `stream`.
+ * Increment: for i in 0 .. S - 1, S = min(rows, max_samples), row r_i = rlgpu_obs_sample_rows(seed, count, ...)[i]; per
+ * column delta = (double)x - mean, deltaN = delta / (double)(count + 1), mean += deltaN, m2 += (delta * deltaN) *
+ * (double)count; count++ after each row.  Normalise (count >= 2): var = m2 / (count - 1), std = var > 0 ? sqrt(var) : 1,
+ * inv = 1.0f / (float)max(std, min_std), shift = -(float)clamp(mean, -max_mean_range, max_mean_range) * inv, then
+ * x = x * inv + shift -- no operation contracted, each rounds on its own.
+ * rlgpu_obs_sample_rows (host, no GPU): the n rows drawn when the state's count is `count`: draw i is the first output
+ * word u of Philox4x32-10 at counter count + i under a key derived from seed and stream tag 3 (disjoint from the
+ * sampler's, the arenas' and rlgpu_host_uniform's streams), row = (uint64(u) * rows) >> 32. */
+int64_t rlgpu_obs_stat_bytes(int32_t width);
+int rlgpu_obs_stat_step(void* d_state, float* d_obs, int32_t rows, int32_t width, uint64_t seed, int32_t max_samples,
+                        float max_mean_range, float min_std, void* stream);
+int rlgpu_obs_sample_rows(uint64_t seed, int64_t count, int32_t rows, int32_t n, int32_t* out);
 
 /* Host plugins and a StepCallbackFn inside the collection loop (Learner.cpp:676-861; EnvSet.cpp:163-255).
  * With a hook set, every collection step runs: the env step WITHOUT resetting terminated arenas, then

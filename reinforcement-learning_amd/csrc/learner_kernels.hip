@@ -1,6 +1,8 @@
 // learner_kernels.hip -- small device helpers of the C++ host Learner (host/learner.cpp):
-// truncated-row compaction, index gathers / scatters, self-play row lists, fp64 moments.
+// truncated-row compaction, index gathers / scatters, self-play row lists, fp64 moments, obs standardisation.
 #include <hipcub/hipcub.hpp>
+
+#include <algorithm>
 
 #include "common.hpp"
 #include "learner_kernels.hpp"
@@ -263,7 +265,180 @@ struct IsTrunc {
     __device__ bool operator()(const int32_t& i) const { return t[i] == 2; }
 };
 
+// ---- obs standardisation (LearnerConfig::standardizeObs; Learner.cpp:679-693, Util/WelfordStat.h:69-243)
+// Philox4x32-10 of a 64-bit counter, first output word; the same function on the host (obs_sample_row)
+__host__ __device__ inline uint32_t obs_philox(uint64_t key, uint64_t ctr) {
+    uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+    uint32_t x0 = (uint32_t)ctr, x1 = (uint32_t)(ctr >> 32), x2 = 0, x3 = 0;
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * x0, p1 = (uint64_t)0xCD9E8D57u * x2;
+        const uint32_t y0 = (uint32_t)(p1 >> 32) ^ x1 ^ k0, y1 = (uint32_t)p1, y2 = (uint32_t)(p0 >> 32) ^ x3 ^ k1,
+                       y3 = (uint32_t)p0;
+        x0 = y0;
+        x1 = y1;
+        x2 = y2;
+        x3 = y3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return x0;
+}
+__host__ __device__ inline int32_t obs_draw(uint64_t key, uint64_t ctr, int32_t rows) {
+    return (int32_t)(((uint64_t)obs_philox(key, ctr) * (uint64_t)(uint32_t)rows) >> 32);
+}
+
+// the state block's parts (obs_stat_bytes): int64 count | double mean[W] | double m2[W] | float coef[2][W] | int32 active
+__host__ __device__ inline double* obs_mean(void* st) { return (double*)((char*)st + 8); }
+__host__ __device__ inline float* obs_coef(void* st, int W) { return (float*)((char*)st + 8 + 16 * (size_t)W); }
+__host__ __device__ inline int32_t* obs_active(void* st, int W) { return (int32_t*)((char*)st + 8 + 24 * (size_t)W); }
+
+// BatchedWelfordStat::IncrementRow over S drawn rows, then the coefficients NormalizeInPlace derives from the new
+// state.  One workgroup, lane j = column j: the columns are independent, so each lane's sequential walk over the
+// rows in draw order is the reference's order.  The draws are made once per chunk of kObsChunk (all lanes, into
+// LDS); a lane has the next kObsAhead rows' elements in flight while it runs the dependent fp64 chain of the
+// kObsAhead before them.  No contraction: every fp64 / fp32 operation rounds on its own, as the reference's
+// /fp:precise build does.
+constexpr int kObsLanes = 192, kObsChunk = 768, kObsAhead = 16;
+__global__ void __launch_bounds__(kObsLanes) k_obs_stat_update(void* st, const float* obs, int P, int W, int S, uint64_t key,
+                                                               float max_mean, float min_std) {
+#pragma clang fp contract(off)
+    __shared__ int32_t rows[kObsChunk];
+    int64_t* pcount = (int64_t*)st;
+    const int64_t c0 = *pcount;
+    double* means = obs_mean(st);
+    double* m2s = means + W;
+    for (int j0 = 0; j0 < W; j0 += kObsLanes) {  // W <= kObsLanes in practice: one pass
+        const int j = j0 + threadIdx.x;
+        const bool on = j < W;
+        double mean = on ? means[j] : 0.0, m2 = on ? m2s[j] : 0.0;
+        for (int i0 = 0; i0 < S; i0 += kObsChunk) {
+            const int n = min(kObsChunk, S - i0);
+            __syncthreads();  // the chunk before is consumed
+            for (int i = threadIdx.x; i < n; i += kObsLanes) rows[i] = obs_draw(key, (uint64_t)(c0 + i0 + i), P);
+            __syncthreads();
+            if (!on) continue;
+            float x[kObsAhead], nx[kObsAhead];
+#pragma unroll
+            for (int u = 0; u < kObsAhead; u++) nx[u] = u < n ? obs[(int64_t)rows[u] * W + j] : 0.f;
+            for (int i = 0; i < n; i += kObsAhead) {
+#pragma unroll
+                for (int u = 0; u < kObsAhead; u++) x[u] = nx[u];
+#pragma unroll
+                for (int u = 0; u < kObsAhead; u++) {  // the group after this one, loaded under this one's chain
+                    const int k = i + kObsAhead + u;
+                    nx[u] = k < n ? obs[(int64_t)rows[k] * W + j] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < kObsAhead; u++) {
+                    if (i + u < n) {  // wave-uniform
+                        const int64_t cnt = c0 + i0 + i + u;
+                        const double delta = (double)x[u] - mean;
+                        const double deltaN = delta / (double)(cnt + 1);
+                        mean += deltaN;
+                        m2 += (delta * deltaN) * (double)cnt;
+                    }
+                }
+            }
+        }
+        if (!on) continue;
+        means[j] = mean;
+        m2s[j] = m2;
+        const int64_t cn = c0 + S;
+        float inv = 1.f, shift = 0.f;
+        if (cn >= 2) {
+            const double var = m2 / (double)(cn - 1);
+            const double sd = var > 0 ? sqrt(var) : 1.0;
+            const double mn = (double)min_std, mr = (double)max_mean;
+            const double csd = sd > mn ? sd : mn;                  // RS_MAX
+            const double lo = mean > -mr ? mean : -mr;            // RS_CLAMP = RS_MIN(RS_MAX(v, lo), hi)
+            const double cmean = lo < mr ? lo : mr;
+            inv = 1.0f / (float)csd;
+            shift = -(float)cmean * inv;
+        }
+        float* coef = obs_coef(st, W);
+        coef[j] = inv;
+        coef[W + j] = shift;
+    }
+    __syncthreads();  // every lane has read the old count
+    if (threadIdx.x == 0) {
+        *pcount = c0 + S;
+        *obs_active(st, W) = c0 + S >= 2 ? 1 : 0;
+    }
+}
+
+// x <- x * inv[col] + shift[col] over the flat [n] array, col = index % W: 16-byte vectors from the first aligned
+// element on, the elements before it and the last n % 4 by the first lanes of workgroup 0.  A workgroup takes
+// kStdVecs * 256 consecutive vectors, every lane its kStdVecs loads before the first store.  Returns at once while the
+// statistic is inactive (count < 2).
+constexpr int kStdVecs = 4;
+__global__ void __launch_bounds__(256) k_obs_standardize_rows(float* x, int64_t n, int W, const void* st) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) float coef[];  // [2][W]
+    if (*obs_active(const_cast<void*>(st), W) == 0) return;
+    const float* g = obs_coef(const_cast<void*>(st), W);
+    for (int k = threadIdx.x; k < 2 * W; k += blockDim.x) coef[k] = g[k];
+    __syncthreads();
+    const int64_t lead = (int64_t)(((16 - ((uintptr_t)x & 15)) & 15) / 4);
+    const int64_t head = lead < n ? lead : n;
+    const int64_t nvec = (n - head) / 4;
+    const int64_t tail0 = head + 4 * nvec;
+    if (blockIdx.x == 0) {
+        const int64_t edge = head + (n - tail0);  // < 8 elements
+        if ((int64_t)threadIdx.x < edge) {
+            const int64_t e = (int64_t)threadIdx.x < head ? (int64_t)threadIdx.x : tail0 + (threadIdx.x - head);
+            const int c = (int)(e % W);
+            x[e] = x[e] * coef[c] + coef[W + c];
+        }
+    }
+    float4* xv = reinterpret_cast<float4*>(x + head);
+    const int64_t v0 = (int64_t)blockIdx.x * (kStdVecs * 256) + threadIdx.x;
+    float4 q[kStdVecs];
+#pragma unroll
+    for (int k = 0; k < kStdVecs; k++)
+        if (v0 + k * 256 < nvec) q[k] = xv[v0 + k * 256];
+    int c0 = (int)((head + 4 * v0) % W);
+    const int hop = (4 * 256) % W;  // columns between a lane's consecutive vectors
+#pragma unroll
+    for (int k = 0; k < kStdVecs; k++) {
+        if (v0 + k * 256 < nvec) {
+            float* f = reinterpret_cast<float*>(&q[k]);
+            int c = c0;
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                f[u] = f[u] * coef[c] + coef[W + c];
+                c = c + 1 == W ? 0 : c + 1;
+            }
+            xv[v0 + k * 256] = q[k];
+        }
+        c0 = c0 + hop >= W ? c0 + hop - W : c0 + hop;
+    }
+}
+
 }  // namespace
+
+size_t obs_stat_bytes(int W) { return 8 + 24 * (size_t)W + 8; }
+uint64_t obs_stat_key(uint64_t seed) {
+    auto mix = [](uint64_t x) {  // splitmix64
+        x += 0x9E3779B97F4A7C15ull;
+        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+        return x ^ (x >> 31);
+    };
+    return mix(seed ^ mix(kObsStatStream << 48));
+}
+int32_t obs_sample_row(uint64_t key, int64_t counter, int32_t rows) { return obs_draw(key, (uint64_t)counter, rows); }
+void obs_stat_update(void* state, const float* obs, int P, int W, int S, uint64_t key, float max_mean, float min_std,
+                     hipStream_t s) {
+    hipLaunchKernelGGL(k_obs_stat_update, dim3(1), dim3(kObsLanes), 0, s, state, obs, P, W, S, key, max_mean, min_std);
+    RLGPU_CHECK_HIP(hipGetLastError());
+}
+void obs_standardize_rows(float* obs, int64_t n, int W, const void* state, hipStream_t s) {
+    if (n <= 0) return;
+    RLGPU_REQUIRE(n / 4 / (kStdVecs * 256) < (int64_t)1 << 31, "obs_standardize_rows: too many elements for one launch");
+    const unsigned blocks = std::max(1u, ceil_div(n / 4, kStdVecs * 256));  // n / 4 >= the vectors of any alignment
+    hipLaunchKernelGGL(k_obs_standardize_rows, dim3(blocks), dim3(256), 2 * (size_t)W * sizeof(float), s, obs, n, W, state);
+    RLGPU_CHECK_HIP(hipGetLastError());
+}
 
 void gather_f32(const float* src, const int32_t* idx, int64_t n, float* dst, hipStream_t s) {
     if (n <= 0) return;

@@ -38,6 +38,25 @@ void stack_frames(const float* cur, const float* trunc, const int8_t* codes, flo
 void host_step_finish(const uint8_t* arena_terms, int8_t* codes, const float* rewards, float* rew_out, const float* obs,
                       float* trunc_env, float* trunc_out, int P, int obs_w, hipStream_t s);
 
+// ---- obs standardisation (LearnerConfig::standardizeObs: Learner.cpp:679-693, Util/WelfordStat.h:69-243)
+// The state block of a W-column BatchedWelfordStat, obs_stat_bytes(W) bytes, zero-filled = fresh:
+//   int64 count | double mean[W] | double m2[W]   (the statistic: all a checkpoint or a resumed run needs)
+//   float coef[2][W] (inv, shift) | int32 active  (rewritten by every update before they are read)
+size_t obs_stat_bytes(int W);
+// The row draws are Philox4x32-10 under a key of their own: splitmix64(seed ^ splitmix64(kObsStatStream << 48)), the
+// stream numbering of rlgpu_host_uniform (1 self-play, 2 skill runs); draw i of a step that starts at `count` has the
+// counter count + i and picks row (u * rows) >> 32 of its first output word u.
+constexpr uint64_t kObsStatStream = 3;
+uint64_t obs_stat_key(uint64_t seed);
+int32_t obs_sample_row(uint64_t key, int64_t counter, int32_t rows);  // host
+// IncrementRow over S rows of obs [P][W] drawn with replacement, in draw order, then coef / active from the new
+// state: inv = 1 / (float)max(std, min_std), shift = -(float)clamp(mean, +-max_mean) * inv; active = count >= 2
+void obs_stat_update(void* state, const float* obs, int P, int W, int S, uint64_t key, float max_mean, float min_std,
+                     hipStream_t s);
+// obs[e] = obs[e] * inv[e % W] + shift[e % W] (a rounded product, a rounded add) over n = rows * W floats in place;
+// nothing while the state is inactive.  obs 4-byte aligned: a row pitch of 668 B leaves rows off the 16-byte grid
+void obs_standardize_rows(float* obs, int64_t n, int W, const void* state, hipStream_t s);
+
 // ---- reference experience mode (complete trajectories with carry-over, Learner.cpp:504-547,823-861)
 // Trajectory records, structure of arrays (capacity rows each), appended in the reference's order:
 // by the step a trajectory ends, then by player index (combinedTraj.Append in the newPlayerIndices loop).

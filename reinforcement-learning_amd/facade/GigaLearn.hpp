@@ -691,7 +691,11 @@ inline void Learner::ValidateConfig(const LearnerConfig& c) {
     if (c.renderMode) bad("renderMode is not supported (the RLBot render path is out of this engine's scope)");
     if (c.deviceType == LearnerDeviceType::CPU) bad("deviceType CPU: this engine runs on the GPU only");
     if (c.numGames <= 0) bad("numGames must be positive");
-    if (c.standardizeObs) bad("standardizeObs is not supported (obs standardisation is not on the device path)");
+    // standardizeObs: rlgpu_learner_set_obs_standardization's checks, by the reference's field names
+    if (c.standardizeObs && !(std::isfinite(c.minObsSTD) && c.minObsSTD > 0)) bad("minObsSTD must be finite and > 0");
+    if (c.standardizeObs && !(std::isfinite(c.maxObsMeanRange) && c.maxObsMeanRange >= 0))
+        bad("maxObsMeanRange must be finite and >= 0");
+    if (c.standardizeObs && c.maxObsSamples < 1) bad("maxObsSamples must be >= 1");
     if (!std::isfinite(c.ppo.policyTemperature) || !(c.ppo.policyTemperature > 0))
         bad("ppo.policyTemperature must be finite and > 0");
     if (c.ppo.useGuidingPolicy && !c.ppo.useHalfPrecision)
@@ -734,6 +738,9 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
                                 std::chrono::system_clock::now().time_since_epoch()).count();
     std::printf("Learner::Learner():\n\tCheckpoint Save/Load Dir: %s\n", config.checkpointFolder.string().c_str());
     if (config.sendMetrics) std::printf("\t(metrics are printed; the Python metrics receiver is not part of this engine)\n");
+    if (config.standardizeObs && options.world > 1)
+        throw std::invalid_argument("LearnerConfig: standardizeObs with world > 1 is not supported (per-rank obs statistics "
+                                    "would diverge)");
     if (options.stream) stream_ = options.stream;
     else detail::HipOk(hipStreamCreate(&stream_), "stream");
     LoadMeshes();
@@ -840,6 +847,10 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
                                               config.tsPerVersion, config.skillTracker);
     }
     if (config.ppo.useGuidingPolicy) LoadGuidingPolicy();  // PPOLearner ctor (PPOLearner.cpp:35-38)
+    if (config.standardizeObs)  // obsStat (Learner.cpp:111-112), before Load reads its "obs_stat"
+        RLGC::RlgpuCheck(rlgpu_learner_set_obs_standardization(h_, 1, config.minObsSTD, config.maxObsMeanRange,
+                                                               config.maxObsSamples),
+                         "standardizeObs");
     if (!config.checkpointFolder.empty()) Load();
     if (versionMgr) versionMgr->LoadVersions((int64_t)totalTimesteps);
 }
@@ -1049,6 +1060,18 @@ inline void Learner::SaveStats(const std::filesystem::path& path) {
     if (config.standardizeReturns)  // WelfordStat::ToJSON
         j += ",\n    \"return_stat\": {\"mean\": " + detail::Num(st.return_mean) + ", \"var\": " + detail::Num(st.return_m2) +
              ", \"count\": " + std::to_string(st.return_n) + "}";
+    if (config.standardizeObs) {  // BatchedWelfordStat::ToJSON (Learner.cpp:184-185): vars = the running m2
+        int64_t n = 0;
+        std::vector<double> mean(RLGPU_OBS), m2(RLGPU_OBS);
+        RLGC::RlgpuCheck(rlgpu_learner_get_obs_stat(h_, &n, mean.data(), m2.data()), "obs stat");
+        auto list = [](const std::vector<double>& v) {
+            std::string o = "[";
+            for (size_t k = 0; k < v.size(); k++) o += (k ? ", " : "") + detail::Num(v[k]);
+            return o + "]";
+        };
+        j += ",\n    \"obs_stat\": {\"means\": " + list(mean) + ", \"vars\": " + list(m2) + ", \"count\": " +
+             std::to_string(n) + "}";
+    }
     if (versionMgr) versionMgr->AddRunningStatsToJSON(j);
     j += "\n}\n";
     detail::WriteFile(path, j.data(), j.size());
@@ -1070,6 +1093,15 @@ inline void Learner::LoadStats(const std::filesystem::path& path) {
         st.return_n = r["count"].Int();
     }
     RLGC::RlgpuCheck(rlgpu_learner_set_stats(h_, &st), "stats");
+    if (config.standardizeObs && j.Has("obs_stat")) {  // BatchedWelfordStat::ReadFromJSON (Learner.cpp:214-215)
+        const detail::Json& o = j["obs_stat"];
+        std::vector<double> mean, m2;
+        for (auto& x : o["means"].arr) mean.push_back(x.Num());
+        for (auto& x : o["vars"].arr) m2.push_back(x.Num());
+        if (mean.size() != (size_t)RLGPU_OBS || m2.size() != (size_t)RLGPU_OBS)
+            throw std::runtime_error(path.string() + ": obs_stat does not hold " + std::to_string(RLGPU_OBS) + " means and vars");
+        RLGC::RlgpuCheck(rlgpu_learner_set_obs_stat(h_, o["count"].Int(), mean.data(), m2.data()), "obs stat");
+    }
     if (versionMgr) versionMgr->LoadRunningStatsFromJSON(j);
 }
 

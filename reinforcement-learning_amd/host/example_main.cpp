@@ -172,6 +172,8 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(argv[i], "--fp32-inference")) cfg.ppo.useHalfPrecision = false;
             else if (!std::strcmp(argv[i], "--policy-temperature")) cfg.ppo.policyTemperature = std::strtof(next(), nullptr);
             else if (!std::strcmp(argv[i], "--mask-entropy")) cfg.ppo.maskEntropy = true;
+            else if (!std::strcmp(argv[i], "--standardize-obs")) cfg.standardizeObs = true;  // LearnerConfig::standardizeObs
+            else if (!std::strcmp(argv[i], "--min-obs-std")) cfg.minObsSTD = std::strtof(next(), nullptr);
             else if (!std::strcmp(argv[i], "--guiding-policy")) {  // PPOLearnerConfig::useGuidingPolicy / guidingPolicyPath
                 cfg.ppo.useGuidingPolicy = true;
                 cfg.ppo.guidingPolicyPath = next();
@@ -202,6 +204,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "%s\nusage: %s [--iterations N] [--arenas A] [--rollout T] [--trajectories] [--f32-gemm] "
                                  "[--c2-model] [--seed S] [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] "
                                  "[--self-play] [--fp32-inference] [--policy-temperature X] [--mask-entropy] "
+                                 "[--standardize-obs [--min-obs-std X]] "
                                  "[--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm] [--guiding-policy DIR "
                                  "[--guiding-strength X]] [--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);
             return 2;

@@ -375,7 +375,8 @@ int Learner::CollectGroups() const {
     const int want = cfg_.collect_groups > 0                   ? cfg_.collect_groups
                      : cfg_.num_arenas >= kAutoCollectArenas ? kAutoCollectGroups
                                                              : 1;
-    if (want <= 1 || hook_ || K_ > 1 || trajMode() || !rlgpu_ppo_fused_infer(ppo_->handle(), 0)) return 1;
+    // obs standardisation: every step's statistic draws rows of all arenas, so the groups cannot run ahead of each other
+    if (want <= 1 || hook_ || K_ > 1 || trajMode() || obsStd_ || !rlgpu_ppo_fused_infer(ppo_->handle(), 0)) return 1;
     if (cfg_.num_arenas % (4 * want) != 0) return 1;
     return want;
 }
@@ -456,7 +457,8 @@ void Learner::CollectGrouped(int G) {
 constexpr bool kAutoCollectLoop = true;
 
 bool Learner::CollectLoopOk() const {
-    if (hook_ || K_ > 1 || trajMode() || oldTeam_ >= 0) return false;
+    // (obs standardisation needs all arenas' rows between two steps, which no workgroup of the loop has)
+    if (hook_ || K_ > 1 || trajMode() || oldTeam_ >= 0 || obsStd_) return false;
     return rlgpu_envset_collect_loop_ok(env_->handle(), ppo_->handle()) != 0;
 }
 
@@ -475,6 +477,11 @@ void Learner::CollectLoop() {
 }
 
 void Learner::Collect() {
+    collected_ = true;
+    if (obsStd_ && row0Raw_) {  // lazily, so a checkpoint's statistic loaded after create is the one it meets
+        StandardizeObs(exp_.v.obs);
+        row0Raw_ = false;
+    }
     if (trajMode()) {
         CollectTrajectories();
         return;
@@ -521,6 +528,66 @@ void Learner::ActAndStep(size_t row, size_t next, float* trunc, float* truncStac
     StepEnv(v.actions + row, o);
     if (timing) hipCheck(hipEventRecord(timing[1], s_), "event");
     if (K_ > 1) lk::stack_frames(st.obs, st.trunc_obs, v.terms + row, hist_.p, K_, P, OBS, v.obs + next * W, truncStacked, s_);
+    // the appended row is the next step's policy input (the fused step holds the reset): the reference's "top of the
+    // next step".  The pre-reset rows (`trunc`) stay raw, as traj.nextStates do (Learner.cpp:855-858)
+    if (obsStd_) StandardizeObs(v.obs + next * W);
+}
+
+// One step of Learner.cpp:679-693 on [P][OBS] rows in place, two launches on s_: the statistic's increment from
+// min(P, maxObsSamples) drawn rows (one workgroup; it leaves the coefficient table), then the row rewrite.
+void Learner::StandardizeObs(float* d_rows) {
+    const int P = exp_.P;
+    lk::obs_stat_update(obsStat_.p, d_rows, P, OBS, std::min(P, obsSamples_), lk::obs_stat_key(cfg_.seed), obsMeanRange_,
+                        obsMinStd_, s_);
+    lk::obs_standardize_rows(d_rows, (int64_t)P * OBS, OBS, obsStat_.p, s_);
+}
+
+void Learner::SetObsStandardization(bool enable, float minStd, float maxMeanRange, int maxSamples) {
+    if (collected_)
+        throw rlgpu::Error(RLGPU_ERR_STATE, "Learner: obs standardisation (standardize_obs) cannot change after the first "
+                                            "collection: row 0 has been taken as it was");
+    if (!enable) {
+        obsStd_ = row0Raw_ = false;
+        return;
+    }
+    RLGPU_REQUIRE(std::isfinite(minStd) && minStd > 0.f, "Learner: min_std (minObsSTD) must be finite and > 0");
+    RLGPU_REQUIRE(std::isfinite(maxMeanRange) && maxMeanRange >= 0.f,
+                  "Learner: max_mean_range (maxObsMeanRange) must be finite and >= 0");
+    RLGPU_REQUIRE(maxSamples >= 1, "Learner: max_samples (maxObsSamples) must be >= 1");
+    if (K_ > 1)
+        throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "Learner: standardize_obs with frame_stack > 1 is not supported (a stacked "
+                                                  "row mixes steps; the reference has no stacking)");
+    if (cfg_.world > 1)
+        throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "Learner: standardize_obs with world > 1 is not supported (per-rank "
+                                                  "statistics would diverge)");
+    obsStat_.Reserve((int64_t)lk::obs_stat_bytes(OBS), s_, false, true);  // zero-filled: a fresh BatchedWelfordStat
+    obsMinStd_ = minStd;
+    obsMeanRange_ = maxMeanRange;
+    obsSamples_ = maxSamples;
+    obsStd_ = row0Raw_ = true;
+}
+
+void Learner::GetObsStat(int64_t* count, double* means, double* m2s) {
+    if (!obsStd_) throw rlgpu::Error(RLGPU_ERR_STATE, "Learner: obs standardisation is not enabled");
+    std::vector<char> h(8 + 16 * (size_t)OBS);
+    hipCheck(hipMemcpyAsync(h.data(), obsStat_.p, h.size(), hipMemcpyDeviceToHost, s_), "obs stat");
+    hipCheck(hipStreamSynchronize(s_), "sync");
+    if (count) std::memcpy(count, h.data(), 8);
+    if (means) std::memcpy(means, h.data() + 8, 8 * (size_t)OBS);
+    if (m2s) std::memcpy(m2s, h.data() + 8 + 8 * (size_t)OBS, 8 * (size_t)OBS);
+}
+
+void Learner::SetObsStat(int64_t count, const double* means, const double* m2s) {
+    if (!obsStd_) throw rlgpu::Error(RLGPU_ERR_STATE, "Learner: obs standardisation is not enabled");
+    if (collected_)
+        throw rlgpu::Error(RLGPU_ERR_STATE, "Learner: the obs statistic cannot be set after the first collection");
+    RLGPU_REQUIRE(count >= 0 && means && m2s, "Learner: obs statistic: count must be >= 0, means / m2s non-null");
+    std::vector<char> h(8 + 16 * (size_t)OBS);
+    std::memcpy(h.data(), &count, 8);
+    std::memcpy(h.data() + 8, means, 8 * (size_t)OBS);
+    std::memcpy(h.data() + 8 + 8 * (size_t)OBS, m2s, 8 * (size_t)OBS);
+    hipCheck(hipMemcpyAsync(obsStat_.p, h.data(), h.size(), hipMemcpyHostToDevice, s_), "obs stat");
+    hipCheck(hipStreamSynchronize(s_), "sync");
 }
 
 // at least `count` timing events in ev_ (recreated when it grows)
@@ -1110,6 +1177,53 @@ extern "C" int rlgpu_learner_guide_logits(rlgpu_learner* h, const uint16_t** d_l
         RLGPU_REQUIRE(d_logits && rows, "rlgpu_learner_guide_logits: null argument");
         *d_logits = h->L->guideLogits();
         *rows = h->L->guideRows();
+    });
+}
+
+extern "C" int rlgpu_learner_set_obs_standardization(rlgpu_learner* h, int32_t enable, float min_std, float max_mean_range,
+                                                     int32_t max_samples) {
+    return rlgpu::guarded([&] {
+        RLGPU_LEARNER(h);
+        h->L->SetObsStandardization(enable != 0, min_std, max_mean_range, max_samples);
+    });
+}
+extern "C" int rlgpu_learner_get_obs_stat(rlgpu_learner* h, int64_t* count, double* means, double* m2s) {
+    return rlgpu::guarded([&] {
+        RLGPU_LEARNER(h);
+        h->L->GetObsStat(count, means, m2s);
+    });
+}
+extern "C" int rlgpu_learner_set_obs_stat(rlgpu_learner* h, int64_t count, const double* means, const double* m2s) {
+    return rlgpu::guarded([&] {
+        RLGPU_LEARNER(h);
+        h->L->SetObsStat(count, means, m2s);
+    });
+}
+
+extern "C" int64_t rlgpu_obs_stat_bytes(int32_t width) { return width > 0 ? (int64_t)lk::obs_stat_bytes(width) : 0; }
+
+extern "C" int rlgpu_obs_stat_step(void* d_state, float* d_obs, int32_t rows, int32_t width, uint64_t seed,
+                                   int32_t max_samples, float max_mean_range, float min_std, void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(d_state && d_obs && rows > 0 && width > 0, "rlgpu_obs_stat_step: null pointer, or rows / width <= 0");
+        RLGPU_REQUIRE(((uintptr_t)d_state & 7) == 0 && ((uintptr_t)d_obs & 3) == 0,
+                      "rlgpu_obs_stat_step: d_state must be 8-byte and d_obs 4-byte aligned");
+        RLGPU_REQUIRE(std::isfinite(min_std) && min_std > 0.f, "rlgpu_obs_stat_step: min_std must be finite and > 0");
+        RLGPU_REQUIRE(std::isfinite(max_mean_range) && max_mean_range >= 0.f,
+                      "rlgpu_obs_stat_step: max_mean_range must be finite and >= 0");
+        RLGPU_REQUIRE(max_samples >= 1, "rlgpu_obs_stat_step: max_samples must be >= 1");
+        hipStream_t s = rlgpu::as_stream(stream);
+        lk::obs_stat_update(d_state, d_obs, rows, width, std::min(rows, max_samples), lk::obs_stat_key(seed), max_mean_range,
+                            min_std, s);
+        lk::obs_standardize_rows(d_obs, (int64_t)rows * width, width, d_state, s);
+    });
+}
+
+extern "C" int rlgpu_obs_sample_rows(uint64_t seed, int64_t count, int32_t rows, int32_t n, int32_t* out) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(out && count >= 0 && rows > 0 && n >= 0, "rlgpu_obs_sample_rows: bad argument");
+        const uint64_t key = lk::obs_stat_key(seed);
+        for (int32_t i = 0; i < n; i++) out[i] = lk::obs_sample_row(key, count + i, rows);
     });
 }
 

@@ -214,6 +214,12 @@ public:
         hookUser_ = user;
     }
     void SetEnvTiming(bool on) { envTiming_ = on; }
+    // LearnerConfig::standardizeObs / minObsSTD / maxObsMeanRange / maxObsSamples (Learner.cpp:679-693): every obs set
+    // the policy sees first increments a BatchedWelfordStat from min(P, maxSamples) drawn rows and is then rewritten in
+    // place; the truncation rows stay raw, as in the reference.  Before the first collection only.
+    void SetObsStandardization(bool enable, float minStd, float maxMeanRange, int maxSamples);
+    void GetObsStat(int64_t* count, double* means, double* m2s);  // [OBS] each; synchronises
+    void SetObsStat(int64_t count, const double* means, const double* m2s);
 
     const rlgpu_learner_config& config() const { return cfg_; }
     RLGC::EnvSetGPU& env() { return *env_; }
@@ -250,6 +256,14 @@ private:
     void* gradHookUser_ = nullptr;
     int K_ = 1;                 // frames stacked (config C4)
     DevArray<float> hist_;      // [K-1][P][OBS] frame history
+    // obs standardisation: the statistic and the coefficient table it yields, in one block (empty while off)
+    DevArray<char> obsStat_;    // lk::obs_stat_bytes(OBS): count, means, m2, then coef [2][OBS] and the active word
+    bool obsStd_ = false;
+    bool row0Raw_ = false;      // rollout / store row 0 still holds the env's raw initial obs
+    bool collected_ = false;    // the first collection has started
+    float obsMinStd_ = 0.1f, obsMeanRange_ = 3.f;
+    int obsSamples_ = 100;
+    void StandardizeObs(float* d_rows);  // one reference step on [P][OBS] rows: increment, then normalise
     std::vector<hipEvent_t> ev_;
     // the rollout collection in arena groups (rlgpu_learner_config.collect_groups): one stream per group, each on
     // its own CU partition (host/cu_partition.hpp), joined to s_ by events at the phase's start and end

@@ -191,6 +191,8 @@ def save(learner, folder, keep=8):
     os.makedirs(path, exist_ok=True)
     stats = {"total_timesteps": int(learner.total_steps), "total_iterations": int(learner.iteration),
              "return_stat": learner.return_stat.to_json()}
+    if getattr(learner, "obs_stat", None) is not None:  # Learner.cpp:184-185
+        stats["obs_stat"] = learner.obs_stat.to_json()
     skill = getattr(learner, "skill", None)
     if skill is not None:  # PolicyVersionManager::AddRunningStatsToJSON
         stats["skill_ratings"] = skill.cur_ratings.to_json()
@@ -242,6 +244,8 @@ def load(learner, folder, allow_missing_models=True):
     learner.iteration = int(j["total_iterations"])
     if "return_stat" in j:
         learner.return_stat.read_json(j["return_stat"])
+    if getattr(learner, "obs_stat", None) is not None and "obs_stat" in j:  # Learner.cpp:214-215
+        learner.obs_stat.read_json(j["obs_stat"])
     skill = getattr(learner, "skill", None)
     if skill is not None and "skill_ratings" in j:  # LoadRunningStatsFromJSON
         from .skill import SkillRating

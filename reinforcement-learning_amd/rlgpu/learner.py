@@ -98,6 +98,39 @@ def sample_indices(seed, rank, iteration, rng, n):
     return out[:n]
 
 
+def obs_sample_rows(seed, count, rows, n):
+    """rlgpu_obs_sample_rows: the n rows in [0, rows) that the obs statistic draws (with replacement) in a step that
+    starts at state count `count` (draw i: Philox counter count + i)."""
+    L = _host_lib()
+    L.rlgpu_obs_sample_rows.argtypes = [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
+    out = np.zeros(max(n, 1), np.int32)
+    _lib.check(L.rlgpu_obs_sample_rows(seed & (2**64 - 1), count, rows, n, out.ctypes.data), "rlgpu_obs_sample_rows")
+    return out[:n]
+
+
+def obs_stat_bytes(width):
+    """rlgpu_obs_stat_bytes: device bytes of an obs-statistic state block (int64 count, fp64 means, fp64 m2, scratch)."""
+    L = _host_lib()
+    L.rlgpu_obs_stat_bytes.argtypes, L.rlgpu_obs_stat_bytes.restype = [ctypes.c_int32], ctypes.c_int64
+    return int(L.rlgpu_obs_stat_bytes(width))
+
+
+def obs_stat_step(state, obs, seed, max_samples=100, max_mean_range=3.0, min_std=0.1):
+    """rlgpu_obs_stat_step on the current stream: `state` a device uint8 tensor of obs_stat_bytes(width) bytes (zeros =
+    fresh), `obs` a device fp32 [rows, width] tensor (contiguous; a view at any row of a larger one will do), rewritten
+    in place after the statistic took its min(rows, max_samples) drawn rows."""
+    L = _host_lib()
+    L.rlgpu_obs_stat_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                      ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
+    _lib.require_gpu_tensor(state, "state")
+    _lib.require_gpu_tensor(obs, "obs")
+    rows, width = obs.shape
+    if not obs.is_contiguous() or state.numel() * state.element_size() < obs_stat_bytes(width):
+        raise _lib.RLGPUError("obs_stat_step: obs must be contiguous and state hold obs_stat_bytes(width) bytes")
+    _lib.check(L.rlgpu_obs_stat_step(_lib.ptr(state), _lib.ptr(obs), rows, width, seed & (2**64 - 1), max_samples,
+                                     max_mean_range, min_std, _lib.stream_ptr()), "rlgpu_obs_stat_step")
+
+
 def last_ends(terms):
     """Per column of a [T, P] trajectory-code array: the last step with a nonzero code, -1 if none."""
     t = np.asarray(terms)
@@ -232,6 +265,12 @@ class LearnerConfig:
         self.use_guiding_policy = False
         self.guiding_policy_path = "guiding_policy/"
         self.guiding_strength = 0.03
+        # LearnerConfig::standardizeObs / minObsSTD / maxObsMeanRange / maxObsSamples (LearnerConfig.h:42-45): the policy,
+        # the critic and Learn see obs standardised by a running per-column statistic (Learner.obs_stat)
+        self.standardize_obs = False
+        self.min_obs_std = 0.1
+        self.max_obs_mean_range = 3.0
+        self.max_obs_samples = 100
         # checkpoints (LearnerConfig.h:31-38): None = no save / load
         self.checkpoint_folder = None
         self.ts_per_save = 10_000_000     # 0 = every iteration (Learner.cpp:44-45)
@@ -325,6 +364,9 @@ def _bind():
     L.rlgpu_learner_step_metrics.argtypes = [vp, vp, vp, ctypes.c_int32]
     L.rlgpu_learner_set_guide.argtypes = [vp, vp, ctypes.c_float]
     L.rlgpu_learner_guide_logits.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64)]
+    L.rlgpu_learner_set_obs_standardization.argtypes = [vp, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_int32]
+    L.rlgpu_learner_get_obs_stat.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), vp, vp]
+    L.rlgpu_learner_set_obs_stat.argtypes = [vp, ctypes.c_int64, vp, vp]
     return L
 
 
@@ -348,6 +390,38 @@ class _ReturnStat:
         st = self._L._stats()
         st.return_n, st.return_mean, st.return_m2 = int(j["count"]), float(j["mean"]), float(j["var"])
         self._L._set_stats(st)
+
+
+class _ObsStat:
+    """The C++ Learner's obs statistic (BatchedWelfordStat, Util/WelfordStat.h:69-243) on the device, seen through
+    rlgpu_learner_get / set_obs_stat (checkpoint JSON: means, vars = the running m2, count)."""
+
+    def __init__(self, learner):
+        self._L = learner
+
+    def get(self):
+        """(count, means [OBS] float64, m2 [OBS] float64)"""
+        n, mean, m2 = ctypes.c_int64(), np.zeros(OBS, np.float64), np.zeros(OBS, np.float64)
+        _lib.check(_lib.lib().rlgpu_learner_get_obs_stat(self._L._h, ctypes.byref(n), mean.ctypes.data, m2.ctypes.data),
+                   "rlgpu_learner_get_obs_stat")
+        return n.value, mean, m2
+
+    def set(self, count, means, m2):
+        mean = np.ascontiguousarray(means, np.float64).ravel()
+        m2 = np.ascontiguousarray(m2, np.float64).ravel()
+        if mean.size != OBS or m2.size != OBS:
+            raise ValueError(f"obs_stat: expected {OBS} means and vars, got {mean.size} and {m2.size}")
+        _lib.check(_lib.lib().rlgpu_learner_set_obs_stat(self._L._h, int(count), mean.ctypes.data, m2.ctypes.data),
+                   "rlgpu_learner_set_obs_stat")
+
+    n = property(lambda self: self.get()[0])
+
+    def to_json(self):  # BatchedWelfordStat::ToJSON
+        n, mean, m2 = self.get()
+        return {"means": mean.tolist(), "vars": m2.tolist(), "count": n}
+
+    def read_json(self, j):  # BatchedWelfordStat::ReadFromJSON
+        self.set(int(j["count"]), j["means"], j["vars"])
 
 
 class Learner:
@@ -449,6 +523,14 @@ class Learner:
         self.target = a(r.target, (T, P), f32, d)
         self.ret = a(r.ret, (T, P), f32, d)
         self.return_stat = _ReturnStat(self)
+        self.obs_stat = None  # the obs statistic while cfg.standardize_obs (before the checkpoint load: it reads it)
+        if cfg.standardize_obs:
+            try:
+                self.set_obs_standardization(True, cfg.min_obs_std, cfg.max_obs_mean_range, cfg.max_obs_samples)
+            except _lib.RLGPUError:  # a refused config leaves no half-built learner (and no device memory) behind
+                L.rlgpu_learner_destroy(self._h)
+                self._h = None
+                raise
         # old-version player rows: team of player p is p % 2 (cars 0, 2 blue; 1, 3 orange)
         team = torch.arange(P, device=d) % 2
         self._old_rows = [(team == k).to(torch.uint8) for k in range(2)]
@@ -598,6 +680,13 @@ class Learner:
         _lib.check(_lib.lib().rlgpu_learner_set_guide(self._h, _lib.ptr(self._guide_params), float(strength)),
                    "rlgpu_learner_set_guide")
         self.ppo._guided = True
+
+    def set_obs_standardization(self, enable, min_std=0.1, max_mean_range=3.0, max_samples=100):
+        """rlgpu_learner_set_obs_standardization (LearnerConfig::standardizeObs & co.), before the first collection."""
+        _lib.check(_lib.lib().rlgpu_learner_set_obs_standardization(self._h, int(bool(enable)), float(min_std),
+                                                                    float(max_mean_range), int(max_samples)),
+                   "rlgpu_learner_set_obs_standardization")
+        self.obs_stat = _ObsStat(self) if enable else None
 
     def guide_logits_view(self):
         """The last learn phase's guide logits [rows, ACTIONS] (16-bit inference format), or None before the first."""
