@@ -257,6 +257,42 @@ int rlgpu_learner_set_old_team(rlgpu_learner* h, int32_t team);
 int rlgpu_learner_set_guide(rlgpu_learner* h, const float* d_policy_params, float guiding_strength);
 int rlgpu_learner_guide_logits(rlgpu_learner* h, const uint16_t** d_logits, int64_t* rows);
 
+/* Transfer learning (Learner::StartTransferLearn, Learner.cpp:299-480; TransferLearnConfig.h): distil an old policy -- the
+ * teacher, an ordinary rlgpu_ppo handle built from the old policy / shared-head configuration with obs_size = RLGPU_OBS
+ * and num_actions = RLGPU_ACTIONS, its parameters loaded by the caller -- into the learner's policy (and shared head).
+ * set_teacher borrows the handle (the caller keeps it alive and destroys it after the learner; NULL removes it).
+ * transfer_iterate is one iteration of the reference's loop:
+ *   collect    the rollout the usual way, on whichever collection path is eligible, the current policy sampling the
+ *              actions; the batch is the rollout's rollout_len * players rows (the caller sizes rollout_len as
+ *              ceil(batchSize / players)); there is no consume phase (no critic pass, no GAE);
+ *   teacher    one rlgpu_ppo_teacher_probs pass over rows [0, T * P) of the rollout's obs / masks;
+ *   epochs     cfg->epochs times: rlgpu_ppo_transfer_chunk over the whole batch in chunks of the handle's max_rows (no
+ *              minibatches: the chunks sum to the whole-batch gradient), then rlgpu_ppo_transfer_step(cfg->lr);
+ *   finish     as rlgpu_learner_finish_iteration (counters, the next rollout starts from the last obs).
+ * The critic, its moments and its optimiser step count do not move.  Metrics (rlgpu_learner_metrics; the count
+ * advances by one per transfer iteration): RLGPU_M_TL_OLD_ENTROPY, and from epoch 0 RLGPU_M_TL_LOSS, RLGPU_M_TL_ACCURACY
+ * and RLGPU_M_ENTROPY, each the whole batch's mean; RLGPU_M_TL_UPDATE_MAGNITUDE ("Policy Update Magnitude") is written,
+ * not summed.  Reset the metrics between ordinary and transfer iterations: both use RLGPU_M_ENTROPY and the count.
+ * The report has collect_s and learn_s (the teacher pass, the epochs and the finish); consume_s is 0.
+ * Supported teacher at this level: the engine's own obs builder and action parser (whatever width the env emits), any
+ * architecture.  RLGPU_ERR_STATE without a teacher; RLGPU_ERR_INVALID_ARG for loss_exponent < 1 (rlgpu_ppo_transfer_chunk);
+ * RLGPU_ERR_UNSUPPORTED, each named in the message, for
+ *   world > 1            the whole-batch mean and the policy-only step are not reduced over ranks,
+ *   frame_stack > 1      the teacher would need its own frame history,
+ *   RLGPU_EXP_TRAJECTORIES  the batch is the rollout's rows,
+ *   obs standardisation  the teacher would need the raw rows,
+ *   deterministic        the reference samples the batch's actions,
+ *   an old team set      the batch is collected by the current policy alone. */
+typedef struct {
+    float lr;             /* TransferLearnConfig::lr (3e-4) */
+    int32_t epochs;       /* 5 */
+    int32_t use_kl;       /* useKLDiv: |o log(o / c)| instead of |o - c| */
+    float loss_scale;     /* 500 */
+    float loss_exponent;  /* 1; finite and >= 1 */
+} rlgpu_transfer_config;
+int rlgpu_learner_set_teacher(rlgpu_learner* h, rlgpu_ppo* teacher);
+int rlgpu_learner_transfer_iterate(rlgpu_learner* h, const rlgpu_transfer_config* cfg, rlgpu_learner_report* rep);
+
 /* Obs standardisation (LearnerConfig::standardizeObs / minObsSTD / maxObsMeanRange / maxObsSamples; Learner.cpp:679-693,
  * Util/WelfordStat.h:69-243).  Every obs set the policy is about to see -- row 0, then each step's appended row -- takes
  * one rlgpu_obs_stat_step on the learner's stream: a BatchedWelfordStat over the obs columns (int64 count, fp64 means and

@@ -113,6 +113,12 @@ enum {
     RLGPU_M_ENTROPY = 0, RLGPU_M_KL, RLGPU_M_POLICY_LOSS, RLGPU_M_CRITIC_LOSS, RLGPU_M_RATIO,
     RLGPU_M_CLIP_FRACTION, RLGPU_M_COUNT, RLGPU_M_GRAD_NORM_POLICY, RLGPU_M_GRAD_NORM_CRITIC,
     RLGPU_M_GRAD_NORM_SHARED, RLGPU_M_GUIDING_LOSS = 10 /* rlgpu_ppo_minibatch_guided: mean |guide probs - probs| */,
+    /* transfer learning (rlgpu_ppo_teacher_probs / rlgpu_ppo_transfer_chunk), each a whole-batch mean once every chunk
+     * of the batch has run: the distillation loss, the share of rows whose argmax matches the teacher's, the teacher's
+     * entropy; the student's entropy goes to RLGPU_M_ENTROPY */
+    RLGPU_M_TL_LOSS = 11, RLGPU_M_TL_ACCURACY = 12, RLGPU_M_TL_OLD_ENTROPY = 13,
+    /* the host Learner's transfer iteration: ||policy model before - after|| of the last iteration (written, not summed) */
+    RLGPU_M_TL_UPDATE_MAGNITUDE = 14,
     RLGPU_NUM_METRICS = 16
 };
 
@@ -120,6 +126,9 @@ int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out);
 int rlgpu_ppo_destroy(rlgpu_ppo* h);
 /* sizeof(rlgpu_ppo_config), for language bindings to check their mirror of the struct against. */
 int32_t rlgpu_ppo_config_size(void);
+/* The configuration the handle runs with (defaults resolved: policy_temperature 0 -> 1, RLGPU_ACT_RELU as LeakyReLU with
+ * slope 0). */
+int rlgpu_ppo_get_config(rlgpu_ppo* h, rlgpu_ppo_config* out);
 
 /* Flat fp32 buffers of all models, contiguous (policy first, then critic, then the shared head). */
 int rlgpu_ppo_buffers(rlgpu_ppo* h, float** d_params, float** d_grads, int64_t* num_params);
@@ -250,6 +259,58 @@ int rlgpu_ppo_optimizer_state(rlgpu_ppo* h, int64_t* step, float** d_exp_avg, fl
 /* Restore the AdamW step count (checkpoint resume; the moments are written through the pointers
  * rlgpu_ppo_optimizer_state returns). */
 int rlgpu_ppo_set_optimizer_step(rlgpu_ppo* h, int64_t step);
+/* The step count is kept per model (0 policy, 1 critic, 2 shared head), as libtorch keeps it per parameter:
+ * rlgpu_ppo_optimizer_step advances every model's, rlgpu_ppo_transfer_step the policy's and the shared head's only.
+ * rlgpu_ppo_optimizer_state returns the policy's and rlgpu_ppo_set_optimizer_step sets all of them; these two read and
+ * write one model's (model 2 without a shared head: RLGPU_ERR_INVALID_ARG). */
+int rlgpu_ppo_model_optimizer_step(rlgpu_ppo* h, int32_t model, int64_t* step);
+int rlgpu_ppo_set_model_optimizer_step(rlgpu_ppo* h, int32_t model, int64_t step);
+
+/* ---- Transfer learning (Learner::StartTransferLearn, Learner.cpp:299-480; PPOLearner::TransferLearn,
+ * PPOLearner.cpp:583-637): distil an old policy (the teacher, any architecture) into this one.
+ *
+ * teacher_probs: h_teacher is an ordinary handle built from the old policy / shared-head configuration (its own
+ * obs_size, num_actions = A_old, widths, activation, LayerNorm setting and an unused minimal critic).  Runs its
+ * inference forward (16-bit or fp32 per its infer_fp16, in chunks of its max_rows) over d_obs [n, obs_size], then
+ *   old = clamp(softmax(logit / policy_temperature + (-1e10) * !mask), 1e-11, 1)      d_masks [n, A_old]
+ * (InferPolicyProbsFromModels), adds the mean over the n rows of old's entropy (the engine's definition, the handle's
+ * mask_entropy included) to d_metrics[RLGPU_M_TL_OLD_ENTROPY] (d_metrics may be NULL), and writes
+ *   d_probs [n, A_out] f32:  old[i][k], or with d_action_map (int32 [n, A_out]) old[i][map[i][k]]
+ *   d_argmax [n] int32:      the argmax of the written row, the first index on ties.
+ * Without a map A_out must equal A_old; A_out in 2..128.  A map entry outside [0, A_old) is the caller's error and,
+ * the map being device memory, is not checked: the value read for it is unspecified (the read itself stays in bounds).
+ * Callers whose map is host-visible validate it before the upload. */
+int rlgpu_ppo_teacher_probs(rlgpu_ppo* h_teacher, const float* d_obs, const uint8_t* d_masks, int64_t n,
+                            const int32_t* d_action_map, int32_t A_out, float* d_probs, int32_t* d_argmax,
+                            float* d_metrics, void* stream);
+/* The same from given f32 logits [n, A_old] instead of a handle's forward (building block, exported for tests). */
+int rlgpu_teacher_probs_from_logits(const float* d_logits, const uint8_t* d_masks, int64_t n, int32_t A_old,
+                                    const int32_t* d_action_map, int32_t A_out, float policy_temperature,
+                                    int32_t mask_entropy, float* d_probs, int32_t* d_argmax, float* d_metrics, void* stream);
+/* One chunk of a transfer-learning epoch: rows idx[start .. start + n) (d_index NULL: identity; n <= max_rows) of a
+ * batch of total_rows rows, gathered from d_obs [*, obs_size], d_masks [*, A], d_target_probs [*, A] and
+ * d_target_argmax [*] (teacher_probs' outputs).  Shared head forward, policy forward (fp32 training path), then with c
+ * the policy's clamped probabilities and o the targets
+ *   loss = loss_scale * mean over all total_rows * A elements of |o - c|^e        (use_kl: |o log(o / c)|^e)
+ * and its backward through the policy and, from the policy's input gradient alone, the shared head.  Gradients are
+ * ACCUMULATED, so the chunks of one batch sum to the whole-batch gradient; the critic's parameters, gradients, activation
+ * buffers and stream are not touched (its H3 operand-scale slots, scratch that every pass rebuilds, are cleared with the
+ * other models' at the chunk's start).  d_metrics (may be NULL): RLGPU_M_TL_LOSS, RLGPU_M_TL_ACCURACY (share of rows with argmax c =
+ * d_target_argmax) and RLGPU_M_ENTROPY each receive this chunk's part of the whole-batch mean.
+ * loss_exponent e must be finite and >= 1, else RLGPU_ERR_INVALID_ARG: below 1 the reference's own backward is
+ * inf * 0 = NaN on every masked column (|o - c| = 0 there and d t^e / d t = e t^(e-1) = inf). */
+int rlgpu_ppo_transfer_chunk(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, const float* d_target_probs,
+                             const int32_t* d_target_argmax, const int32_t* d_index, int64_t start, int32_t n,
+                             int64_t total_rows, int32_t use_kl, float loss_scale, float loss_exponent, float* d_metrics,
+                             void* stream);
+/* The optimiser step of a transfer-learning epoch (ModelSet::StepOptims after SetOptimLR(tlConfig.lr); no
+ * clip_grad_norm_): the handle's AdamW arithmetic at learning rate lr on the policy and the shared head, without a clip
+ * coefficient; zeroes those models' gradients, advances their step counts and refreshes their 16-bit copies.  The
+ * critic's parameters, gradients, moments and step count are not touched. */
+int rlgpu_ppo_transfer_step(rlgpu_ppo* h, float lr, void* stream);
+/* ||a - b|| of two device spans of n floats into d_out[0] ("Policy Update Magnitude": the policy model before and after
+ * the epochs).  d_scratch: 512 floats of device scratch the caller owns, or NULL for a stream-ordered temporary. */
+int rlgpu_diff_norm(const float* d_a, const float* d_b, int64_t n, float* d_out, float* d_scratch, void* stream);
 
 /* Building block, exported for tests and microbenchmarks: C[I,J] = sum_k A(i,k) B(k,j) (+ bias[j])
  * in the fp32 arithmetic `mode` (RLGPU_GEMM_F32X6 / RLGPU_GEMM_F32 / RLGPU_GEMM_F16X3).  a_layout 0: A stored [I][lda] (k contiguous), 1: [K][lda] (i contiguous);

@@ -68,6 +68,52 @@ void launch_mlp_infer_act(int act, bool f16, unsigned blocks, hipStream_t s, con
 // infer_wave.hip: one launch of the one-wave form (infer::mlp_infer_wave<f16>, LeakyReLU / ReLU), 16 rows per workgroup
 void launch_mlp_infer_wave(bool f16, unsigned blocks, hipStream_t s, const void* args, size_t bytes);
 
+// transfer.hip: the transfer-learning kernels (transfer_kernels.hpp), launched for ppo.hip's entry points.
+// teacher_probs over n rows of f32 logits [n][A_old]: clamped masked softmax, its entropy / total_rows added into the
+// metric slot, the optional gather by map [n][A] into probs [n][A], the gathered row's argmax.
+struct TeacherProbsArgs {
+    const float* logits;
+    const uint8_t* masks;
+    int n, A_old;
+    const int32_t* map;  // null: A = A_old, no gather
+    int A;
+    float temp;
+    int mask_entropy;
+    int64_t total_rows;
+    float* probs;
+    int32_t* argmax;
+    float* metrics;
+};
+void launch_teacher_probs(const TeacherProbsArgs& a, hipStream_t s);
+// transfer_loss over the n rows idx[start .. start + n) (idx null: identity) of a batch of total_rows rows: dlogits rows of
+// ldd floats, bias partials [transfer_loss_blocks(n)][A], the H3 max |dlogits| (amax null outside H3), the metric sums
+struct TransferLossArgs {
+    const float* logits;
+    const uint8_t* masks;
+    const float* target;
+    const int32_t* target_argmax;
+    const int32_t* idx;
+    int64_t start;
+    int n, A;
+    float temp;
+    int mask_entropy;
+    int64_t total_rows;
+    int use_kl;
+    float loss_scale, exponent;
+    float* dlogits;
+    int ldd;
+    float* metrics;
+    float* bias_part;
+    float* amax;
+};
+int transfer_loss_blocks(int n);
+void launch_transfer_loss(const TransferLossArgs& a, hipStream_t s);
+// adamw's arithmetic without a clip coefficient on one span of n parameters; zeroes g
+void launch_adam_models(float* p, float* g, float* m, float* v, int64_t n, float decay_mul, float beta1, float beta2,
+                        float step_size, float bc2_sqrt, float eps, hipStream_t s);
+// *out = ||a - b|| over n floats (part512: 512 floats of scratch)
+void launch_diff_norm(const float* a, const float* b, int64_t n, float* part512, float* out, hipStream_t s);
+
 }  // namespace rlgpu
 
 // ppo.hip, for env.hip's collection loop (rlgpu_envset_collect_loop): whether the policy runs on the one-wave

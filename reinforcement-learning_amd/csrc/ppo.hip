@@ -165,12 +165,13 @@ struct rlgpu_ppo {
     uint16_t *half_guide = nullptr, *frag_guide = nullptr;
     float* guide_f = nullptr;
     bool has_guide = false;
+    float* teach_f = nullptr;  // a teacher handle's f32 logits of one chunk [max_rows][A] (rlgpu_ppo_teacher_probs), on first use
     // the training GEMMs' split weight planes are stale (parameters changed since the last split):
     // set by init / refresh_half / the optimizer step, cleared when forward_train re-splits.  With
     // the whole iteration as one batch the planes are rebuilt once per optimizer step, not per
     // minibatch.
     bool split_dirty[3] = {true, true, true};
-    int64_t step = 0;
+    int64_t step[3] = {0, 0, 0};  // AdamW step count per model (libtorch keeps it per parameter)
     int hmax = 0;
     float *scratch = nullptr;  // clip partials + coefficients
     hipStream_t aux = nullptr;  // second stream: the critic's minibatch pass overlaps the policy's
@@ -1013,6 +1014,13 @@ static_assert(mlp::ACT_LEAKY == RLGPU_ACT_LEAKY_RELU && mlp::ACT_SIGMOID == RLGP
 
 extern "C" int32_t rlgpu_ppo_config_size(void) { return (int32_t)sizeof(rlgpu_ppo_config); }
 
+extern "C" int rlgpu_ppo_get_config(rlgpu_ppo* h, rlgpu_ppo_config* out) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && out, "rlgpu_ppo_get_config: null argument");
+        *out = h->cfg;
+    });
+}
+
 extern "C" int rlgpu_ppo_create(const rlgpu_ppo_config* cfg, rlgpu_ppo** out) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(cfg && out, "rlgpu_ppo_create: null argument");
@@ -1481,13 +1489,13 @@ extern "C" int rlgpu_ppo_optimizer_step(rlgpu_ppo* h, float* d_metrics, void* st
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(h, "null handle");
         hipStream_t s = rlgpu::as_stream(stream);
-        h->step++;
         const auto& c = h->cfg;
-        double bc1 = 1.0 - std::pow((double)c.beta1, (double)h->step);
-        double bc2 = 1.0 - std::pow((double)c.beta2, (double)h->step);
         const int slot[3] = {RLGPU_M_GRAD_NORM_POLICY, RLGPU_M_GRAD_NORM_CRITIC, RLGPU_M_GRAD_NORM_SHARED};
         for (int mi = 0; mi < h->nm; mi++) {
             Model& m = h->M[mi];
+            h->step[mi]++;
+            double bc1 = 1.0 - std::pow((double)c.beta1, (double)h->step[mi]);
+            double bc2 = 1.0 - std::pow((double)c.beta2, (double)h->step[mi]);
             float* coef = h->scratch + 600 + mi;
             float* norm_out = d_metrics ? d_metrics + slot[mi] : nullptr;
             sumsq_coef(h, h->grads + m.off, m.count, c.max_grad_norm, coef, norm_out, s);
@@ -1514,7 +1522,7 @@ extern "C" int rlgpu_ppo_zero_grad(rlgpu_ppo* h, void* stream) {
 extern "C" int rlgpu_ppo_optimizer_state(rlgpu_ppo* h, int64_t* step, float** d_exp_avg, float** d_exp_avg_sq) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(h, "null handle");
-        if (step) *step = h->step;
+        if (step) *step = h->step[0];
         if (d_exp_avg) *d_exp_avg = h->exp_avg;
         if (d_exp_avg_sq) *d_exp_avg_sq = h->exp_avg_sq;
     });
@@ -1523,7 +1531,130 @@ extern "C" int rlgpu_ppo_optimizer_state(rlgpu_ppo* h, int64_t* step, float** d_
 extern "C" int rlgpu_ppo_set_optimizer_step(rlgpu_ppo* h, int64_t step) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(h && step >= 0, "rlgpu_ppo_set_optimizer_step: bad argument");
-        h->step = step;
+        for (int mi = 0; mi < 3; mi++) h->step[mi] = step;
+    });
+}
+
+extern "C" int rlgpu_ppo_model_optimizer_step(rlgpu_ppo* h, int32_t model, int64_t* step) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && step && model >= 0 && model < h->nm, "rlgpu_ppo_model_optimizer_step: bad argument");
+        *step = h->step[model];
+    });
+}
+
+extern "C" int rlgpu_ppo_set_model_optimizer_step(rlgpu_ppo* h, int32_t model, int64_t step) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && step >= 0 && model >= 0 && model < h->nm, "rlgpu_ppo_set_model_optimizer_step: bad argument");
+        h->step[model] = step;
+    });
+}
+
+// ---- transfer learning: the kernels are transfer.hip's (transfer_kernels.hpp), launched through common.hpp
+static_assert(RLGPU_M_TL_LOSS == 11 && RLGPU_M_TL_ACCURACY == 12 && RLGPU_M_TL_OLD_ENTROPY == 13 && RLGPU_M_ENTROPY == 0,
+              "the transfer kernels' metric slots (transfer_kernels.hpp: kTlLossSlot, kTlAccuracySlot, kTlOldEntropySlot)");
+
+namespace {
+void check_teacher_shapes(int64_t n, int A_old, const int32_t* map, int A_out) {
+    RLGPU_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "teacher_probs: n must be in [0, 2^31)");
+    RLGPU_REQUIRE(A_old >= 2 && A_old <= ppo::kMaxA && A_out >= 2 && A_out <= ppo::kMaxA,
+                  "teacher_probs: the action counts must be in [2, 128]");
+    RLGPU_REQUIRE(map || A_out == A_old, "teacher_probs: without an action map A_out must be the teacher's num_actions");
+}
+}  // namespace
+
+extern "C" int rlgpu_teacher_probs_from_logits(const float* d_logits, const uint8_t* d_masks, int64_t n, int32_t A_old,
+                                               const int32_t* d_action_map, int32_t A_out, float policy_temperature,
+                                               int32_t mask_entropy, float* d_probs, int32_t* d_argmax, float* d_metrics,
+                                               void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(d_logits && d_masks && d_probs && d_argmax, "rlgpu_teacher_probs_from_logits: null argument");
+        check_teacher_shapes(n, A_old, d_action_map, A_out);
+        RLGPU_REQUIRE(std::isfinite(policy_temperature) && policy_temperature > 0.f, "policy_temperature must be finite and > 0");
+        rlgpu::launch_teacher_probs({d_logits, d_masks, (int)n, A_old, d_action_map, A_out, policy_temperature, mask_entropy != 0, n,
+                                     d_probs, d_argmax, d_metrics},
+                                    rlgpu::as_stream(stream));
+    });
+}
+
+extern "C" int rlgpu_ppo_teacher_probs(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int64_t n,
+                                       const int32_t* d_action_map, int32_t A_out, float* d_probs, int32_t* d_argmax,
+                                       float* d_metrics, void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && d_obs && d_masks && d_probs && d_argmax, "rlgpu_ppo_teacher_probs: null argument");
+        const int A_old = h->cfg.num_actions;
+        check_teacher_shapes(n, A_old, d_action_map, A_out);
+        hipStream_t s = rlgpu::as_stream(stream);
+        if (!h->teach_f) h->teach_f = h->alloc<float>((int64_t)h->cfg.max_rows * A_old);
+        const Rows rows{d_obs, n, 0, d_masks};
+        for (int64_t b = 0; b < n; b += h->cfg.max_rows) {
+            const Rows r = rows.sub(h->cfg, b, std::min<int64_t>(h->cfg.max_rows, n - b));
+            infer_values(h, 0, r, h->teach_f, s);  // the handle's inference path: fp32, fused or layered 16-bit
+            rlgpu::launch_teacher_probs({h->teach_f, r.masks, (int)r.n, A_old, d_action_map ? d_action_map + b * A_out : nullptr,
+                                         A_out, h->cfg.policy_temperature, h->cfg.mask_entropy, n, d_probs + b * A_out,
+                                         d_argmax + b, d_metrics},
+                                        s);
+        }
+    });
+}
+
+extern "C" int rlgpu_ppo_transfer_chunk(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, const float* d_target_probs,
+                                        const int32_t* d_target_argmax, const int32_t* d_index, int64_t start, int32_t n,
+                                        int64_t total_rows, int32_t use_kl, float loss_scale, float loss_exponent,
+                                        float* d_metrics, void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && d_obs && d_masks && d_target_probs && d_target_argmax, "rlgpu_ppo_transfer_chunk: null argument");
+        RLGPU_REQUIRE(n > 0 && n <= h->cfg.max_rows, "chunk rows must be in [1, max_rows]");
+        RLGPU_REQUIRE(start >= 0 && start + n <= total_rows, "the chunk's rows [start, start + n) must lie inside total_rows");
+        RLGPU_REQUIRE(std::isfinite(loss_scale), "loss_scale must be finite");
+        RLGPU_REQUIRE(std::isfinite(loss_exponent) && loss_exponent >= 1.f,
+                      "loss_exponent must be finite and >= 1: below 1 the loss's backward is inf * 0 = NaN on every masked "
+                      "column (|old - new| = 0 there), in the reference too");
+        hipStream_t s = rlgpu::as_stream(stream);
+        const int A = h->cfg.num_actions;
+        Model& pm = h->M[0];
+        gather_obs(h, d_obs, d_index, start, n, s);
+        const Operand obs_in = obs_input(h), xin = model_input(h, 0);
+        if (h->shared()) forward_train(h, 2, obs_in, n, nullptr, s);
+        forward_train(h, 0, xin, n, pm.y, s);
+        rlgpu::launch_transfer_loss({pm.y, d_masks, d_target_probs, d_target_argmax, d_index, start, n, A,
+                                     h->cfg.policy_temperature, h->cfg.mask_entropy, total_rows, use_kl != 0, loss_scale,
+                                     loss_exponent, pm.dy, dout_ld(A), d_metrics, pm.lpart, amax_slot(pm, kAmaxOut)},
+                                    s);
+        backward(h, 0, xin, n, pm.dy, s, pm.lpart, rlgpu::transfer_loss_blocks(n));
+        // the shared head's backward from the policy's input gradient alone: the critic has no part in this loss
+        if (h->shared()) backward(h, 2, obs_in, n, pm.dX, s);
+    });
+}
+
+extern "C" int rlgpu_ppo_transfer_step(rlgpu_ppo* h, float lr, void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && std::isfinite(lr) && lr >= 0.f, "rlgpu_ppo_transfer_step: lr must be finite and >= 0");
+        hipStream_t s = rlgpu::as_stream(stream);
+        const auto& c = h->cfg;
+        for (int mi = 0; mi < h->nm; mi += 2) {  // GetPolicyModels(): the policy and the shared head
+            Model& m = h->M[mi];
+            h->step[mi]++;
+            // rlgpu_ppo_optimizer_step's scalars with lr in place of the model's
+            const double bc1 = 1.0 - std::pow((double)c.beta1, (double)h->step[mi]);
+            const double bc2 = 1.0 - std::pow((double)c.beta2, (double)h->step[mi]);
+            const double dlr = lr;
+            rlgpu::launch_adam_models(h->params + m.off, h->grads + m.off, h->exp_avg + m.off, h->exp_avg_sq + m.off, m.count,
+                                      (float)(1.0 - dlr * (double)c.weight_decay), c.beta1, c.beta2, (float)(dlr / bc1),
+                                      (float)std::sqrt(bc2), c.eps, s);
+            half_from(h, mi, h->params + m.off, h->half, h->frag, s);
+            h->split_dirty[mi] = true;
+        }
+    });
+}
+
+extern "C" int rlgpu_diff_norm(const float* d_a, const float* d_b, int64_t n, float* d_out, float* d_scratch, void* stream) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(d_a && d_b && d_out && n >= 0, "rlgpu_diff_norm: bad argument");
+        hipStream_t s = rlgpu::as_stream(stream);
+        float* part = d_scratch;  // the caller's 512 floats, or a stream-ordered temporary
+        if (!part) RLGPU_CHECK_HIP(hipMallocAsync((void**)&part, 512 * sizeof(float), s));
+        rlgpu::launch_diff_norm(d_a, d_b, n, part, d_out, s);
+        if (!d_scratch) RLGPU_CHECK_HIP(hipFreeAsync(part, s));
     });
 }
 

@@ -101,7 +101,7 @@ struct PPOLearnerConfig {
 
 // PPO/TransferLearnConfig.h: the fields of Learner::StartTransferLearn's configuration (distilling an old policy
 // with its own obs builder / action parser into the current one, Learner.cpp:290-470, PPOLearner.cpp:583-637).
-// Restated so a caller's source compiles; the engine does not run that mode (StartTransferLearn says so).
+// Learner::StartTransferLearn runs it for the engine's native obs builder / action parser.
 using MakeObsFn = std::function<RLGC::ObsBuilder*()>;
 using MakeActFn = std::function<RLGC::ActionParser*()>;
 struct TransferLearnConfig {
@@ -641,11 +641,19 @@ class Learner {
     Learner& operator=(const Learner&) = delete;
 
     void Start();
-    // Learner::StartTransferLearn (Learner.h:45): not part of the engine's path; refused by name
-    [[noreturn]] void StartTransferLearn(const TransferLearnConfig&) {
-        throw std::runtime_error("GGL::Learner::StartTransferLearn: transfer learning (PPOLearner::TransferLearn) is not "
-                                 "implemented by the rlgpu engine");
-    }
+    // Learner::StartTransferLearn (Learner.h:45, Learner.cpp:299-480): Start()'s loop with TransferIterate as its body.
+    // The teacher is an rlgpu_ppo handle built from oldPolicyConfig / oldSharedHeadConfig and filled from oldModelsPath
+    // (POLICY.lt, SHARED_HEAD.lt; a missing file is an error).  makeOldObsFn / makeOldActFn must produce the engine's
+    // native AdvancedObs / DefaultAction (recognised by type, as EnvSetGPU's plugin translation does) and mapActsFn must
+    // be null; anything else throws, naming the remaining gap.  The batch is the Learner's rollout (ppo.tsPerItr steps,
+    // fixed when the Learner was made): size tsPerItr as tlConfig.batchSize.  Save, version manager and step callback
+    // behave as in Start().
+    void StartTransferLearn(const TransferLearnConfig& tlConfig);
+    // one StartTransferLearn loop body into `report` (the teacher set by StartTransferLearn, or SetTeacher); returns the
+    // timesteps before it
+    int64_t TransferIterate(Report& report, const TransferLearnConfig& tlConfig);
+    // the teacher handle of tlConfig (the caller destroys it with rlgpu_ppo_destroy after the learner is done with it)
+    rlgpu_ppo* MakeTeacher(const TransferLearnConfig& tlConfig) const;
     // one Start() loop body (collection, consumption, learning, versions) into `report`; returns the timesteps
     // before it (engine extension: Start() without the loop)
     int64_t Iterate(Report& report);
@@ -679,6 +687,8 @@ class Learner {
     void PushStats();
     void LoadMeshes();
     void LoadGuidingPolicy();
+    void Loop(const std::function<int64_t(Report&)>& iterate);  // Start()'s iteration loop: save rules, report display
+    void FinishReport(Report& report, const rlgpu_learner_report& rep, int64_t prev);
     float* guideParams_ = nullptr;  // device: the guiding policy's flat parameters (policy, then shared head)
     void SaveModels(const std::filesystem::path& folder, bool saveOptim, const float* flatParams,
                     const std::vector<int>& which) const;
@@ -993,6 +1003,12 @@ inline int64_t Learner::Iterate(Report& report) {
         report["Critic Loss"] = m[RLGPU_M_CRITIC_LOSS] / cnt;
         report["SB3 Clip Fraction"] = m[RLGPU_M_CLIP_FRACTION] / cnt;
     }
+    FinishReport(report, rep, prev);
+    return prev;
+}
+
+// the timing and counter entries of an iteration's report, then the version manager (Learner.cpp:992-1005)
+inline void Learner::FinishReport(Report& report, const rlgpu_learner_report& rep, int64_t prev) {
     const double steps = (double)((int64_t)totalTimesteps - prev);
     report["Collected Timesteps"] = steps;
     report["Collection Time"] = rep.collect_s;
@@ -1005,7 +1021,139 @@ inline int64_t Learner::Iterate(Report& report) {
     report["Total Timesteps"] = (double)totalTimesteps;
     report["Total Iterations"] = (double)totalIterations;
     if (versionMgr) versionMgr->OnIteration(report, (int64_t)totalTimesteps, prev);
+}
+
+// ---- transfer learning (Learner.cpp:299-480) --------------------------------------------------------------
+inline rlgpu_ppo* Learner::MakeTeacher(const TransferLearnConfig& tl) const {
+    auto bad = [](const std::string& what) { throw std::invalid_argument("TransferLearnConfig: " + what); };
+    // what remains for anything but the engine's own builder / parser: their host-side evaluation per player and step
+    static const char* kGap = ": the engine evaluates the old obs builder, action parser and action map only as its own "
+                              "AdvancedObs / DefaultAction without a map; what remains is the host-side evaluation of the old "
+                              "builders (the C ABI, rlgpu_ppo_teacher_probs, already takes teacher rows and maps)";
+    if (tl.mapActsFn) throw std::runtime_error(std::string("GGL::Learner::StartTransferLearn: mapActsFn is set") + kGap);
+    if (!tl.makeOldObsFn || !tl.makeOldActFn) bad("makeOldObsFn and makeOldActFn must be set");
+    {
+        std::unique_ptr<RLGC::ObsBuilder> ob(tl.makeOldObsFn());
+        std::unique_ptr<RLGC::ActionParser> ap(tl.makeOldActFn());
+        if (!ob || typeid(*ob) != typeid(RLGC::AdvancedObs))
+            throw std::runtime_error(std::string("GGL::Learner::StartTransferLearn: old obs builder ") +
+                                     (ob ? typeid(*ob).name() : "(null)") + kGap);
+        if (!ap || typeid(*ap) != typeid(RLGC::DefaultAction))
+            throw std::runtime_error(std::string("GGL::Learner::StartTransferLearn: old action parser ") +
+                                     (ap ? typeid(*ap).name() : "(null)") + kGap);
+    }
+    const PartialModelConfig& op = tl.oldPolicyConfig;
+    const PartialModelConfig& os = tl.oldSharedHeadConfig;
+    const bool sh = os.IsValid();
+    if (!op.IsValid()) bad("oldPolicyConfig has no layers");
+    if ((int)op.layerSizes.size() > RLGPU_MAX_LAYERS || (int)os.layerSizes.size() > RLGPU_MAX_LAYERS) bad("more than 8 layers");
+    if (sh && (os.activationType != op.activationType || os.addLayerNorm != op.addLayerNorm))
+        bad("oldSharedHeadConfig must use oldPolicyConfig's activationType and addLayerNorm");
+    if (tl.oldModelsPath.empty()) bad("oldModelsPath is not set");
+    rlgpu_ppo_config pc{};
+    RLGC::RlgpuCheck(rlgpu_ppo_get_config(ppo_, &pc), "config");  // the student's: formats, temperature, rows, AdamW
+    pc.n_policy_layers = (int32_t)op.layerSizes.size();
+    for (int i = 0; i < pc.n_policy_layers; i++) pc.policy_layers[i] = op.layerSizes[i];
+    pc.n_shared_layers = sh ? (int32_t)os.layerSizes.size() : 0;
+    for (int i = 0; i < pc.n_shared_layers; i++) pc.shared_layers[i] = os.layerSizes[i];
+    pc.n_critic_layers = 1;  // unused, minimal
+    pc.critic_layers[0] = 8;
+    const ModelActivationType at = op.activationType;
+    pc.activation = at == ModelActivationType::RELU      ? RLGPU_ACT_RELU
+                    : at == ModelActivationType::SIGMOID ? RLGPU_ACT_SIGMOID
+                    : at == ModelActivationType::TANH    ? RLGPU_ACT_TANH
+                                                         : RLGPU_ACT_LEAKY_RELU;
+    pc.leaky_slope = 0.01f;
+    pc.layer_norm = op.addLayerNorm ? 1 : 0;
+    rlgpu_rollout_view v{};
+    RLGC::RlgpuCheck(rlgpu_learner_rollout(h_, &v), "rollout");
+    pc.max_rows = (int32_t)std::min<int64_t>((int64_t)v.T * v.P, 65536);
+    rlgpu_ppo* t = nullptr;
+    RLGC::RlgpuCheck(rlgpu_ppo_create(&pc, &t), "teacher");
+    try {
+        const char* an = at == ModelActivationType::RELU      ? "relu"
+                         : at == ModelActivationType::SIGMOID ? "sigmoid"
+                         : at == ModelActivationType::TANH    ? "tanh"
+                                                              : "leaky_relu";
+        const int feat = sh ? os.layerSizes.back() : RLGPU_OBS;
+        std::vector<ModelSpec> old{{0, "policy", feat, RLGPU_ACTIONS, op.layerSizes, op.addLayerNorm, an}};
+        if (sh) old.push_back({2, "shared_head", RLGPU_OBS, 0, os.layerSizes, op.addLayerNorm, an});
+        float* params = nullptr;
+        RLGC::RlgpuCheck(rlgpu_ppo_buffers(t, &params, nullptr, nullptr), "teacher buffers");
+        for (const ModelSpec& m : old) {  // Model::Load with allowNotExist = false
+            const std::filesystem::path p = tl.oldModelsPath / m.FileName();
+            if (!std::filesystem::exists(p)) throw std::runtime_error("transfer-learning teacher: " + p.string() + " does not exist");
+            int64_t off = 0, cnt = 0;
+            RLGC::RlgpuCheck(rlgpu_ppo_model_range(t, m.index, &off, &cnt), "model range");
+            const auto tmp = detail::TempFile("teacher.f32");
+            std::vector<std::string> a{"model-load", p.string(), tmp.string()};
+            for (auto& x : m.HelperShape()) a.push_back(x);
+            detail::RunHelper(a);
+            const std::string raw = detail::ReadFile(tmp);
+            std::filesystem::remove(tmp);
+            if ((int64_t)raw.size() != cnt * 4)
+                throw std::runtime_error("transfer-learning teacher: " + p.string() + " has different size than the old model config");
+            detail::HipOk(hipMemcpy(params + off, raw.data(), raw.size(), hipMemcpyHostToDevice), "teacher params");
+        }
+        RLGC::RlgpuCheck(rlgpu_ppo_refresh_half(t, stream_), "teacher refresh");
+        detail::HipOk(hipStreamSynchronize(stream_), "sync");
+    } catch (...) {
+        rlgpu_ppo_destroy(t);
+        throw;
+    }
+    return t;
+}
+
+inline int64_t Learner::TransferIterate(Report& report, const TransferLearnConfig& tl) {
+    SyncStats();
+    const int64_t prev = (int64_t)totalTimesteps;
+    oldTeam_ = -1;  // the batch is collected by the current policy alone (Learner.cpp:330-370)
+    RLGC::RlgpuCheck(rlgpu_learner_set_old_team(h_, -1), "old team");
+    float m[RLGPU_NUM_METRICS];
+    int64_t cnt = 0;
+    RLGC::RlgpuCheck(rlgpu_learner_metrics(h_, m, &cnt, 1), "metrics");  // the slots are shared with the PPO loop
+    const rlgpu_transfer_config tc{tl.lr, tl.epochs, tl.useKLDiv ? 1 : 0, tl.lossScale, tl.lossExponent};
+    curReport_ = &report;
+    hookError_.clear();
+    rlgpu_learner_report rep{};
+    const int st = rlgpu_learner_transfer_iterate(h_, &tc, &rep);
+    curReport_ = nullptr;
+    if (st != RLGPU_OK) {
+        if (!hookError_.empty()) throw std::runtime_error("step hook: " + hookError_);
+        RLGC::RlgpuCheck(st, "Learner transfer iteration");
+    }
+    SyncStats();
+    RLGC::RlgpuCheck(rlgpu_learner_metrics(h_, m, &cnt, 1), "metrics");
+    report["Old Policy Entropy"] = m[RLGPU_M_TL_OLD_ENTROPY];  // PPOLearner.cpp:596,621-636
+    if (tl.epochs > 0) {
+        report["Transfer Learn Accuracy"] = m[RLGPU_M_TL_ACCURACY];
+        report["Transfer Learn Loss"] = m[RLGPU_M_TL_LOSS];
+        report["Policy Entropy"] = m[RLGPU_M_ENTROPY];
+    }
+    report["Policy Update Magnitude"] = m[RLGPU_M_TL_UPDATE_MAGNITUDE];
+    FinishReport(report, rep, prev);
     return prev;
+}
+
+inline void Learner::StartTransferLearn(const TransferLearnConfig& tl) {
+    std::printf("Learner::StartTransferLearn():\n\tObs size: %d\n\tAction amount: %d\n", obsSize, numActions);
+    rlgpu_ppo* teacher = MakeTeacher(tl);
+    rlgpu_rollout_view v{};
+    RLGC::RlgpuCheck(rlgpu_learner_rollout(h_, &v), "rollout");
+    if ((int64_t)v.T * v.P != tl.batchSize)
+        std::printf("\tbatch: the Learner's rollout, %d x %d = %lld rows (tlConfig.batchSize %d asks for %lld steps; size "
+                    "ppo.tsPerItr to change it)\n", v.T, v.P, (long long)v.T * v.P, tl.batchSize,
+                    (long long)((tl.batchSize + v.P - 1) / v.P) * v.P);
+    struct Guard {  // the Learner stops borrowing the teacher before it goes
+        rlgpu_learner* h;
+        rlgpu_ppo* t;
+        ~Guard() {
+            (void)rlgpu_learner_set_teacher(h, nullptr);
+            (void)rlgpu_ppo_destroy(t);
+        }
+    } guard{h_, teacher};
+    RLGC::RlgpuCheck(rlgpu_learner_set_teacher(h_, teacher), "set teacher");
+    Loop([&](Report& r) { return TransferIterate(r, tl); });
 }
 
 inline void Learner::Start() {
@@ -1020,9 +1168,13 @@ inline void Learner::Start() {
                 }
         }).detach();
     }
+    Loop([this](Report& r) { return Iterate(r); });
+}
+
+inline void Learner::Loop(const std::function<int64_t(Report&)>& iterate) {
     for (int64_t n = 0;; n++) {
         Report report;
-        const int64_t prev = Iterate(report);
+        const int64_t prev = iterate(report);
         const bool quit = quitPressed_ || (options.maxIterations >= 0 && n + 1 >= options.maxIterations);
         if (quit) {  // saveQueued: save and leave (Learner.cpp:1007-1010)
             if (!config.checkpointFolder.empty()) Save();
@@ -1032,7 +1184,8 @@ inline void Learner::Start() {
         report.Finish();
         if (options.displayReport)
             report.Display({"Average Step Reward", "Policy Entropy", "Mean KL Divergence", "SB3 Clip Fraction", "",
-                            "Policy Update Magnitude", "Critic Update Magnitude", "", "Collection Steps/Second",
+                            "Policy Update Magnitude", "Critic Update Magnitude", "Transfer Learn Loss",
+                            "Transfer Learn Accuracy", "Old Policy Entropy", "", "Collection Steps/Second",
                             "Consumption Steps/Second", "Overall Steps/Second", "", "Collection Time", "Consumption Time",
                             "-PPO Learn Time", "", "Collected Timesteps", "Total Timesteps", "Total Iterations"});
     }
@@ -1143,6 +1296,14 @@ inline void Learner::SaveModels(const std::filesystem::path& folder, bool saveOp
     detail::Tensor tstep{"I64", {1}, std::vector<char>(8)};
     std::memcpy(tstep.bytes.data(), &step, 8);
     ts["step"] = tstep;
+    // one AdamW step count per model: they differ only after transfer learning (the critic's does not advance there);
+    // while they are equal the files are what they always were ("step" alone, the policy's)
+    std::map<int, int64_t> steps;
+    bool differ = false;
+    for (const ModelSpec& m : models) {
+        RLGC::RlgpuCheck(rlgpu_ppo_model_optimizer_step(ppo_, m.index, &steps[m.index]), "optimizer step");
+        differ |= steps[m.index] != step;
+    }
     const float lrs[3] = {config.ppo.policyLR, config.ppo.criticLR, std::min(config.ppo.policyLR, config.ppo.criticLR)};
     const bool adam = config.ppo.policy.optimType == ModelOptimType::ADAM;
     for (const ModelSpec& m : models) {
@@ -1156,13 +1317,18 @@ inline void Learner::SaveModels(const std::filesystem::path& folder, bool saveOp
             std::memcpy(t.bytes.data(), mv.data() + (size_t)k * cnt, (size_t)cnt * 4);
             ts[std::string(m.name) + (k ? ".exp_avg_sq" : ".exp_avg")] = std::move(t);
         }
+        if (differ) {
+            detail::Tensor t{"I64", {1}, std::vector<char>(8)};
+            std::memcpy(t.bytes.data(), &steps[m.index], 8);
+            ts[std::string(m.name) + ".step"] = std::move(t);
+        }
         // <NAME>_OPTIM.lt: libtorch's own AdamW::save (Models.cpp:122-125)
         const auto tmp = detail::TempFile("optim.f32");
         detail::WriteFile(tmp, mv.data(), mv.size() * 4);
         char lr[32], wd[32];
         std::snprintf(lr, sizeof lr, "%.9g", (double)lrs[m.index]);
         std::snprintf(wd, sizeof wd, "%.9g", adam ? 0.0 : 1e-2);
-        std::vector<std::string> a{"save", (folder / m.FileName("_OPTIM")).string(), tmp.string(), std::to_string(step), lr,
+        std::vector<std::string> a{"save", (folder / m.FileName("_OPTIM")).string(), tmp.string(), std::to_string(steps[m.index]), lr,
                                    "0.9", "0.999", "1e-08", wd};
         for (auto& s : m.ParamShapes()) a.push_back(s);
         try {
@@ -1254,8 +1420,15 @@ inline void Learner::Load() {
         int64_t s = 0;
         std::memcpy(&s, ts.at("step").bytes.data(), 8);
         RLGC::RlgpuCheck(rlgpu_ppo_set_optimizer_step(ppo_, s), "optimizer step");
+        for (const ModelSpec& m : models) {  // per-model counts, written when they differ
+            const std::string key = std::string(m.name) + ".step";
+            if (!ts.count(key)) continue;
+            std::memcpy(&s, ts.at(key).bytes.data(), 8);
+            RLGC::RlgpuCheck(rlgpu_ppo_set_model_optimizer_step(ppo_, m.index, s), "optimizer step");
+        }
     } else {  // the reference's <NAME>_OPTIM.lt archives (Models.cpp:168-186); a model without one is reset
         int64_t s = 0;
+        std::map<int, int64_t> own;  // each archive's own count (they differ after transfer learning)
         for (const ModelSpec& m : models) {
             int64_t off = 0, cnt = 0;
             RLGC::RlgpuCheck(rlgpu_ppo_model_range(ppo_, m.index, &off, &cnt), "model range");
@@ -1275,10 +1448,12 @@ inline void Learner::Load() {
             std::filesystem::remove(tmp);
             if ((int64_t)raw.size() != 8 + 2 * cnt * 4) throw std::runtime_error("optimizer archive " + p.string() + " has other sizes");
             std::memcpy(&s, raw.data(), 8);
+            own[m.index] = s;
             detail::HipOk(hipMemcpy(dm + off, raw.data() + 8, (size_t)cnt * 4, hipMemcpyHostToDevice), "exp_avg");
             detail::HipOk(hipMemcpy(dv + off, raw.data() + 8 + cnt * 4, (size_t)cnt * 4, hipMemcpyHostToDevice), "exp_avg_sq");
         }
-        RLGC::RlgpuCheck(rlgpu_ppo_set_optimizer_step(ppo_, s), "optimizer step");
+        RLGC::RlgpuCheck(rlgpu_ppo_set_optimizer_step(ppo_, s), "optimizer step");  // a model without an archive: the last read
+        for (auto& [mi, c] : own) RLGC::RlgpuCheck(rlgpu_ppo_set_model_optimizer_step(ppo_, mi, c), "optimizer step");
     }
     std::printf(" > Done.\n");
 }

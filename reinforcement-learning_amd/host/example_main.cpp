@@ -153,6 +153,21 @@ int main(int argc, char** argv) {
     cfg.trainAgainstOldVersions = false;
     cfg.sendMetrics = false;
     std::string idFile, nonce, resaveTo;
+    // --transfer-learn DIR: Learner::StartTransferLearn from DIR's POLICY.lt (+ SHARED_HEAD.lt) instead of the PPO loop
+    bool transferLearn = false, tlMapActs = false;
+    TransferLearnConfig tl;
+    tl.makeOldObsFn = [] { return new AdvancedObs(); };
+    tl.makeOldActFn = [] { return new DefaultAction(); };
+    tl.oldPolicyConfig.layerSizes = {512, 512};
+    auto intList = [](const std::string& v) {
+        std::vector<int> out;
+        for (size_t at = 0; at < v.size();) {
+            const size_t c = std::min(v.find(',', at), v.size());
+            out.push_back(std::atoi(v.substr(at, c - at).c_str()));
+            at = c + 1;
+        }
+        return out;
+    };
     for (int i = 1; i < argc; i++) {
         auto next = [&]() -> const char* {
             if (i + 1 >= argc) throw std::invalid_argument(std::string("missing value after ") + argv[i]);
@@ -178,6 +193,17 @@ int main(int argc, char** argv) {
                 cfg.ppo.useGuidingPolicy = true;
                 cfg.ppo.guidingPolicyPath = next();
             } else if (!std::strcmp(argv[i], "--guiding-strength")) cfg.ppo.guidingStrength = std::strtof(next(), nullptr);
+            else if (!std::strcmp(argv[i], "--transfer-learn")) {
+                transferLearn = true;
+                tl.oldModelsPath = next();
+            } else if (!std::strcmp(argv[i], "--old-policy-layers")) tl.oldPolicyConfig.layerSizes = intList(next());
+            else if (!std::strcmp(argv[i], "--old-shared-layers")) tl.oldSharedHeadConfig.layerSizes = intList(next());
+            else if (!std::strcmp(argv[i], "--tl-lr")) tl.lr = std::strtof(next(), nullptr);
+            else if (!std::strcmp(argv[i], "--tl-epochs")) tl.epochs = std::atoi(next());
+            else if (!std::strcmp(argv[i], "--tl-kl")) tl.useKLDiv = true;
+            else if (!std::strcmp(argv[i], "--tl-loss-scale")) tl.lossScale = std::strtof(next(), nullptr);
+            else if (!std::strcmp(argv[i], "--tl-loss-exponent")) tl.lossExponent = std::strtof(next(), nullptr);
+            else if (!std::strcmp(argv[i], "--tl-map-acts")) tlMapActs = true;  // an identity mapActsFn: shows the refusal
             else if (!std::strcmp(argv[i], "--activation")) {  // ModelConfig::activationType of every model
                 const std::string a = next();
                 ModelActivationType t;
@@ -206,10 +232,13 @@ int main(int argc, char** argv) {
                                  "[--self-play] [--fp32-inference] [--policy-temperature X] [--mask-entropy] "
                                  "[--standardize-obs [--min-obs-std X]] "
                                  "[--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm] [--guiding-policy DIR "
-                                 "[--guiding-strength X]] [--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);
+                                 "[--guiding-strength X]] [--transfer-learn DIR [--old-policy-layers a,b,..] [--old-shared-layers a,b,..] "
+                                 "[--tl-lr X] [--tl-epochs N] [--tl-kl] [--tl-loss-scale X] [--tl-loss-exponent X] [--tl-map-acts]] "
+                                 "[--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);
             return 2;
         }
     }
+    if (transferLearn) opt.displayReport = true;
     const int players = 4 * cfg.numGames;
     cfg.ppo.tsPerItr = (int64_t)opt.rolloutLen * players;  // one rollout per iteration (or that many trajectory steps)
     cfg.ppo.batchSize = cfg.ppo.tsPerItr;
@@ -239,6 +268,20 @@ int main(int argc, char** argv) {
             if (!resaveTo.empty()) {  // the loaded checkpoint, saved again elsewhere without training
                 learner.config.checkpointFolder = resaveTo;
                 learner.Save();
+            } else if (transferLearn) {  // the old models take the trained ones' activation and LayerNorm setting
+                for (PartialModelConfig* m : {&tl.oldPolicyConfig, &tl.oldSharedHeadConfig}) {
+                    m->activationType = cfg.ppo.policy.activationType;
+                    m->addLayerNorm = cfg.ppo.policy.addLayerNorm;
+                }
+                tl.oldSharedHeadConfig.addOutputLayer = false;
+                tl.batchSize = (int)cfg.ppo.tsPerItr;
+                if (tlMapActs)
+                    tl.mapActsFn = [](const Player&, const GameState&) {
+                        std::vector<int> m(RLGPU_ACTIONS);
+                        for (int k = 0; k < RLGPU_ACTIONS; k++) m[k] = k;
+                        return m;
+                    };
+                learner.StartTransferLearn(tl);  // --iterations of Start()'s loop; saves at its end, displays each report
             } else {
                 for (int64_t it = 0; it < opt.maxIterations; it++) {
                     Report report;

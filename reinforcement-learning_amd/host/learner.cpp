@@ -1012,6 +1012,77 @@ rlgpu_learner_report Learner::Iterate() {
     return r;
 }
 
+rlgpu_learner_report Learner::TransferIterate(const rlgpu_transfer_config& tc) {
+    const auto refuse = [](const char* why) {
+        throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, std::string("transfer learning: ") + why);
+    };
+    if (!teacher_) throw rlgpu::Error(RLGPU_ERR_STATE, "transfer learning: no teacher set (rlgpu_learner_set_teacher)");
+    if (cfg_.world > 1) refuse("world > 1 (the whole-batch mean and the policy-only step are not reduced over ranks)");
+    if (K_ > 1) refuse("frame stacking (the teacher would need its own frame history)");
+    if (trajMode()) refuse("the trajectory mode (the batch is the rollout's rows)");
+    if (obsStd_) refuse("obs standardisation (the teacher would need the raw rows)");
+    if (cfg_.deterministic) refuse("deterministic collection (the reference samples the batch's actions)");
+    if (oldTeam_ >= 0) refuse("an old version playing (the batch is collected by the current policy alone)");
+    rlgpu_ppo_config tcfg{};
+    RlgpuCheck(rlgpu_ppo_get_config(teacher_, &tcfg), "teacher config");
+    if (tcfg.obs_size != exp_.W || tcfg.num_actions != ACT)  // the teacher reads the rollout's own rows
+        refuse("a teacher whose obs_size / num_actions are not the env's (another obs builder or action parser: its rows "
+               "would have to be built on the host)");
+    RLGPU_REQUIRE(tc.epochs >= 0, "transfer learning: epochs must be >= 0");
+    RLGPU_REQUIRE(std::isfinite(tc.lr) && tc.lr >= 0.f, "transfer learning: lr must be finite and >= 0");
+    RLGPU_REQUIRE(std::isfinite(tc.loss_scale), "transfer learning: loss_scale must be finite");
+    RLGPU_REQUIRE(std::isfinite(tc.loss_exponent) && tc.loss_exponent >= 1.f,
+                  "transfer learning: loss_exponent must be finite and >= 1 (below 1 the loss's backward is inf * 0 = NaN on "
+                  "every masked column, in the reference too)");
+    rlgpu_learner_report r{};
+    auto t0 = clk::now();
+    Collect();
+    auto t0i = clk::now();
+    hipCheck(hipStreamSynchronize(s_), "sync");
+    auto t1 = clk::now();
+    r.collect_issue_s = secs(t0, t0i);
+    // no consume: no critic pass, no GAE
+    const int T = exp_.T, P = exp_.P;
+    const rlgpu_rollout_view& v = exp_.v;
+    const int64_t N = (int64_t)T * P;
+    rlgpu_ppo* h = ppo_->handle();
+    tlProbs_.Reserve(N * ACT, s_);
+    tlArgmax_.Reserve(N, s_);
+    int64_t poff = 0, pcount = 0;
+    RlgpuCheck(rlgpu_ppo_model_range(h, 0, &poff, &pcount), "model range");
+    tlSnapshot_.Reserve(pcount + 512, s_);  // the policy model, then the norm kernel's partials
+    float* params = nullptr;
+    RlgpuCheck(rlgpu_ppo_buffers(h, &params, nullptr, nullptr), "buffers");
+    float* M = ppo_->metrics();
+    RlgpuCheck(rlgpu_ppo_teacher_probs(teacher_, v.obs, v.masks, N, nullptr, ACT, tlProbs_.p, tlArgmax_.p, M, s_), "teacher pass");
+    hipCheck(hipMemcpyAsync(tlSnapshot_.p, params + poff, (size_t)pcount * sizeof(float), hipMemcpyDeviceToDevice, s_), "snapshot");
+    rlgpu_ppo_config pc{};
+    RlgpuCheck(rlgpu_ppo_get_config(h, &pc), "config");
+    const int32_t maxRows = pc.max_rows;
+    for (int epoch = 0; epoch < tc.epochs; epoch++) {
+        for (int64_t s0 = 0; s0 < N; s0 += maxRows)  // the metrics are epoch 0's, as the reference reports them
+            RlgpuCheck(rlgpu_ppo_transfer_chunk(h, v.obs, v.masks, tlProbs_.p, tlArgmax_.p, nullptr, s0,
+                                                (int32_t)std::min<int64_t>(maxRows, N - s0), N, tc.use_kl, tc.loss_scale,
+                                                tc.loss_exponent, epoch == 0 ? M : nullptr, s_),
+                       "transfer chunk");
+        RlgpuCheck(rlgpu_ppo_transfer_step(h, tc.lr, s_), "transfer step");
+    }
+    // "Policy Update Magnitude": overwritten, not summed (one value per iteration)
+    RlgpuCheck(rlgpu_diff_norm(tlSnapshot_.p, params + poff, pcount, M + RLGPU_M_TL_UPDATE_MAGNITUDE, tlSnapshot_.p + pcount, s_),
+               "update magnitude");
+    ppo_->minibatches++;  // one set of whole-batch means per transfer iteration
+    FinishIteration();
+    auto t2i = clk::now();
+    hipCheck(hipStreamSynchronize(s_), "sync");
+    auto t2 = clk::now();
+    r.learn_issue_s = secs(t1, t2i);
+    r.collect_s = secs(t0, t1);
+    r.learn_s = secs(t1, t2);
+    r.env_steps = (int64_t)T * cfg_.num_arenas;
+    r.env_launch_arenas = cfg_.num_arenas / std::max(1, collectGroupsUsed_);
+    return r;
+}
+
 void Learner::Start(int64_t iterations) {
     for (int64_t i = 0; i < iterations; i++) Iterate();
 }
@@ -1134,6 +1205,22 @@ extern "C" int rlgpu_learner_iterate(rlgpu_learner* h, rlgpu_learner_report* rep
         if (rep) *rep = r;
     });
 }
+extern "C" int rlgpu_learner_set_teacher(rlgpu_learner* h, rlgpu_ppo* teacher) {
+    return rlgpu::guarded([&] {
+        RLGPU_LEARNER(h);
+        h->L->SetTeacher(teacher);
+    });
+}
+
+extern "C" int rlgpu_learner_transfer_iterate(rlgpu_learner* h, const rlgpu_transfer_config* tc, rlgpu_learner_report* rep) {
+    return rlgpu::guarded([&] {
+        RLGPU_LEARNER(h);
+        RLGPU_REQUIRE(tc, "rlgpu_learner_transfer_iterate: null config");
+        rlgpu_learner_report r = h->L->TransferIterate(*tc);
+        if (rep) *rep = r;
+    });
+}
+
 extern "C" int rlgpu_learner_collect(rlgpu_learner* h) {
     return rlgpu::guarded([&] {
         RLGPU_LEARNER(h);

@@ -198,6 +198,11 @@ public:
     void FinishIteration();   // obs[0] <- obs[T], step counters
     rlgpu_learner_report Iterate();
     void Start(int64_t iterations);  // Learner::Start loop (Learner.cpp:482-1056), a fixed count
+    // Learner::StartTransferLearn's iteration (Learner.cpp:330-462): collect with the current policy, one teacher pass
+    // over the rollout's T * P rows, tc.epochs times [every chunk, then the policy-only step], finish.  The teacher is
+    // borrowed (SetTeacher); rlgpu_learner_transfer_iterate documents what is refused.
+    void SetTeacher(rlgpu_ppo* teacher) { teacher_ = teacher; }
+    rlgpu_learner_report TransferIterate(const rlgpu_transfer_config& tc);
 
     void SetOldTeam(int team) { oldTeam_ = team; }
     // PPOLearnerConfig::useGuidingPolicy: the guide's flat fp32 parameters (rlgpu_ppo_set_guide's layout) and
@@ -295,6 +300,11 @@ private:
     float guideStrength_ = 0.f;
     bool hasGuide_ = false;
     void NeedLearnRows(int64_t n, const char* what) const;
+    // transfer learning: the borrowed teacher handle, its target probabilities [T * P][ACT] and argmax [T * P] of the
+    // rollout's rows, and the policy model's snapshot (reserved by the first transfer iteration; empty otherwise)
+    rlgpu_ppo* teacher_ = nullptr;
+    DevArray<float> tlProbs_, tlSnapshot_;
+    DevArray<int32_t> tlArgmax_;
     DevArray<int32_t> truncRows_, truncCount_;
     DevArray<char> selScratch_;
     size_t selBytes_ = 0;

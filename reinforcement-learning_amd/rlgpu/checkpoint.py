@@ -205,10 +205,15 @@ def save(learner, folder, keep=8):
         shapes[mi] = [tuple(p.shape) for p in mod.parameters()]
         write_model(mod, model_path(path, MODEL_NAMES[mi]))
     step, m, v = ppo.optimizer_state()
+    # one AdamW step count per model: they differ only after transfer learning, whose steps leave the critic's alone;
+    # while they are equal the file is what it always was ("step" alone, the policy's)
+    steps = {mi: ppo.model_optimizer_step(mi) for mi in ppo.models}
     t = {"step": torch.tensor([step], dtype=torch.int64)}
     for mi in ppo.models:
         name = MODEL_NAMES[mi]
         o, c = ppo.model_range(mi)
+        if len(set(steps.values())) > 1:
+            t[name + ".step"] = torch.tensor([steps[mi]], dtype=torch.int64)
         t[name + ".exp_avg"] = m[o:o + c].detach().cpu().contiguous()
         t[name + ".exp_avg_sq"] = v[o:o + c].detach().cpu().contiguous()
     save_file(t, os.path.join(path, OPTIM_FILE))
@@ -219,7 +224,7 @@ def save(learner, folder, keep=8):
     else:
         for mi in ppo.models:
             name = MODEL_NAMES[mi]
-            write_optim_archive(model_path(path, name, "_OPTIM"), shapes[mi], step, opts["lr"][mi], opts["betas"], opts["eps"],
+            write_optim_archive(model_path(path, name, "_OPTIM"), shapes[mi], steps[mi], opts["lr"][mi], opts["betas"], opts["eps"],
                                 opts["weight_decay"], t[name + ".exp_avg"].numpy(), t[name + ".exp_avg_sq"].numpy())
     if keep != -1:
         dirs = numbered_dirs(folder)
@@ -281,11 +286,14 @@ def load(learner, folder, allow_missing_models=True):
             m[o:o + c].copy_(t[name + ".exp_avg"].to(m.device))
             v[o:o + c].copy_(t[name + ".exp_avg_sq"].to(v.device))
         ppo.set_optimizer_step(int(t["step"][0]))
+        for mi in ppo.models:  # per-model counts, written when they differ
+            if MODEL_NAMES[mi] + ".step" in t:
+                ppo.set_model_optimizer_step(mi, int(t[MODEL_NAMES[mi] + ".step"][0]))
     elif any(os.path.exists(model_path(path, MODEL_NAMES[mi], "_OPTIM")) for mi in ppo.models):
         # a reference checkpoint: its AdamW archives (Model::Load, Models.cpp:168-186); a model
         # without one resets its moments, as the reference resets that model's optimizer
         step, m, v = ppo.optimizer_state()
-        steps = []
+        steps, own = [], {}
         for mi in ppo.models:
             name = MODEL_NAMES[mi]
             o, c = ppo.model_range(mi)
@@ -306,7 +314,11 @@ def load(learner, folder, allow_missing_models=True):
             m[o:o + c].copy_(torch.from_numpy(ea).to(m.device))
             v[o:o + c].copy_(torch.from_numpy(eas).to(v.device))
             steps.append(s_)
+            own[mi] = s_
         ppo.set_optimizer_step(max(steps) if steps else 0)
+        for mi, s_ in own.items():  # each archive's own count (they differ after transfer learning)
+            if s_ != max(steps):
+                ppo.set_model_optimizer_step(mi, s_)
     else:
         warnings.warn(f"no optimizer state found in {path}, optimizer will be reset")
         step, m, v = ppo.optimizer_state()

@@ -192,10 +192,10 @@ def sync_from_rank0(learner, group=None, error=None):
                 learner.versions.add_version(int(ts[k]), t)
 
 
-def load_guiding_policy(ppo, folder):
-    """The guiding policy's flat parameters from <folder>/POLICY.lt (and SHARED_HEAD.lt when ppo has a shared head),
-    in parameters() order, on ppo's device.  A missing file or a model of another size is an error naming the file
-    (the reference loads the guide with allowNotExist = false)."""
+def load_policy_models(ppo, folder, what="guiding policy"):
+    """The flat parameters of the policy models of ppo's architecture from <folder>/POLICY.lt (and SHARED_HEAD.lt when
+    ppo has a shared head), in parameters() order, on ppo's device.  A missing file or a model of another size is an
+    error naming the file (the reference loads the guide and the transfer-learning teacher with allowNotExist = false)."""
     import os
     import torch
     from . import checkpoint as _ckpt
@@ -205,14 +205,63 @@ def load_guiding_policy(ppo, folder):
             continue
         p = _ckpt.model_path(folder, _ckpt.MODEL_NAMES[mi])
         if not os.path.exists(p):
-            raise FileNotFoundError(f"guiding policy: {p} does not exist")
+            raise FileNotFoundError(f"{what}: {p} does not exist")
         tensors = _ckpt.read_model_state(p)
         want, got = ppo.model_sizes(mi), [t.numel() for t in tensors]
         if got != want:
-            raise ValueError(f"guiding policy: {p} has different sizes than the current model:\n"
+            raise ValueError(f"{what}: {p} has different sizes than the current model:\n"
                              f" > Current model: {want},\n > Saved model:   {got}")
         parts += [t.reshape(-1) for t in tensors]
     return torch.cat(parts).to(ppo.device)
+
+
+def load_guiding_policy(ppo, folder):
+    """load_policy_models for PPOLearnerConfig::guidingPolicyPath: the layout rlgpu_ppo_set_guide takes."""
+    return load_policy_models(ppo, folder, "guiding policy")
+
+
+def load_teacher(teacher, folder):
+    """TransferLearnConfig::oldModelsPath: <folder>/POLICY.lt (+ SHARED_HEAD.lt) into the teacher handle `teacher` (a PPO
+    built from the old policy / shared-head configuration); its 16-bit copy is refreshed.  A missing file is an error."""
+    flat = load_policy_models(teacher, folder, "transfer-learning teacher")
+    o = 0
+    for mi in teacher.models:
+        if mi == 1:
+            continue
+        dst = teacher.model_slice(mi)
+        dst.copy_(flat[o:o + dst.numel()])
+        o += dst.numel()
+    teacher.refresh_half()
+    return teacher
+
+
+class TransferLearnConfig:
+    """GGL::TransferLearnConfig (PPO/TransferLearnConfig.h) in snake case.  make_old_obs_fn / make_old_act_fn /
+    map_acts_fn: None means the engine's own obs builder and action parser and no action map, the teacher this level
+    supports; old_policy_layers / old_shared_layers: the teacher's hidden widths (oldPolicyConfig / oldSharedHeadConfig);
+    old_models_path: the directory with its POLICY.lt (and SHARED_HEAD.lt)."""
+
+    def __init__(self, **kw):
+        self.make_old_obs_fn = None
+        self.make_old_act_fn = None
+        self.map_acts_fn = None
+        self.old_policy_layers = (512, 512)
+        self.old_shared_layers = ()
+        # oldPolicyConfig / oldSharedHeadConfig's activationType and addLayerNorm (one setting for both old models, as
+        # for the trained ones); None = the trained models' setting
+        self.old_activation = None
+        self.old_layer_norm = None
+        self.old_models_path = None       # required: the reference loads the old models with allowNotExist = false
+        self.lr = 3e-4
+        self.batch_size = 50_000          # no minibatches: the whole batch per epoch
+        self.epochs = 5
+        self.use_kl_div = False
+        self.loss_scale = 500.0
+        self.loss_exponent = 1.0
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError(f"unknown TransferLearnConfig field {k}")
+            setattr(self, k, v)
 
 
 # ------------------------------------------------------------------ config
@@ -344,6 +393,12 @@ class _CReport(ctypes.Structure):
                 ("env_kernel_max_ms", ctypes.c_double)]
 
 
+class _CTransfer(ctypes.Structure):
+    """rlgpu_transfer_config (include/rlgpu_learner.h)."""
+    _fields_ = [("lr", ctypes.c_float), ("epochs", ctypes.c_int32), ("use_kl", ctypes.c_int32),
+                ("loss_scale", ctypes.c_float), ("loss_exponent", ctypes.c_float)]
+
+
 def _bind():
     L = _lib.lib()
     vp = ctypes.c_void_p
@@ -367,6 +422,8 @@ def _bind():
     L.rlgpu_learner_set_obs_standardization.argtypes = [vp, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_int32]
     L.rlgpu_learner_get_obs_stat.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), vp, vp]
     L.rlgpu_learner_set_obs_stat.argtypes = [vp, ctypes.c_int64, vp, vp]
+    L.rlgpu_learner_set_teacher.argtypes = [vp, vp]
+    L.rlgpu_learner_transfer_iterate.argtypes = [vp, ctypes.POINTER(_CTransfer), ctypes.POINTER(_CReport)]
     return L
 
 
@@ -752,6 +809,81 @@ class Learner:
 
     def finish_iteration(self):
         _lib.check(_lib.lib().rlgpu_learner_finish_iteration(self._h), "rlgpu_learner_finish_iteration")
+
+    # ---------------------------------------------------------------- transfer learning
+    def set_teacher(self, teacher):
+        """rlgpu_learner_set_teacher: borrow `teacher` (a PPO built from the old policy / shared-head configuration, its
+        parameters loaded -- load_teacher); kept alive with the learner.  None removes it."""
+        self._teacher = teacher
+        _lib.check(_lib.lib().rlgpu_learner_set_teacher(self._h, teacher._h if teacher is not None else None),
+                   "rlgpu_learner_set_teacher")
+
+    def make_teacher(self, cfg):
+        """The teacher handle of a TransferLearnConfig: the old policy / shared-head widths on the engine's obs and
+        action widths, the old models' activation and LayerNorm setting (cfg.old_activation / old_layer_norm, default this
+        learner's), this learner's inference format, temperature and mask_entropy (PPOLearnerConfig's, as the reference
+        applies them to the old models), a minimal unused critic; parameters from cfg.old_models_path (required; a
+        missing file is an error)."""
+        from .ppo import PPO
+        if cfg.make_old_obs_fn is not None or cfg.make_old_act_fn is not None or cfg.map_acts_fn is not None:
+            raise _lib.RLGPUError("transfer learning runs the engine's own obs builder and action parser for the teacher; "
+                                  "what remains for another builder, parser or action map is the host-side evaluation of "
+                                  "the old builders (the C ABI already takes teacher rows and maps)")
+        if cfg.old_models_path is None:
+            raise ValueError("TransferLearnConfig.old_models_path is not set (the directory with the old POLICY.lt)")
+        c = self.cfg
+        t = PPO(obs_size=self.W, num_actions=ACTIONS, policy_layers=tuple(cfg.old_policy_layers), critic_layers=(8,),
+                shared_layers=tuple(cfg.old_shared_layers),
+                layer_norm=c.layer_norm if cfg.old_layer_norm is None else cfg.old_layer_norm,
+                activation=c.activation if cfg.old_activation is None else cfg.old_activation,
+                max_rows=min(self.T * self.P, 65536), init=False, device=self.device,
+                infer_fp16=c.infer_fp16, policy_temperature=c.policy_temperature, mask_entropy=c.mask_entropy)
+        try:
+            load_teacher(t, cfg.old_models_path)
+        except Exception:
+            t.close()
+            raise
+        return t
+
+    def transfer_iterate(self, cfg):
+        """One iteration of Learner::StartTransferLearn (rlgpu_learner_transfer_iterate): collect, the teacher pass, cfg.epochs
+        whole-batch epochs with the policy-only step.  Returns the report dict with the reference's entries under
+        "report"."""
+        c = _CTransfer(float(cfg.lr), int(cfg.epochs), int(bool(cfg.use_kl_div)), float(cfg.loss_scale), float(cfg.loss_exponent))
+        _lib.check(_lib.lib().rlgpu_learner_set_old_team(self._h, -1), "rlgpu_learner_set_old_team")
+        self._metrics(True)
+        rep = _CReport()
+        t0 = time.perf_counter()
+        _lib.check(_lib.lib().rlgpu_learner_transfer_iterate(self._h, ctypes.byref(c), ctypes.byref(rep)),
+                   "rlgpu_learner_transfer_iterate")
+        m, _ = self._metrics(True)
+        report = {"Old Policy Entropy": m[13], "Transfer Learn Accuracy": m[12], "Transfer Learn Loss": m[11],
+                  "Policy Entropy": m[0], "Policy Update Magnitude": m[14]}
+        return {"report": report, "iteration_s": time.perf_counter() - t0, "collect_s": rep.collect_s, "learn_s": rep.learn_s,
+                "collect_issue_s": rep.collect_issue_s, "learn_issue_s": rep.learn_issue_s}
+
+    def start_transfer_learn(self, cfg, iterations, teacher=None):
+        """Learner::StartTransferLearn for a fixed count of iterations; the batch is the rollout (cfg.batch_size is what
+        the caller sized rollout_len from: ceil(batch_size / players)).  teacher: a PPO handle, else built from cfg
+        (make_teacher).  Saves as iterate does when cfg.checkpoint_folder is set.  Returns the iterations' reports."""
+        own = teacher is None
+        teacher = self.make_teacher(cfg) if own else teacher
+        self.set_teacher(teacher)
+        out = []
+        try:
+            for _ in range(iterations):
+                prev = self.total_steps
+                r = self.transfer_iterate(cfg)
+                if self.cfg.checkpoint_folder:
+                    per = self.cfg.ts_per_save or self.T * self.P * self.world
+                    if self.total_steps // per > prev // per:
+                        r["checkpoint"] = self.save()
+                out.append(r)
+        finally:
+            self.set_teacher(None)
+            if own:
+                teacher.close()
+        return out
 
     def iterate(self):
         """One PPO iteration (collect T steps, consume, learn); returns a report dict."""

@@ -20,8 +20,10 @@ from ._lib import alias
 MAX_LAYERS = 8
 NUM_METRICS = 16
 METRICS = ("entropy", "kl", "policy_loss", "critic_loss", "ratio", "clip_fraction", "count",
-           "grad_norm_policy", "grad_norm_critic", "grad_norm_shared", "guiding_loss")
+           "grad_norm_policy", "grad_norm_critic", "grad_norm_shared", "guiding_loss", "tl_loss", "tl_accuracy",
+           "tl_old_entropy")
 M_GUIDING_LOSS = 10  # RLGPU_M_GUIDING_LOSS
+M_TL_LOSS, M_TL_ACCURACY, M_TL_OLD_ENTROPY = 11, 12, 13  # RLGPU_M_TL_*
 MODEL_NAMES = ("policy", "critic", "shared_head")  # GGL::Model::modelName (PPOLearner.cpp:66-72)
 
 
@@ -79,6 +81,13 @@ def _bind():
     L.rlgpu_ppo_zero_grad.argtypes = [vp, vp]
     L.rlgpu_ppo_optimizer_state.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.rlgpu_ppo_set_optimizer_step.argtypes = [vp, i64]
+    L.rlgpu_ppo_model_optimizer_step.argtypes = [vp, i32, ctypes.POINTER(i64)]
+    L.rlgpu_ppo_set_model_optimizer_step.argtypes = [vp, i32, i64]
+    L.rlgpu_ppo_teacher_probs.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp]
+    L.rlgpu_teacher_probs_from_logits.argtypes = [vp, vp, i64, i32, vp, i32, f32, i32, vp, vp, vp, vp]
+    L.rlgpu_ppo_transfer_chunk.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i64, i32, f32, f32, vp, vp]
+    L.rlgpu_ppo_transfer_step.argtypes = [vp, f32, vp]
+    L.rlgpu_diff_norm.argtypes = [vp, vp, i64, vp, vp, vp]
     L.rlgpu_ppo_set_version.argtypes = [vp, vp, vp]
     L.rlgpu_ppo_infer_actions_mixed.argtypes = [vp, vp, vp, i32, i32, u64, vp, vp, vp, vp]
     L.rlgpu_ppo_infer_actions_rows.argtypes = [vp, vp, vp, i32, i64, i32, u64, vp, vp, vp, vp]
@@ -463,6 +472,87 @@ class PPO:
     def set_optimizer_step(self, step):
         _lib.check(_lib.lib().rlgpu_ppo_set_optimizer_step(self._h, int(step)), "set_optimizer_step")
 
+    def model_optimizer_step(self, model):
+        """The AdamW step count of one model (0 policy, 1 critic, 2 shared head): equal for all models unless
+        transfer_step ran, which leaves the critic's alone."""
+        step = ctypes.c_int64()
+        _lib.check(_lib.lib().rlgpu_ppo_model_optimizer_step(self._h, model, ctypes.byref(step)), "model_optimizer_step")
+        return step.value
+
+    def set_model_optimizer_step(self, model, step):
+        _lib.check(_lib.lib().rlgpu_ppo_set_model_optimizer_step(self._h, model, int(step)), "set_model_optimizer_step")
+
+    # ---------------------------------------------------------------- transfer learning
+    def teacher_probs(self, obs, masks, action_map=None, num_actions_out=None, metrics=None):
+        """This handle as the teacher of PPOLearner::TransferLearn: its inference forward over obs [n, obs_size], the
+        clamped masked softmax at its policy_temperature over masks [n, num_actions], and -- action_map int32
+        [n, num_actions_out] given -- the gather out[i][k] = old[i][map[i][k]].  Returns (probs f32 [n, A_out], argmax
+        int32 [n]); the teacher's mean entropy is added to metrics[M_TL_OLD_ENTROPY] (metrics: a NUM_METRICS device
+        tensor, usually the student's; default this handle's own).  Map entries must lie in [0, num_actions): they are
+        not checked on the device."""
+        import torch
+        n = obs.shape[0]
+        A = self.num_actions if action_map is None else (num_actions_out or action_map.shape[-1])
+        if action_map is not None and (action_map.dtype != torch.int32 or tuple(action_map.shape) != (n, A)
+                                       or not action_map.is_contiguous()):
+            raise _lib.RLGPUError("action_map must be contiguous int32 [rows, num_actions_out]")
+        probs = torch.empty((n, A), device=self.device)
+        arg = torch.empty(n, dtype=torch.int32, device=self.device)
+        metrics = self.metrics if metrics is None else metrics
+        _lib.check(_lib.lib().rlgpu_ppo_teacher_probs(
+            self._h, _lib.ptr(obs.contiguous()), _lib.ptr(masks.contiguous()), n,
+            _lib.ptr(action_map) if action_map is not None else None, A, _lib.ptr(probs), _lib.ptr(arg), _lib.ptr(metrics),
+            _lib.stream_ptr()), "rlgpu_ppo_teacher_probs")
+        return probs, arg
+
+    def transfer_chunk(self, obs, masks, target_probs, target_argmax, index, start, n, total_rows, use_kl=False,
+                       loss_scale=1.0, loss_exponent=1.0):
+        """rlgpu_ppo_transfer_chunk: rows index[start : start + n] (index None: identity) of a batch of total_rows rows;
+        the distillation loss toward target_probs and its backward through the policy and the shared head, accumulating
+        gradients; this chunk's share of the whole-batch metrics into self.metrics."""
+        for t in (obs, masks, target_probs, target_argmax):
+            if not t.is_contiguous():
+                raise _lib.RLGPUError("transfer_chunk takes contiguous tensors")
+        if target_probs.shape[-1] != self.num_actions or target_probs.shape[0] != masks.shape[0]:
+            raise _lib.RLGPUError("target_probs must be [rows of masks, num_actions]")
+        _lib.check(_lib.lib().rlgpu_ppo_transfer_chunk(
+            self._h, _lib.ptr(obs), _lib.ptr(masks), _lib.ptr(target_probs), _lib.ptr(target_argmax),
+            _lib.ptr(index) if index is not None else None, start, n, total_rows, int(use_kl), loss_scale, loss_exponent,
+            _lib.ptr(self.metrics), _lib.stream_ptr()), "rlgpu_ppo_transfer_chunk")
+
+    def transfer_step(self, lr):
+        """rlgpu_ppo_transfer_step: AdamW at learning rate lr on the policy and the shared head, no gradient clipping; the
+        critic, its moments and its step count stay."""
+        _lib.check(_lib.lib().rlgpu_ppo_transfer_step(self._h, lr, _lib.stream_ptr()), "rlgpu_ppo_transfer_step")
+
+    def transfer_learn(self, teacher, obs, masks, cfg, old_obs=None, old_masks=None, action_map=None):
+        """PPOLearner::TransferLearn (PPOLearner.cpp:583-637) on one batch held on the device: the teacher pass, cfg.epochs
+        times the whole batch in chunks of max_rows followed by transfer_step(cfg.lr).  cfg: a TransferLearnConfig
+        (rlgpu.learner) or anything with its lr / epochs / use_kl_div / loss_scale / loss_exponent.  Returns the report
+        entries of the reference."""
+        import torch
+        N = obs.shape[0]
+        tm = torch.zeros(NUM_METRICS, device=self.device)
+        probs, arg = teacher.teacher_probs(obs if old_obs is None else old_obs, masks if old_masks is None else old_masks,
+                                           action_map, self.num_actions, metrics=tm)
+        before = self.model_slice(0).clone()
+        first = None
+        for _ in range(cfg.epochs):
+            self.metrics.zero_()
+            for b in range(0, N, self.max_rows):
+                self.transfer_chunk(obs, masks, probs, arg, None, b, min(self.max_rows, N - b), N, cfg.use_kl_div,
+                                    cfg.loss_scale, cfg.loss_exponent)
+            if first is None:
+                first = self.metrics.clone()
+            self.transfer_step(cfg.lr)
+        self.metrics.zero_()
+        rep = {"Old Policy Entropy": float(tm[M_TL_OLD_ENTROPY])}
+        if first is not None:
+            rep.update({"Transfer Learn Accuracy": float(first[M_TL_ACCURACY]), "Transfer Learn Loss": float(first[M_TL_LOSS]),
+                        "Policy Entropy": float(first[0])})
+        rep["Policy Update Magnitude"] = diff_norm(before, self.model_slice(0))
+        return rep
+
     def model_sizes(self, model):
         """Per-parameter element counts in torch order (GetSeqSizes, Models.cpp:79-87)."""
         return [p.numel() for p in self.torch_module(model).parameters()]
@@ -505,6 +595,33 @@ def kernel_timing_read():
     _lib.check(_lib.lib().rlgpu_kernel_timing_read(ms.ctypes.data, work.ctypes.data, cnt.ctypes.data, n),
                "rlgpu_kernel_timing_read")
     return {k: (float(ms[i]), float(work[i]), int(cnt[i])) for i, k in enumerate(KERNEL_TIMING_SLOTS)}
+
+
+def teacher_probs_from_logits(logits, masks, temperature=1.0, mask_entropy=False, action_map=None, metrics=None):
+    """rlgpu_teacher_probs_from_logits: PPO.teacher_probs after the forward, from f32 logits [n, A_old] on the device.
+    Returns (probs [n, A_out], argmax int32 [n]); metrics as in PPO.teacher_probs (None: not written)."""
+    import torch
+    _bind()
+    n, a_old = logits.shape
+    A = a_old if action_map is None else action_map.shape[-1]
+    probs = torch.empty((n, A), device=logits.device)
+    arg = torch.empty(n, dtype=torch.int32, device=logits.device)
+    _lib.check(_lib.lib().rlgpu_teacher_probs_from_logits(
+        _lib.ptr(logits.contiguous()), _lib.ptr(masks.contiguous()), n, a_old,
+        _lib.ptr(action_map.contiguous()) if action_map is not None else None, A, temperature, int(mask_entropy),
+        _lib.ptr(probs), _lib.ptr(arg), _lib.ptr(metrics) if metrics is not None else None, _lib.stream_ptr()),
+        "rlgpu_teacher_probs_from_logits")
+    return probs, arg
+
+
+def diff_norm(a, b):
+    """||a - b|| of two device tensors of equal size (rlgpu_diff_norm), as a float."""
+    import torch
+    _bind()
+    out = torch.empty(1, device=a.device)
+    _lib.check(_lib.lib().rlgpu_diff_norm(_lib.ptr(a.contiguous()), _lib.ptr(b.contiguous()), a.numel(), _lib.ptr(out),
+                                          None, _lib.stream_ptr()), "rlgpu_diff_norm")
+    return float(out)
 
 
 def permutation(n, seed, counter, out=None, device="cuda:0"):
