@@ -47,6 +47,12 @@ extern "C" {
 #define RLGPU_MAX_TERMINALS 8 /* terminal conditions per env set */
 #define RLGPU_SS_KICKOFF 0        /* KickoffState */
 #define RLGPU_SS_FUZZED_KICKOFF 1 /* FuzzedKickoffState */
+#define RLGPU_SS_RANDOM 2         /* RandomState(randBallSpeed, randCarSpeed, carsOnGround) */
+#define RLGPU_SS_COMBINED 3       /* CombinedState over a weighted list of the three above */
+#define RLGPU_MAX_STATE_SETTERS 8 /* children of a CombinedState */
+#define RLGPU_SS_RAND_BALL_SPEED 1  /* RandomState flag bits */
+#define RLGPU_SS_RAND_CAR_SPEED 2
+#define RLGPU_SS_CARS_ON_GROUND 4
 
 /* Reward plugins of the device registry: RLGymCPP's CommonRewards (RG/Rewards/CommonRewards.h),
  * KickoffProximityReward2v2Enhanced (RG/Rewards/KickoffProximityReward2v2Enhanced.h) and ExampleMain's
@@ -102,6 +108,13 @@ typedef struct {
     int32_t type;  /* RLGPU_TC_* */
     float param;
 } rlgpu_terminal_spec;
+
+/* One {StateSetter*, weight} of a CombinedState (RG/StateSetters/CombinedState.h:18-31). */
+typedef struct {
+    int32_t type;   /* RLGPU_SS_KICKOFF, _FUZZED_KICKOFF or _RANDOM */
+    float weight;   /* >= 0 and finite */
+    int32_t flags;  /* RLGPU_SS_RANDOM: RLGPU_SS_RAND_BALL_SPEED | _RAND_CAR_SPEED | _CARS_ON_GROUND */
+} rlgpu_state_setter_spec;
 
 /* One contact point (btManifoldPoint subset, bullet units). */
 typedef struct {
@@ -242,8 +255,17 @@ typedef struct {
     /* EnvCreateResult::stateSetter (RLGPU_SS_*): KickoffState (RG/StateSetters/KickoffState.h), or
      * FuzzedKickoffState (FuzzedKickoffState.h:7-26: the kickoff, then every car's position moved by
      * RandFloat(-0.1, 0.1) uu per axis through CarState, RS/Sim/Car/Car.cpp:23-36) -- the skill tracker's
-     * (PolicyVersionManager.cpp:24-31).  The fuzz draws are the arena's Philox stream after the kickoff's. */
+     * (PolicyVersionManager.cpp:24-31).  The fuzz draws are the arena's Philox stream after the kickoff's.
+     * RLGPU_SS_RANDOM: RandomState (RG/StateSetters/RandomState.cpp) with the flag bits of state_setter_flags --
+     * the kickoff, then the ball and the four cars drawn from the same stream (DESIGN.md section 6 fixes the
+     * draw order the reference leaves open).  RLGPU_SS_COMBINED: CombinedState over state_setters[0 ..
+     * n_state_setters) (host memory, copied at create; 1..RLGPU_MAX_STATE_SETTERS children, none of them
+     * COMBINED): one draw picks the child, whose reset follows on the same stream.  The list is read only for
+     * RLGPU_SS_COMBINED, the flags only for RLGPU_SS_RANDOM. */
     int32_t state_setter;
+    int32_t state_setter_flags;
+    const rlgpu_state_setter_spec* state_setters;
+    int32_t n_state_setters;
 } rlgpu_envset_config;
 
 /* Experience-append destinations of the fused step (Learner.cpp:823-861); any may be NULL. */
@@ -390,6 +412,7 @@ int rlgpu_envset_default_plugins(rlgpu_reward_spec* rewards, int32_t* n_rewards,
 
 /* Static sizes for binding checks. */
 int rlgpu_arena_state_size(void);
+int rlgpu_envset_config_size(void);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,13 @@ typedef struct {
     int32_t n_rewards;
     const rlgpu_terminal_spec* terminals;
     int32_t n_terminals;
+    /* EnvCreateResult::stateSetter of the training arenas (rlgpu_envset_config.state_setter, _flags and the
+     * CombinedState list, passed to the env set as they are; 0 = KickoffState).  The list is host memory
+     * copied at create. */
+    int32_t state_setter;
+    int32_t state_setter_flags;
+    const rlgpu_state_setter_spec* state_setters;
+    int32_t n_state_setters;
     /* Experience scheduling.  RLGPU_EXP_ROLLOUT (0, default): a fixed [T, P] rollout trained in full,
      * the unfinished tail bootstrapped from V(obs_T) (the engine's fast path, BASELINE configs).
      * RLGPU_EXP_TRAJECTORIES (1): the reference's -- steps are kept per player until the trajectory

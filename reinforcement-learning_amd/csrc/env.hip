@@ -334,6 +334,53 @@ rl::Plugins plugins_from(const rlgpu_envset_config* cfg) {
     }
     return p;
 }
+
+// the config's state setter as the kernel's table (Plugins::ss), validated: a plain setter is one entry, a
+// CombinedState its children with CombinedState's cumulative weights (CombinedState.h:18-31)
+void state_setters_from(const rlgpu_envset_config* cfg, rl::Plugins& p) {
+    const auto child_ok = [](int type) {
+        return type == RLGPU_SS_KICKOFF || type == RLGPU_SS_FUZZED_KICKOFF || type == RLGPU_SS_RANDOM;
+    };
+    const int all_flags = RLGPU_SS_RAND_BALL_SPEED | RLGPU_SS_RAND_CAR_SPEED | RLGPU_SS_CARS_ON_GROUND;
+    if (cfg->state_setter != RLGPU_SS_COMBINED) {
+        if (!child_ok(cfg->state_setter))
+            throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "rlgpu_envset_create: unknown state setter " +
+                                                          std::to_string(cfg->state_setter) + " (RLGPU_SS_*)");
+        const int flags = cfg->state_setter == RLGPU_SS_RANDOM ? cfg->state_setter_flags : 0;
+        RLGPU_REQUIRE((flags & ~all_flags) == 0, "rlgpu_envset_create: state_setter_flags " + std::to_string(flags) +
+                                                     " has bits outside RLGPU_SS_RAND_BALL_SPEED | _RAND_CAR_SPEED | "
+                                                     "_CARS_ON_GROUND");
+        p.ns = 1;
+        p.ss_combined = 0;
+        p.ss[0] = rlgpu_state_setter_spec{cfg->state_setter, 1.f, flags};
+        p.ss_cum[0] = p.ss_total = 1.f;
+        return;
+    }
+    RLGPU_REQUIRE(cfg->state_setters && cfg->n_state_setters >= 1 && cfg->n_state_setters <= RLGPU_MAX_STATE_SETTERS,
+                  "rlgpu_envset_create: RLGPU_SS_COMBINED needs a state_setters list of 1.." +
+                      std::to_string(RLGPU_MAX_STATE_SETTERS) + " entries, got " +
+                      (cfg->state_setters ? std::to_string(cfg->n_state_setters) : std::string("none")));
+    p.ns = cfg->n_state_setters;
+    p.ss_combined = 1;
+    float total = 0.f;
+    for (int i = 0; i < p.ns; i++) {
+        const rlgpu_state_setter_spec& c = cfg->state_setters[i];
+        const std::string who = "rlgpu_envset_create: state setter " + std::to_string(i);
+        if (c.type == RLGPU_SS_COMBINED)
+            throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, who + " is RLGPU_SS_COMBINED: a nested CombinedState has no device code");
+        if (!child_ok(c.type))
+            throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, who + " has unknown type " + std::to_string(c.type) + " (RLGPU_SS_*)");
+        RLGPU_REQUIRE(std::isfinite(c.weight) && c.weight >= 0.f,
+                      who + " has a negative or invalid weight of " + std::to_string(c.weight));
+        const int flags = c.type == RLGPU_SS_RANDOM ? c.flags : 0;
+        RLGPU_REQUIRE((flags & ~all_flags) == 0, who + " has flags " + std::to_string(flags) +
+                                                     " outside RLGPU_SS_RAND_BALL_SPEED | _RAND_CAR_SPEED | _CARS_ON_GROUND");
+        total += c.weight;  // fp32, list order
+        p.ss[i] = rlgpu_state_setter_spec{c.type, c.weight, flags};
+        p.ss_cum[i] = total;
+    }
+    p.ss_total = total;
+}
 }  // namespace
 
 extern "C" int rlgpu_envset_default_plugins(rlgpu_reward_spec* rewards, int32_t* n_rewards, rlgpu_terminal_spec* terminals,
@@ -448,7 +495,6 @@ rl::StepArgs placed(rlgpu_envset* e, rl::StepArgs g, Range r) {
     g.plug = e->d_plug;
     g.arith = e->cfg.arith;
     g.arena_offset = e->cfg.arena_offset + r.first;
-    g.fuzz = e->cfg.state_setter == RLGPU_SS_FUZZED_KICKOFF;
     g.pen_slots = e->pen_slots;
     g.reward_values = g.build && e->d_reward_values ? e->d_reward_values + p0 * nr : nullptr;
     output_only_rows(e, g);
@@ -529,6 +575,7 @@ void free_set(rlgpu_envset* e) {
 }  // namespace
 
 extern "C" int rlgpu_arena_state_size(void) { return (int)sizeof(rlgpu_arena_state); }
+extern "C" int rlgpu_envset_config_size(void) { return (int)sizeof(rlgpu_envset_config); }
 
 extern "C" int rlgpu_envset_create(const rlgpu_envset_config* cfg, rlgpu_envset** out) {
     return rlgpu::guarded([&] {
@@ -540,9 +587,8 @@ extern "C" int rlgpu_envset_create(const rlgpu_envset_config* cfg, rlgpu_envset*
         RLGPU_REQUIRE(cfg->mesh_tris == nullptr || cfg->mesh_ntris > 0, "mesh_ntris must be > 0 with mesh_tris");
         RLGPU_REQUIRE(cfg->arith >= 0 && cfg->arith < RLGPU_NUM_ARITH,
                       "rlgpu_envset_create: unknown arithmetic mode " + std::to_string(cfg->arith) + " (RLGPU_ARITH_*)");
-        RLGPU_REQUIRE(cfg->state_setter == RLGPU_SS_KICKOFF || cfg->state_setter == RLGPU_SS_FUZZED_KICKOFF,
-                      "rlgpu_envset_create: unknown state setter " + std::to_string(cfg->state_setter) + " (RLGPU_SS_*)");
-        const rl::Plugins plug = plugins_from(cfg);
+        rl::Plugins plug = plugins_from(cfg);
+        state_setters_from(cfg, plug);
         device_init(cfg->arith);
         // arena meshes (Arena::_SetupArenaCollisionShapes): triangle table + grid index in HBM
         std::vector<float> builtin;
@@ -563,6 +609,7 @@ extern "C" int rlgpu_envset_create(const rlgpu_envset_config* cfg, rlgpu_envset*
             e->cfg.mesh_object_ntris = nullptr;
             e->cfg.rewards = nullptr;
             e->cfg.terminals = nullptr;
+            e->cfg.state_setters = nullptr;
             e->plug = plug;
             e->d_plug = e->alloc_copy(std::vector<rl::Plugins>(1, plug));
             e->mesh.cell_start = e->alloc_copy(grid.cell_start);

@@ -1,5 +1,5 @@
 // env_builders.hpp -- the RLGymCPP layer of the env kernel: GameState snapshot, terminal
-// conditions, the ExampleMain reward list, AdvancedObs and DefaultAction masks, kickoff reset.
+// conditions, the ExampleMain reward list, AdvancedObs and DefaultAction masks, the state setters' reset.
 #pragma once
 #include "env_contacts.hpp"
 
@@ -389,6 +389,99 @@ DEV void kickoff_reset(ArenaLDS* A, uint64_t seed, int arena, bool fuzz) {
         for (int k = 0; k < 8; k++) e.prev_action[p][k] = 0.f;
         e.ev_bump[p] = e.ev_bumped[p] = e.ev_demo[p] = e.ev_demoed[p] = 0;
     }
+}
+
+// RocketSim Math::RandFloat(min, max) (Math.cpp:54-57) and RLGC Math::RandVec (RG/Math.cpp:3-9: x, y, z in that
+// order) on the arena's stream
+DEV float rand_float(ArenaLDS* A, uint64_t seed, int arena, float lo, float hi) {
+    return lo + rng_uniform(A, seed, arena) * (hi - lo);
+}
+DEV v3 rand_vec(ArenaLDS* A, uint64_t seed, int arena, v3 lo, v3 hi) {
+    v3 r;
+    r.x = rand_float(A, seed, arena, lo.x, hi.x);
+    r.y = rand_float(A, seed, arena, lo.y, hi.y);
+    r.z = rand_float(A, seed, arena, lo.z, hi.z);
+    return r;
+}
+DEV v3 rand_norm_vec(ArenaLDS* A, uint64_t seed, int arena) {  // RandNormVec (RandomState.cpp:7-9)
+    return rs_norm(rand_vec(A, seed, arena, v3{-1, -1, -1}, v3{1, 1, 1}));
+}
+// Angle::ToRotMat's btMatrix3x3::setEulerYPR (btMatrix3x3.h:290-321), one sincos per angle
+DEV m3 euler_ypr(float yaw, float pitch, float roll) {
+    float ci, cj, ch, si, sj, sh;
+    rs_sincosf(roll, &si, &ci);
+    rs_sincosf(pitch, &sj, &cj);
+    rs_sincosf(yaw, &sh, &ch);
+    float cc = ci * ch, cs = ci * sh, sc = si * ch, ss = si * sh;
+    return m3{v3{cj * ch, sj * sc - cs, sj * cc + ss}, v3{cj * sh, sj * ss + cc, sj * cs - sc}, v3{-sj, cj * si, cj * ci}};
+}
+
+// RandomState::ResetArena after its ResetToRandomKickoff (RandomState.cpp:11-63), one lane.  The draws are taken
+// in the order the source text reads, left to right, cars in index order: ball position
+// 3, [randBallSpeed: direction 3, speed 1, angular velocity 3], then per car position 3, [randCarSpeed: the
+// unused randVelDir 3, direction 3, speed 1, angular direction 3], yaw / pitch / roll 3, [!carsOnGround: the
+// on-ground coin 1], boost 1.  Ball::SetState / Car::SetState (Ball.cpp:35-49, Car.cpp:23-36) of a default
+// state with those fields: isOnGround stays true whatever the height (Car.h:25).
+DEV void random_state(ArenaLDS* A, uint64_t seed, int arena, int flags) {
+    const float X = 3500.f, Y = 4000.f, Z = 1820.f, PI = 3.14159265358979323846f, HALF_PI = 1.57079632679489661923f;
+    {
+        const v3 pos = rand_vec(A, seed, arena, v3{-X, -Y, 92.75f}, v3{X, Y, Z});  // CommonValues::BALL_RADIUS
+        v3 vel = zero3(), ang = zero3();
+        if (flags & RLGPU_SS_RAND_BALL_SPEED) {
+            const v3 dir = rand_norm_vec(A, seed, arena);
+            vel = dir * rand_float(A, seed, arena, 0.f, 4000.f);
+            ang = rand_vec(A, seed, arena, v3{-4, -4, -4}, v3{4, 4, 4});
+        }
+        st3(A->s.ball.pos, pos * kUU2BT);
+        stm(A->s.ball.rot, ident3());
+        st3(A->s.ball.vel, vel * kUU2BT);
+        st3(A->s.ball.angvel, ang);
+        st3(A->s.ball_vel_impulse_cache, zero3());
+    }
+#pragma unroll 1
+    for (int ci = 0; ci < 4; ci++) {
+        v3 pos = rand_vec(A, seed, arena, v3{-X, -Y, 150.f}, v3{X, Y, Z});
+        v3 vel = zero3(), ang = zero3();
+        if (flags & RLGPU_SS_RAND_CAR_SPEED) {
+            rand_vec(A, seed, arena, v3{-1, -1, -1}, v3{1, 1, 1});  // randVelDir (:41): drawn, never used
+            const v3 dir = rand_norm_vec(A, seed, arena);
+            vel = dir * rand_float(A, seed, arena, 0.f, 2300.f);  // RLConst::CAR_MAX_SPEED
+            ang = rand_norm_vec(A, seed, arena) * 5.5f;
+        }
+        const float yaw = rand_float(A, seed, arena, -PI, PI);
+        float pitch = rand_float(A, seed, arena, -HALF_PI, HALF_PI);
+        float roll = rand_float(A, seed, arena, -PI, PI);
+        const bool on_ground = (flags & RLGPU_SS_CARS_ON_GROUND) ? true : rand_float(A, seed, arena, 0.f, 1.f) > 0.5f;
+        if (on_ground) {
+            pos.z = 17.f;
+            pitch = roll = 0.f;
+            vel.z = 0.f;
+            ang = zero3();
+        }
+        const m3 rot = euler_ypr(yaw, -pitch, -roll);
+        const float boost = rand_float(A, seed, arena, 0.f, 100.f);
+        set_car_state(A, ci, pos, rot, boost, true);
+        st3(A->s.cars[ci].body.vel, vel * kUU2BT);
+        st3(A->s.cars[ci].body.angvel, ang);
+    }
+}
+
+// The env set's one reset entry: the set's state setter (Plugins::ss) on this arena, one lane.  A CombinedState
+// takes one draw, f = RandFloat(0, totalWeight), and runs the first child with f <= cumulativeWeights[i]
+// (CombinedState.h:33-41); the child's reset follows on the same stream.  Every setter of the table starts with
+// Arena::ResetToRandomKickoff (KickoffState.h, FuzzedKickoffState.h:12, RandomState.cpp:14).  Not inlined: the
+// step kernel's register budget is the tick loop's, and the reset runs on one lane of an arena, seldom.
+__device__ __noinline__ void state_reset(ArenaLDS* A, const Plugins* pl, uint64_t seed, int arena) {
+    int pick = 0;
+    if (pl->ss_combined) {
+        const float f = rand_float(A, seed, arena, 0.f, pl->ss_total);
+        pick = pl->ns - 1;
+        for (int i = pl->ns - 1; i >= 0; i--)
+            if (f <= pl->ss_cum[i]) pick = i;
+    }
+    const int type = pl->ss[pick].type;
+    kickoff_reset(A, seed, arena, type == RLGPU_SS_FUZZED_KICKOFF);
+    if (type == RLGPU_SS_RANDOM) random_state(A, seed, arena, pl->ss[pick].flags);
 }
 
 }  // namespace rl

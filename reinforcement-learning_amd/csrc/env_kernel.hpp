@@ -88,6 +88,13 @@ struct Plugins {
     int nr, nt;
     rlgpu_reward_spec rw[RLGPU_MAX_REWARDS];
     rlgpu_terminal_spec tc[RLGPU_MAX_TERMINALS];
+    // the state setter table (rlgpu_envset_config state_setter / state_setters): a plain setter is one entry;
+    // ss_combined: CombinedState over the ns entries, ss_cum[i] = its cumulativeWeights[i] (fp32 sums in list
+    // order), ss_total = totalWeight (CombinedState.h:18-31)
+    int ns, ss_combined;
+    rlgpu_state_setter_spec ss[RLGPU_MAX_STATE_SETTERS];
+    float ss_cum[RLGPU_MAX_STATE_SETTERS];
+    float ss_total;
 };
 
 struct WheelT {

@@ -52,7 +52,6 @@ struct StepArgs {
     int arith;                 // RLGPU_ARITH_* (rlgpu_envset_config.arith): copied into Aux::arith at launch
     int arena_offset;          // global index of arena 0 (the arenas' Philox streams)
     float* reward_values;      // [players][nr] each reward's value before its weight, or null
-    int fuzz;                  // FuzzedKickoffState (rlgpu_envset_config.state_setter)
     int pen_slots;             // deferred penetration queries whose GJK state is saved (kPenSave; tests: fewer)
 };
 

@@ -195,7 +195,7 @@
         }
         sync(); P.mark(13);
         if (g.reset_mode == kResetTerminated) {
-            if (fused_reset && l == 0) kickoff_reset(A, g.seed, arena + g.arena_offset, g.fuzz != 0);
+            if (fused_reset && l == 0) state_reset(A, g.plug, g.seed, arena + g.arena_offset);
             sync(); P.mark(14);
             if (fused_reset) build_obs_rows(A, l);
             sync(); P.mark(14);
@@ -216,7 +216,7 @@
         }
         sync(); P.mark(14);
         if (do_reset && l == 0) {
-            kickoff_reset(A, g.seed, arena + g.arena_offset, g.fuzz != 0);
+            state_reset(A, g.plug, g.seed, arena + g.arena_offset);
             if (g.reset_mode == kResetSet) g.terminals[arena] = 0;
         }
         sync(); P.mark(14);

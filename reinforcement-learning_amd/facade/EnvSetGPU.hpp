@@ -56,7 +56,17 @@ struct PluginPlan {
     std::vector<int> rewardSlot;                        // per EnvCreateResult::rewards entry: device index, -1 = host
     std::vector<int> hostTerminals;                     // indices into terminalConditions that run on the host
     std::vector<std::string> hostNames;                 // host plugins' type names (the log line)
-    int32_t stateSetter = RLGPU_SS_KICKOFF;             // KickoffState / FuzzedKickoffState
+    int32_t stateSetter = RLGPU_SS_KICKOFF;             // RLGPU_SS_* of EnvCreateResult::stateSetter
+    int32_t stateSetterFlags = 0;                       // RandomState's flag bits
+    std::vector<rlgpu_state_setter_spec> stateSetters;  // CombinedState's children, in list order
+    // rlgpu_envset_config / rlgpu_learner_config state setter fields (the list stays this plan's)
+    template <class Cfg>
+    void FillStateSetter(Cfg& c) const {
+        c.state_setter = stateSetter;
+        c.state_setter_flags = stateSetterFlags;
+        c.state_setters = stateSetters.empty() ? nullptr : stateSetters.data();
+        c.n_state_setters = (int32_t)stateSetters.size();
+    }
     int NumHostRewards() const {
         int n = 0;
         for (int s : rewardSlot) n += s < 0;
@@ -171,6 +181,21 @@ inline bool RegistryTerminal(TerminalCondition* c, rlgpu_terminal_spec& s) {
     return true;
 }
 
+// the registry entry of a state setter that is not a CombinedState, or false for any other class
+inline bool RegistrySetter(StateSetter* x, rlgpu_state_setter_spec& s) {
+    const std::type_info& t = typeid(*x);
+    s.flags = 0;
+    if (Is<KickoffState>(x, t)) s.type = RLGPU_SS_KICKOFF;
+    else if (Is<FuzzedKickoffState>(x, t)) s.type = RLGPU_SS_FUZZED_KICKOFF;
+    else if (Is<RandomState>(x, t)) {
+        auto* r = static_cast<RandomState*>(x);
+        s.type = RLGPU_SS_RANDOM;
+        s.flags = (r->randBallSpeed ? RLGPU_SS_RAND_BALL_SPEED : 0) | (r->randCarSpeed ? RLGPU_SS_RAND_CAR_SPEED : 0) |
+                  (r->carsOnGround ? RLGPU_SS_CARS_ON_GROUND : 0);
+    } else return false;
+    return true;
+}
+
 inline bool SameSpec(const rlgpu_reward_spec& a, const rlgpu_reward_spec& b) {
     return a.type == b.type && a.weight == b.weight && a.params[0] == b.params[0] && a.params[1] == b.params[1] &&
            a.params[2] == b.params[2] && a.zero_sum == b.zero_sum && a.zero_sum_team_spirit == b.zero_sum_team_spirit &&
@@ -179,7 +204,7 @@ inline bool SameSpec(const rlgpu_reward_spec& a, const rlgpu_reward_spec& b) {
 }  // namespace detail
 
 // One arena's EnvCreateResult.  Throws std::invalid_argument for what neither side can run: a builder other
-// than AdvancedObs / DefaultAction / KickoffState / FuzzedKickoffState (the kernels' own), a registry class with a field the
+// than AdvancedObs / DefaultAction / the device state setters (the kernels' own), a registry class with a field the
 // registry cannot hold, or lists longer than RLGPU_MAX_REWARDS / RLGPU_MAX_TERMINALS.
 inline PluginPlan TranslatePlugins(const EnvCreateResult& r) {
     if (r.obsBuilder && typeid(*r.obsBuilder) != typeid(AdvancedObs))
@@ -188,11 +213,34 @@ inline PluginPlan TranslatePlugins(const EnvCreateResult& r) {
     if (r.actionParser && typeid(*r.actionParser) != typeid(DefaultAction))
         throw std::invalid_argument(std::string("EnvCreateResult: action parser ") + typeid(*r.actionParser).name() +
                                     " (the kernels parse DefaultAction)");
-    if (r.stateSetter && typeid(*r.stateSetter) != typeid(KickoffState) && typeid(*r.stateSetter) != typeid(FuzzedKickoffState))
-        throw std::invalid_argument(std::string("EnvCreateResult: state setter ") + typeid(*r.stateSetter).name() +
-                                    " (the kernels reset to KickoffState or FuzzedKickoffState)");
     PluginPlan p;
-    if (r.stateSetter && typeid(*r.stateSetter) == typeid(FuzzedKickoffState)) p.stateSetter = RLGPU_SS_FUZZED_KICKOFF;
+    if (r.stateSetter) {
+        const char* const kDevice = " (the kernels reset to KickoffState, FuzzedKickoffState, RandomState or a CombinedState of those)";
+        rlgpu_state_setter_spec s{};
+        if (typeid(*r.stateSetter) == typeid(CombinedState)) {
+            auto* c = static_cast<CombinedState*>(r.stateSetter);
+            if (c->Setters().size() > RLGPU_MAX_STATE_SETTERS)
+                throw std::invalid_argument("EnvCreateResult: CombinedState of " + std::to_string(c->Setters().size()) +
+                                            " setters, more than RLGPU_MAX_STATE_SETTERS");
+            p.stateSetter = RLGPU_SS_COMBINED;
+            for (size_t i = 0; i < c->Setters().size(); i++) {
+                StateSetter* child = c->Setters()[i];
+                if (typeid(*child) == typeid(CombinedState))
+                    throw std::invalid_argument("EnvCreateResult: CombinedState setter " + std::to_string(i) +
+                                                " is a CombinedState: a nested CombinedState has no device code");
+                if (!detail::RegistrySetter(child, s))
+                    throw std::invalid_argument("EnvCreateResult: CombinedState setter " + std::to_string(i) + " " +
+                                                typeid(*child).name() + kDevice);
+                s.weight = c->Weights()[i];
+                p.stateSetters.push_back(s);
+            }
+        } else if (detail::RegistrySetter(r.stateSetter, s)) {
+            p.stateSetter = s.type;
+            p.stateSetterFlags = s.flags;
+        } else {
+            throw std::invalid_argument(std::string("EnvCreateResult: state setter ") + typeid(*r.stateSetter).name() + kDevice);
+        }
+    }
     for (const WeightedReward& w : r.rewards) {
         if (!w.reward) throw std::invalid_argument("EnvCreateResult: null reward");
         rlgpu_reward_spec s{};
@@ -226,6 +274,10 @@ inline PluginPlan TranslatePlugins(const EnvCreateResult& r) {
 inline void RequireSamePlan(const PluginPlan& a, const PluginPlan& b, int index) {
     bool same = a.rewardSlot == b.rewardSlot && a.hostTerminals == b.hostTerminals && a.stateSetter == b.stateSetter &&
                 a.deviceRewards.size() == b.deviceRewards.size() && a.deviceTerminals.size() == b.deviceTerminals.size();
+    same = same && a.stateSetterFlags == b.stateSetterFlags && a.stateSetters.size() == b.stateSetters.size();
+    for (size_t i = 0; same && i < a.stateSetters.size(); i++)
+        same = a.stateSetters[i].type == b.stateSetters[i].type && a.stateSetters[i].weight == b.stateSetters[i].weight &&
+               a.stateSetters[i].flags == b.stateSetters[i].flags;
     for (size_t i = 0; same && i < a.deviceRewards.size(); i++) same = detail::SameSpec(a.deviceRewards[i], b.deviceRewards[i]);
     for (size_t i = 0; same && i < a.deviceTerminals.size(); i++)
         same = a.deviceTerminals[i].type == b.deviceTerminals[i].type && a.deviceTerminals[i].param == b.deviceTerminals[i].param;
@@ -408,7 +460,7 @@ class EnvSetGPU {
         if (!cfg.terminals) cfg.terminals = &kNoTerminals;
         cfg.arith = o.arith;
         cfg.arena_offset = o.arenaOffset;
-        cfg.state_setter = plan.stateSetter;
+        plan.FillStateSetter(cfg);
         RlgpuCheck(rlgpu_envset_create(&cfg, &h), "EnvSet");
         RlgpuCheck(rlgpu_envset_buffers_get(h, &state), "EnvSet buffers");
         InitHost();

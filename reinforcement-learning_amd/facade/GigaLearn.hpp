@@ -821,8 +821,7 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
         c.mesh_objects = (int32_t)meshObjects_.size();
         c.mesh_object_ntris = meshObjects_.data();
     }
-    if (plan.stateSetter != RLGPU_SS_KICKOFF)
-        throw std::invalid_argument("Learner: the training env set resets to KickoffState (FuzzedKickoffState is the skill tracker's)");
+    plan.FillStateSetter(c);
     RLGC::RlgpuCheck(rlgpu_learner_create(&c, options.world > 1 ? options.collective : nullptr, stream_, &h_), "Learner");
     rlgpu_envset* env = nullptr;
     RLGC::RlgpuCheck(rlgpu_learner_handles(h_, &env, &ppo_), "Learner handles");

@@ -424,7 +424,7 @@ class AdvancedObs : public ObsBuilder {};
 class DefaultObs : public ObsBuilder {};        // RG/ObsBuilders/DefaultObs.h (declared; the kernels build AdvancedObs)
 class DefaultAction : public ActionParser {};
 class KickoffState : public StateSetter {};
-class RandomState : public StateSetter {        // RG/StateSetters/RandomState.h (declared; not a device state setter)
+class RandomState : public StateSetter {        // RG/StateSetters/RandomState.h (RLGPU_SS_RANDOM)
   public:
     bool randBallSpeed = true, randCarSpeed = true, carsOnGround = true;
     RandomState(bool randBallSpeed = true, bool randCarSpeed = true, bool carsOnGround = true)
@@ -433,6 +433,30 @@ class RandomState : public StateSetter {        // RG/StateSetters/RandomState.h
 class FuzzedKickoffState : public StateSetter {  // RG/StateSetters/FuzzedKickoffState.h
   public:
     constexpr static float FUZZ_POS_RANGE = 0.1f;
+};
+// RG/StateSetters/CombinedState.h (RLGPU_SS_COMBINED): the reference's constructor; where it closes the program
+// on an empty list or a negative / non-finite weight, this one throws.  The device sums the cumulative weights
+// itself from Weights(), in fp32 in list order as the reference does.
+class CombinedState : public StateSetter {
+  public:
+    CombinedState(const std::vector<std::pair<StateSetter*, float>>& setters) {
+        if (setters.empty()) throw std::invalid_argument("CombinedState: the setter list is empty");
+        for (size_t i = 0; i < setters.size(); i++) {
+            const float w = setters[i].second;
+            if (!setters[i].first) throw std::invalid_argument("CombinedState: state setter " + std::to_string(i) + " is null");
+            if (w < 0 || std::isnan(w) || std::isinf(w))
+                throw std::invalid_argument(std::string("CombinedState: State setter \"") + typeid(*setters[i].first).name() +
+                                            "\" has a negative or invalid weight of " + std::to_string(w));
+            this->setters.push_back(setters[i].first);
+            weights.push_back(w);
+        }
+    }
+    const std::vector<StateSetter*>& Setters() const { return setters; }
+    const std::vector<float>& Weights() const { return weights; }
+
+  private:
+    std::vector<StateSetter*> setters;
+    std::vector<float> weights;
 };
 
 struct EnvCreateResult {  // RG/EnvSet/EnvSet.h:14-24

@@ -22,7 +22,7 @@
 //   rlgpu_train [--iterations N] [--arenas A] [--rollout T] [--trajectories] [--f32-gemm] [--c2-model] [--seed S]
 //               [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] [--self-play] [--fp32-inference]
 //               [--policy-temperature X] [--mask-entropy] [--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm]
-//               [--guiding-policy DIR [--guiding-strength X]]
+//               [--guiding-policy DIR [--guiding-strength X]] [--state-setter kickoff|random|combined:K:R]
 //               [--rank r --world N --rccl-id FILE [--rccl-nonce STR]]
 #include <execinfo.h>
 #include <signal.h>
@@ -41,6 +41,16 @@
 
 using namespace GGL;
 using namespace RLGC;
+
+static int gStateSetter = 0;  // --state-setter: 0 kickoff, 1 random, 2 combined
+static float gKickoffWeight = 1.f, gRandomWeight = 1.f;
+
+static void ParseStateSetter(const char* v) {
+    if (!std::strcmp(v, "kickoff")) gStateSetter = 0;
+    else if (!std::strcmp(v, "random")) gStateSetter = 1;
+    else if (std::sscanf(v, "combined:%f:%f", &gKickoffWeight, &gRandomWeight) == 2) gStateSetter = 2;
+    else throw std::invalid_argument(std::string("--state-setter ") + v + " (kickoff, random or combined:K:R)");
+}
 
 // src/ExampleMain.cpp:128-226 with registry classes only
 static EnvCreateResult EnvCreateFunc(int) {
@@ -69,7 +79,12 @@ static EnvCreateResult EnvCreateFunc(int) {
     }
     r.actionParser = new DefaultAction();
     r.obsBuilder = new AdvancedObs();
-    r.stateSetter = new KickoffState();
+    // --state-setter: kickoff (ExampleMain's), random = RandomState(true, true, false), or combined:K:R =
+    // CombinedState{{KickoffState, K}, {RandomState(true, true, false), R}}
+    if (gStateSetter == 1) r.stateSetter = new RandomState(true, true, false);
+    else if (gStateSetter == 2)
+        r.stateSetter = new CombinedState({{new KickoffState(), gKickoffWeight}, {new RandomState(true, true, false), gRandomWeight}});
+    else r.stateSetter = new KickoffState();
     return r;
 }
 
@@ -187,6 +202,7 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(argv[i], "--fp32-inference")) cfg.ppo.useHalfPrecision = false;
             else if (!std::strcmp(argv[i], "--policy-temperature")) cfg.ppo.policyTemperature = std::strtof(next(), nullptr);
             else if (!std::strcmp(argv[i], "--mask-entropy")) cfg.ppo.maskEntropy = true;
+            else if (!std::strcmp(argv[i], "--state-setter")) ParseStateSetter(next());
             else if (!std::strcmp(argv[i], "--standardize-obs")) cfg.standardizeObs = true;  // LearnerConfig::standardizeObs
             else if (!std::strcmp(argv[i], "--min-obs-std")) cfg.minObsSTD = std::strtof(next(), nullptr);
             else if (!std::strcmp(argv[i], "--guiding-policy")) {  // PPOLearnerConfig::useGuidingPolicy / guidingPolicyPath
@@ -230,7 +246,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "%s\nusage: %s [--iterations N] [--arenas A] [--rollout T] [--trajectories] [--f32-gemm] "
                                  "[--c2-model] [--seed S] [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] "
                                  "[--self-play] [--fp32-inference] [--policy-temperature X] [--mask-entropy] "
-                                 "[--standardize-obs [--min-obs-std X]] "
+                                 "[--standardize-obs [--min-obs-std X]] [--state-setter kickoff|random|combined:K:R] "
                                  "[--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm] [--guiding-policy DIR "
                                  "[--guiding-strength X]] [--transfer-learn DIR [--old-policy-layers a,b,..] [--old-shared-layers a,b,..] "
                                  "[--tl-lr X] [--tl-epochs N] [--tl-kl] [--tl-loss-scale X] [--tl-loss-exponent X] [--tl-map-acts]] "

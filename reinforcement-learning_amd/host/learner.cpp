@@ -220,6 +220,10 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     ec.terminals = cfg.terminals;
     ec.n_terminals = cfg.n_terminals;
     ec.arith = cfg.arith;
+    ec.state_setter = cfg.state_setter;
+    ec.state_setter_flags = cfg.state_setter_flags;
+    ec.state_setters = cfg.state_setters;
+    ec.n_state_setters = cfg.n_state_setters;
     env_ = std::make_unique<RLGC::EnvSetGPU>(ec, s_);
     // ExampleMain registers its StepCallback (ExampleMain.cpp:233-283, 592): restated on the device
     RlgpuCheck(rlgpu_envset_enable_step_metrics(env_->handle(), 1), "step metrics");

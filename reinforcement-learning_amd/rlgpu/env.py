@@ -29,12 +29,77 @@ class _Config(ctypes.Structure):
                 ("mesh_tris", ctypes.c_void_p), ("mesh_ntris", ctypes.c_int32), ("mesh_objects", ctypes.c_int32),
                 ("mesh_object_ntris", ctypes.c_void_p), ("rewards", ctypes.c_void_p), ("n_rewards", ctypes.c_int32),
                 ("terminals", ctypes.c_void_p), ("n_terminals", ctypes.c_int32), ("arith", ctypes.c_int32),
-                ("arena_offset", ctypes.c_int32), ("state_setter", ctypes.c_int32)]
+                ("arena_offset", ctypes.c_int32), ("state_setter", ctypes.c_int32),
+                ("state_setter_flags", ctypes.c_int32), ("state_setters", ctypes.c_void_p),
+                ("n_state_setters", ctypes.c_int32)]
 
 # the reference build whose Bullet arithmetic the arenas follow (include/rlgpu_arith.h)
 ARITH_MSVC_X64, ARITH_GCC_X64, ARITH_SCALAR = 0, 1, 2
 # EnvCreateResult::stateSetter (include/rlgpu_env.h RLGPU_SS_*)
 KICKOFF_STATE, FUZZED_KICKOFF_STATE = 0, 1
+_SS_RANDOM, _SS_COMBINED, MAX_STATE_SETTERS = 2, 3, 8
+STATE_SETTER_SPEC = np.dtype([("type", np.int32), ("weight", np.float32), ("flags", np.int32)])
+
+
+class RandomState:
+    """RLGC::RandomState(randBallSpeed, randCarSpeed, carsOnGround) (RG/StateSetters/RandomState.h): the
+    kickoff, then the ball and the four cars placed at random (RLGPU_SS_RANDOM)."""
+
+    def __init__(self, rand_ball_speed=True, rand_car_speed=True, cars_on_ground=True):
+        self.rand_ball_speed, self.rand_car_speed = bool(rand_ball_speed), bool(rand_car_speed)
+        self.cars_on_ground = bool(cars_on_ground)
+
+    @property
+    def flags(self):
+        return int(self.rand_ball_speed) | int(self.rand_car_speed) << 1 | int(self.cars_on_ground) << 2
+
+    def __repr__(self):
+        return f"RandomState({self.rand_ball_speed}, {self.rand_car_speed}, {self.cars_on_ground})"
+
+
+class CombinedState:
+    """RLGC::CombinedState({{setter, weight}, ...}) (RG/StateSetters/CombinedState.h): every reset runs one child,
+    chosen at random by weight.  Children: KICKOFF_STATE, FUZZED_KICKOFF_STATE or a RandomState."""
+
+    def __init__(self, setters):
+        self.setters = [(s, float(w)) for s, w in setters]
+        state_setter_spec(self)  # reject a bad list where it is written
+
+    def __repr__(self):
+        return f"CombinedState({self.setters})"
+
+
+def _plain_setter(s, who):
+    """(type, flags) of a setter that is not a CombinedState."""
+    if isinstance(s, RandomState):
+        return _SS_RANDOM, s.flags
+    if isinstance(s, (int, np.integer)) and not isinstance(s, bool) and int(s) in (KICKOFF_STATE, FUZZED_KICKOFF_STATE):
+        return int(s), 0
+    raise ValueError(f"{who}: {s!r} is no state setter (KICKOFF_STATE, FUZZED_KICKOFF_STATE, RandomState(...) or "
+                     "CombinedState([...]))")
+
+
+def state_setter_spec(setter):
+    """(state_setter, state_setter_flags, children) of rlgpu_envset_config for a setter: children is a
+    STATE_SETTER_SPEC array for a CombinedState, else None.  Raises ValueError naming the entry at fault."""
+    if not isinstance(setter, CombinedState):
+        t, f = _plain_setter(setter, "state_setter")
+        return t, f, None
+    if not setter.setters:
+        raise ValueError("CombinedState: the setter list is empty")
+    if len(setter.setters) > MAX_STATE_SETTERS:
+        raise ValueError(f"CombinedState: {len(setter.setters)} setters, at most {MAX_STATE_SETTERS} "
+                         "(RLGPU_MAX_STATE_SETTERS)")
+    out = np.zeros(len(setter.setters), STATE_SETTER_SPEC)
+    for i, (s, w) in enumerate(setter.setters):
+        who = f"CombinedState: setter {i}"
+        if isinstance(s, CombinedState):
+            raise ValueError(f"{who} is a CombinedState: a nested CombinedState has no device code")
+        t, f = _plain_setter(s, who)
+        if not np.isfinite(w) or w < 0:
+            raise ValueError(f"{who} ({s!r}) has a negative or invalid weight of {w}")
+        out[i] = (t, w, f)
+    return _SS_COMBINED, 0, out
 
 
 class StepOutputs(ctypes.Structure):
@@ -66,6 +131,9 @@ def _bind():
     if _bound:
         return _lib.lib()
     L = _lib.lib()
+    if L.rlgpu_envset_config_size() != ctypes.sizeof(_Config):
+        raise _lib.RLGPUError(f"rlgpu_envset_config is {L.rlgpu_envset_config_size()} bytes in the library, "
+                              f"{ctypes.sizeof(_Config)} in rlgpu/env.py: the binding is out of date")
     vp, i32 = ctypes.c_void_p, ctypes.c_int32
     L.rlgpu_envset_create.argtypes = [ctypes.POINTER(_Config), ctypes.POINTER(vp)]
     L.rlgpu_envset_destroy.argtypes = [vp]
@@ -98,6 +166,11 @@ def arena_state_size():
     return _lib.lib().rlgpu_arena_state_size()
 
 
+def config_size():
+    """sizeof(rlgpu_envset_config) in the library, for checking the _Config mirror."""
+    return _lib.lib().rlgpu_envset_config_size()
+
+
 def gamestate_size():
     return _lib.lib().rlgpu_gamestate_size()
 
@@ -127,7 +200,8 @@ class EnvSet:
         terminal(...) specs (or structured arrays), None = ExampleMain's.  arith: the reference build
         whose Bullet arithmetic the step follows (ARITH_MSVC_X64 = build.ps1's, ARITH_GCC_X64, ARITH_SCALAR).
         arena_offset: global index of arena 0 for the arenas' random streams (a rank's first arena).
-        state_setter: KICKOFF_STATE, or FUZZED_KICKOFF_STATE (the skill tracker's, rlgpu.skill)."""
+        state_setter: KICKOFF_STATE, FUZZED_KICKOFF_STATE (the skill tracker's, rlgpu.skill), a RandomState or a
+        CombinedState of those."""
         import torch
         if not torch.cuda.is_available():
             raise _lib.RLGPUError("EnvSet needs an MI355X: the product path has no CPU fallback")
@@ -137,7 +211,9 @@ class EnvSet:
         cfg = _Config(num_arenas, tick_skip, action_delay, seed, int(save_rewards), max_episode_steps)
         cfg.arith = int(arith)
         cfg.arena_offset = int(arena_offset)
-        cfg.state_setter = int(state_setter)
+        cfg.state_setter, cfg.state_setter_flags, self._ss = state_setter_spec(state_setter)
+        if self._ss is not None:
+            cfg.state_setters, cfg.n_state_setters = self._ss.ctypes.data, self._ss.size
         self.arith = int(arith)
         if mesh is not None:
             cfg.mesh_tris = mesh.tris.ctypes.data

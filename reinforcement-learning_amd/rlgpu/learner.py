@@ -296,6 +296,8 @@ class LearnerConfig:
         self.arith = 0                     # the reference build's Bullet arithmetic (rlgpu.arith; 0 = MSVC x64)
         self.rewards = None                # EnvCreateFn reward list (rlgpu.plugins.reward specs); None = ExampleMain's
         self.terminals = None              # terminal conditions (rlgpu.plugins.terminal specs); None = ExampleMain's
+        self.state_setter = 0              # EnvCreateResult::stateSetter of the training arenas: rlgpu.env KICKOFF_STATE (0),
+                                           # FUZZED_KICKOFF_STATE, RandomState(...) or CombinedState([...])
         self.mesh = None                   # arena collision meshes (rlgpu.mesh.ArenaMesh); None = the built-in synthetic arena
         self.max_episode_duration = 300.0  # seconds (ExampleMain)
         self.deterministic = False
@@ -356,6 +358,8 @@ class _CConfig(ctypes.Structure):
                 ("shared_layers", ctypes.c_int32 * MAX_LAYERS), ("n_shared_layers", ctypes.c_int32),
                 ("rewards", ctypes.c_void_p), ("n_rewards", ctypes.c_int32),
                 ("terminals", ctypes.c_void_p), ("n_terminals", ctypes.c_int32),
+                ("state_setter", ctypes.c_int32), ("state_setter_flags", ctypes.c_int32),
+                ("state_setters", ctypes.c_void_p), ("n_state_setters", ctypes.c_int32),
                 ("experience_mode", ctypes.c_int32), ("ts_per_itr", ctypes.c_int64),
                 ("experience_capacity", ctypes.c_int32), ("arith", ctypes.c_int32),
                 ("activation", ctypes.c_int32), ("no_layer_norm", ctypes.c_int32), ("optimizer", ctypes.c_int32),
@@ -405,6 +409,9 @@ def _bind():
     L.rlgpu_learner_create.argtypes = [ctypes.POINTER(_CConfig), vp, vp, ctypes.POINTER(vp)]
     L.rlgpu_learner_destroy.argtypes = [vp]
     L.rlgpu_learner_config_size.restype = ctypes.c_int32
+    if L.rlgpu_learner_config_size() != ctypes.sizeof(_CConfig):
+        raise _lib.RLGPUError(f"rlgpu_learner_config is {L.rlgpu_learner_config_size()} bytes in the library, "
+                              f"{ctypes.sizeof(_CConfig)} in rlgpu/learner.py: the binding is out of date")
     L.rlgpu_learner_handles.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.rlgpu_learner_rollout.argtypes = [vp, ctypes.POINTER(_CRollout)]
     L.rlgpu_learner_batch.argtypes = [vp, ctypes.POINTER(_CBatch)]
@@ -523,6 +530,10 @@ class Learner:
             tc = plugins.terminals_array(cfg.terminals)
             self._tc = np.ascontiguousarray(tc if tc.size else np.zeros(1, plugins.TERMINAL_SPEC))
             c.terminals, c.n_terminals = self._tc.ctypes.data, tc.size
+        from .env import state_setter_spec
+        c.state_setter, c.state_setter_flags, self._ss = state_setter_spec(cfg.state_setter)
+        if self._ss is not None:
+            c.state_setters, c.n_state_setters = self._ss.ctypes.data, self._ss.size
         if cfg.mesh is not None:  # copied by the env set at create
             self._mesh = cfg.mesh
             c.mesh_tris, c.mesh_ntris = cfg.mesh.tris.ctypes.data, cfg.mesh.num_tris
