@@ -10,7 +10,7 @@
  *     uniform is a Philox4x32-10 draw, key = seed, counter = (global row, step) -- the reference's
  *     thread-local mt19937 is unseeded, so the draw is injected and both sides use this one;
  * with the softmax in the GPU kernel's operation order (reinforcement-learning_amd/csrc/ppo_kernels.hpp
- * sample_rows: lane l of a 64-lane wave holds actions 2l and 2l+1; max and sum are xor butterflies,
+ * sample_rows_looped: lane l of a 64-lane wave holds actions 2l and 2l+1; max and sum are xor butterflies,
  * i.e. pairwise trees over the lanes; libtorch's softmax order is unpinned), with exp / log from
  * include/rlgpu_detmath.h.  Built with -ffp-contract=off.
  * Logits are the policy's 16-bit (bf16 or fp16) outputs, as the sampler reads them.

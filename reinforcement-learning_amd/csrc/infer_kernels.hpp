@@ -9,7 +9,7 @@
 // unfused path's, operation for operation: the same v_mfma_f32_32x32x16 instruction over the same K
 // order (16-deep steps from k = 0), the same 16-bit rounding of (acc + bias), the same wave-per-row
 // LayerNorm reduction (hcol column ownership, wave_sum order) and the same per-row sampler
-// (ppo::sample_rows), so both paths produce the same bits.
+// (ppo::sample_rows_looped), so both paths produce the same bits.
 //
 // Layout.  LDS Xs[64][520] 16-bit holds the current layer input (the workgroup's rows, k contiguous,
 // zero past the layer's width up to the next multiple of 16).  The weights come from a fragment-major
@@ -42,7 +42,7 @@ constexpr int IT = 64 * IW;        // threads
 constexpr int IRW = IR / IW;       // rows per wave in the row-parallel phases
 constexpr int IMAX = 512;          // widest layer input / hidden layer
 constexpr int IPITCH = IMAX + 8;   // LDS row pitch (16-bit): 1040 B, rows 4 banks apart
-// the sampler's probs (ppo::sample_rows) in each row of Xs past its <= kMaxA 16-bit logits
+// the sampler's probs (ppo::sample_rows_looped) in each row of Xs past its <= kMaxA 16-bit logits
 constexpr int kSampleProbs = 128;
 static_assert(ppo::kMaxA <= kSampleProbs && kSampleProbs * 2 + ppo::kMaxA * 4 <= IPITCH * 2, "probs fit a row of Xs");
 constexpr int IOUT = 128;          // widest output layer (4 x 32-column tiles)

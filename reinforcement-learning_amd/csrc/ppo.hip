@@ -1462,17 +1462,14 @@ extern "C" int rlgpu_ppo_minibatch_guided(rlgpu_ppo* h, const float* d_obs, cons
         // the kernel that knows policy_temperature / mask_entropy only when one of them is set: the defaults run the
         // kernel without them (see policy_loss on why x / 1 alone does not keep the bits)
         const bool pl_opt = h->cfg.policy_temperature != 1.f || h->cfg.mask_entropy != 0;
-        if (d_guide_logits)  // the guided instance (always with the options' semantics); d loss / d c = strength / (n A) sign
-            hipLaunchKernelGGL(ppo::policy_loss_guided_any(A, f16(h)), dim3(pl_blocks), dim3(256), 0, s, pm.y, d_masks, d_actions,
-                               d_old_logp, d_adv, d_index, start, n, A, d_adv_stats, bsr, h->cfg.clip_range, h->cfg.entropy_scale,
-                               1.f / std::log((float)A), h->cfg.policy_temperature, h->cfg.mask_entropy, pm.dy, dout_ld(A),
-                               d_metrics, pm.lpart, amax_slot(pm, kAmaxOut), d_guide_logits,
-                               guiding_strength / ((float)n * (float)A));
-        else
-            hipLaunchKernelGGL(ppo::policy_loss_any(A, pl_opt), dim3(pl_blocks), dim3(256), 0, s, pm.y, d_masks, d_actions, d_old_logp,
-                               d_adv, d_index, start, n, A, d_adv_stats, bsr, h->cfg.clip_range, h->cfg.entropy_scale,
-                               1.f / std::log((float)A), h->cfg.policy_temperature, h->cfg.mask_entropy, pm.dy, dout_ld(A),
-                               d_metrics, pm.lpart, amax_slot(pm, kAmaxOut));
+        // a guide takes the guided instance of its logit format (always with the options' semantics);
+        // d loss / d c = strength / (n A) sign
+        const int guide = d_guide_logits ? (f16(h) ? 2 : 1) : 0;
+        hipLaunchKernelGGL(ppo::policy_loss_any(A, pl_opt, guide), dim3(pl_blocks), dim3(256), 0, s, pm.y, d_masks, d_actions,
+                           d_old_logp, d_adv, d_index, start, n, A, d_adv_stats, bsr, h->cfg.clip_range, h->cfg.entropy_scale,
+                           1.f / std::log((float)A), h->cfg.policy_temperature, h->cfg.mask_entropy, pm.dy, dout_ld(A),
+                           d_metrics, pm.lpart, amax_slot(pm, kAmaxOut), d_guide_logits,
+                           d_guide_logits ? guiding_strength / ((float)n * (float)A) : 0.f);
         RLGPU_CHECK_HIP(hipGetLastError());
         backward(h, 0, xin, n, pm.dy, s, pm.lpart, pl_blocks);
         RLGPU_CHECK_HIP(hipStreamWaitEvent(s, h->ev_join, 0));

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/rlgpu_detmath.h"
 #include "mlp_kernels.hpp"
 
@@ -44,16 +46,7 @@ __device__ __forceinline__ uint32_t philox(uint64_t key, uint32_t c0, uint32_t c
     return x0;
 }
 
-// masked softmax of one row held 2 per lane (actions 2l, 2l+1); returns probs (unclamped)
-__device__ __forceinline__ void masked_softmax(float z0, float z1, bool v0, bool v1, float& p0, float& p1) {
-    float m = wave_max(fmaxf(v0 ? z0 : -INFINITY, v1 ? z1 : -INFINITY));
-    float e0 = v0 ? __expf(z0 - m) : 0.f, e1 = v1 ? __expf(z1 - m) : 0.f;
-    float s = wave_sum(e0 + e1);
-    p0 = e0 / s;
-    p1 = e1 / s;
-}
-
-// InferActions: logits bf16 [n, A] -> action (int32), log prob (PPOLearner.cpp:78-184).  The probs are the
+// InferActions: logits [n, A] -> action (int32), log prob (PPOLearner.cpp:78-184).  The probs are the
 // softmax of logit / temp + (-1e10) * !mask (temp = policyTemperature, wave-uniform; an IEEE fp32 division of
 // the fp32-converted logit, the mask term added after it, :97-102; skipped by a uniform branch at temp = 1, where
 // x / 1 = x) clamped to [1e-11, 1]; deterministic: argmax (lowest index on ties); otherwise the
@@ -65,170 +58,51 @@ __device__ __forceinline__ void masked_softmax(float z0, float z1, bool v0, bool
 // Bit-exact against the CPU oracle (oracle/sampler_ref.c): IEEE + - * / only, exp / log by the shared
 // rs_expf / rs_logf (include/rlgpu_detmath.h), no FMA contraction, max / sum by xor butterflies (= pairwise
 // trees), and the running sum sequential: one lane per row walks the row's probs staged in LDS.
-// row_sel (optional): only rows with (row_sel[row] != 0) == sel are written (mixed-policy inference).
-// RG rows, one wave, interleaved (each cross-lane step issues for all RG rows before the next, so
-// one wave hides the shuffle latency of RG independent rows): lg[g] = row g's A logits (global or
-// LDS), mk[g] its masks, pr[g] A floats of LDS scratch for its probs; writes act[row[g]], logp[row[g]]
-// where ok[g].  sample_actions runs it with RG = 1; the fused inference kernel (infer_kernels.hpp) runs
-// sample_rows_looped (below) over 8 rows -- the per-row arithmetic is the same, so both draw the same actions
-// from the same logits.
+// One text, sample_rows_looped (below), serves every caller -- sample_actions with one row per wave, the fused
+// inference kernel with 8, the one-wave kernel and the collection loop with 16 (infer_kernels.hpp) -- so all
+// draw the same actions from the same logits.
+
 // a logit as the sampler reads it: 16-bit storage (bf16 / fp16), or fp32 (useHalfPrecision = false)
 template <bool F16>
 __device__ __forceinline__ float logit_f(uint16_t u) { return mlp::h2f<F16>(u); }
 template <bool F16>
 __device__ __forceinline__ float logit_f(float x) { return x; }
 
-template <int RG, bool F16, typename LT = uint16_t>
-__device__ __forceinline__ void sample_rows(const LT* const (&lg)[RG], const uint8_t* const (&mk)[RG],
-                                            float* const (&pr)[RG], int A, float temp, int deterministic,
-                                            uint64_t seed, uint64_t step, int64_t row0, const int (&row)[RG],
-                                            const bool (&ok)[RG], int lane, int32_t* act, float* logp) {
-#pragma clang fp contract(off)
-    const int a0 = 2 * lane, a1 = 2 * lane + 1;
-    const bool in0 = a0 < A, in1 = a1 < A;
-    float z0[RG], z1[RG], m[RG], s[RG], p0[RG], p1[RG];
-    int pick[RG];
-    const int c0 = min(a0, A - 1), c1 = min(a1, A - 1);  // loads stay unconditional (no branches between them)
-#pragma unroll
-    for (int g = 0; g < RG; g++) {
-        float l0 = logit_f<F16>(lg[g][c0]), l1 = logit_f<F16>(lg[g][c1]);
-        const uint8_t m0 = mk[g][c0], m1 = mk[g][c1];
-        if (temp != 1.f) {  // wave-uniform; x / 1 = x exactly, the branch only spares T = 1 the division's time
-            l0 = l0 / temp;
-            l1 = l1 / temp;
-        }
-        z0[g] = in0 ? l0 + (m0 ? 0.f : kDisabledLogit) : 0.f;
-        z1[g] = in1 ? l1 + (m1 ? 0.f : kDisabledLogit) : 0.f;
-        // softmax over all A columns (masked ones carry -1e10, exactly as the reference)
-        m[g] = fmaxf(in0 ? z0[g] : -INFINITY, in1 ? z1[g] : -INFINITY);
-    }
-#pragma unroll
-    for (int g = 0; g < RG; g++) m[g] = mlp::wave_max_x(m[g]);
-#pragma unroll
-    for (int g = 0; g < RG; g++) {
-        z0[g] = in0 ? rs_expf(z0[g] - m[g]) : 0.f;  // e0, e1
-        z1[g] = in1 ? rs_expf(z1[g] - m[g]) : 0.f;
-        s[g] = z0[g] + z1[g];
-    }
-#pragma unroll
-    for (int g = 0; g < RG; g++) s[g] = mlp::wave_sum_x(s[g]);
-#pragma unroll
-    for (int g = 0; g < RG; g++) {
-        p0[g] = in0 ? fminf(fmaxf(z0[g] / s[g], kMinProb), 1.f) : 0.f;
-        p1[g] = in1 ? fminf(fmaxf(z1[g] / s[g], kMinProb), 1.f) : 0.f;
-    }
-    if (deterministic) {
-        float best[RG];
-        int bi[RG];
-#pragma unroll
-        for (int g = 0; g < RG; g++) {
-            best[g] = fmaxf(p0[g], p1[g]);
-            bi[g] = p0[g] >= p1[g] ? a0 : a1;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-            for (int g = 0; g < RG; g++) {
-                float ob = __shfl_xor(best[g], o, 64);
-                int oi = __shfl_xor(bi[g], o, 64);
-                const bool take = ob > best[g] || (ob == best[g] && oi < bi[g]);
-                best[g] = take ? ob : best[g];
-                bi[g] = take ? oi : bi[g];
-            }
-#pragma unroll
-        for (int g = 0; g < RG; g++) pick[g] = bi[g];
-    } else {
-        // the probs into LDS (lane l holds actions 2l, 2l + 1), then lane g < RG walks row g
-#pragma unroll
-        for (int g = 0; g < RG; g++) {
-            if (in0) pr[g][a0] = p0[g];
-            if (in1) pr[g][a1] = p1[g];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        int mine = A - 1;  // picked = cols - 1 when no running sum reaches r
-        if (lane < RG) {
-            const float* p = pr[0];
-            int rw = row[0];
-#pragma unroll
-            for (int g = 1; g < RG; g++)
-                if (lane == g) {
-                    p = pr[g];
-                    rw = row[g];
-                }
-            const float r = (float)(philox(sample_key(seed, step), (uint32_t)(row0 + rw), (uint32_t)step) >> 8) *
-                            (1.f / 16777216.f);
-            // the sequential running sum, 8 probs' LDS loads issued ahead of their adds (the loads do not depend
-            // on the sum; one LDS round trip per 8 columns instead of per column)
-            float running = 0.f;
-            bool found = false;
-            int j = 0;
-            for (; j + 8 <= A; j += 8) {
-                float q[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) q[k] = p[j + k];
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    running += q[k];
-                    const bool hit = !found && r <= running;
-                    mine = hit ? j + k : mine;
-                    found = found || hit;
-                }
-            }
-            for (; j < A; j++) {
-                running += p[j];
-                const bool hit = !found && r <= running;
-                mine = hit ? j : mine;
-                found = found || hit;
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < RG; g++) pick[g] = __shfl(mine, g, 64);
-    }
-#pragma unroll
-    for (int g = 0; g < RG; g++) {
-        float pp0 = __shfl(p0[g], pick[g] >> 1, 64), pp1 = __shfl(p1[g], pick[g] >> 1, 64);
-        if (lane == 0 && ok[g]) {
-            act[row[g]] = pick[g];
-            const float pp = (pick[g] & 1) ? pp1 : pp0;
-            if (logp) logp[row[g]] = rs_logf(1e-12f < pp ? pp : 1e-12f);  // log(std::max(1e-12f, p))
-        }
-    }
-}
-// sample_rows with the softmax and the writes in a loop over the RG rows instead of unrolled, for the fused
-// inference kernel: the unrolled form is ~1,900 instructions that each call executes once, so instruction
-// fetch, not arithmetic, set its time (its phase trace: 17 us from the staged logits to the probs).  Same
-// per-row operations in the same order (the probs go to LDS in both modes and the pick's prob is read back
-// from there: the same float), so the same actions and log probs; the running-sum walk keeps one lane per row,
-// all RG rows at once.  rowfn(g, lg, mk, pr, row, ok) gives row g's logits, masks, LDS probs, row and write flag;
+// The sampler for the RG rows of one wave: lane l holds actions 2l and 2l + 1 of the row at hand.  The softmax and
+// the writes loop over the rows (not unrolled: unrolled over 8 rows it was ~1,900 instructions that each call
+// executes once, and instruction fetch, not arithmetic, set its time -- 17 us from the staged logits to the probs in
+// the fused kernel's phase trace); the probs go to LDS in both modes and the pick's prob is read back from there;
+// the running-sum walk keeps one lane per row, all RG rows at once.  rowfn(g, lg, mk, pr, row, ok) gives row g's A
+// logits (global or LDS; LT: 16-bit in the format F16 names, or float), its masks, A floats of LDS scratch for its
+// probs, its row and write flag: act[row], logp[row] are written where ok.  row_sel is the caller's business.
 // mark(k) optional phase timestamps (the fused kernel's trace): 0 = probs in LDS, 1 = picks known.
 struct NoMark {
     __device__ void operator()(int) const {}
 };
-template <int RG, bool F16, typename RowFn, typename Mark = NoMark>
+template <int RG, bool F16, typename LT = uint16_t, typename RowFn, typename Mark = NoMark>
 __device__ __forceinline__ void sample_rows_looped(RowFn rowfn, int A, float temp, int deterministic, uint64_t seed,
                                                    uint64_t step, int64_t row0, int lane, int32_t* act, float* logp,
                                                    Mark mark = Mark{}) {
 #pragma clang fp contract(off)
     const int a0 = 2 * lane, a1 = 2 * lane + 1;
     const bool in0 = a0 < A, in1 = a1 < A;
-    const int c0 = min(a0, A - 1), c1 = min(a1, A - 1);
-    int mine = A - 1;  // lane g < RG: row g's pick (deterministic: its argmax)
+    const int c0 = min(a0, A - 1), c1 = min(a1, A - 1);  // loads stay unconditional (no branches between them)
+    int mine = A - 1;  // lane g < RG: row g's pick (deterministic: its argmax); cols - 1 when no running sum reaches r
 #pragma unroll 1
     for (int g = 0; g < RG; g++) {
-        const uint16_t* lg;
+        const LT* lg;
         const uint8_t* mk;
         float* pr;
         int rw;
         bool ok;
         rowfn(g, lg, mk, pr, rw, ok);
-        float l0 = mlp::h2f<F16>(lg[c0]), l1 = mlp::h2f<F16>(lg[c1]);
+        float l0 = logit_f<F16>(lg[c0]), l1 = logit_f<F16>(lg[c1]);
         const uint8_t m0 = mk[c0], m1 = mk[c1];
-        if (temp != 1.f) {  // wave-uniform, as in sample_rows
+        if (temp != 1.f) {  // wave-uniform; x / 1 = x exactly, the branch only spares T = 1 the division's time
             l0 = l0 / temp;
             l1 = l1 / temp;
         }
+        // softmax over all A columns (masked ones carry -1e10, exactly as the reference)
         float z0 = in0 ? l0 + (m0 ? 0.f : kDisabledLogit) : 0.f;
         float z1 = in1 ? l1 + (m1 ? 0.f : kDisabledLogit) : 0.f;
         const float m = mlp::wave_max_x(fmaxf(in0 ? z0 : -INFINITY, in1 ? z1 : -INFINITY));
@@ -258,7 +132,7 @@ __device__ __forceinline__ void sample_rows_looped(RowFn rowfn, int A, float tem
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (!deterministic && lane < RG) {
-        const uint16_t* lg;
+        const LT* lg;
         const uint8_t* mk;
         float* p;
         int rw;
@@ -266,6 +140,8 @@ __device__ __forceinline__ void sample_rows_looped(RowFn rowfn, int A, float tem
         rowfn(lane, lg, mk, p, rw, ok);
         const float r = (float)(philox(sample_key(seed, step), (uint32_t)(row0 + rw), (uint32_t)step) >> 8) *
                         (1.f / 16777216.f);
+        // the sequential running sum, 8 probs' LDS loads issued ahead of their adds (the loads do not depend
+        // on the sum; one LDS round trip per 8 columns instead of per column)
         float running = 0.f;
         bool found = false;
         int j = 0;
@@ -292,7 +168,7 @@ __device__ __forceinline__ void sample_rows_looped(RowFn rowfn, int A, float tem
 #pragma unroll 1
     for (int g = 0; g < RG; g++) {
         const int pk = __shfl(mine, g, 64);
-        const uint16_t* lg;
+        const LT* lg;
         const uint8_t* mk;
         float* pr;
         int rw;
@@ -306,21 +182,25 @@ __device__ __forceinline__ void sample_rows_looped(RowFn rowfn, int A, float tem
     }
 }
 
+// the sampler alone (the layered inference path): one wave per row, 4 rows per block.
+// row_sel (optional): only rows with (row_sel[row] != 0) == sel are written (mixed-policy inference).
 template <bool F16, typename LT = uint16_t>
 __global__ void __launch_bounds__(256) sample_actions(const LT* logits, const uint8_t* masks, int n, int A, float temp,
                                                      int deterministic, uint64_t seed, uint64_t step, int64_t row0,
                                                      int32_t* act, float* logp, const uint8_t* row_sel = nullptr,
                                                      int sel = 0) {
-    __shared__ float probs[4][kMaxA];  // one row of probs per wave (sample_rows' running sum)
+    __shared__ float probs[4][kMaxA];  // one row of probs per wave (the sampler's running sum)
     int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n) return;
     if (row_sel && ((row_sel[row] != 0) != (sel != 0))) return;
-    const LT* const lg[1] = {logits + (int64_t)row * A};
-    const uint8_t* const mk[1] = {masks + (int64_t)row * A};
-    float* const pr[1] = {probs[threadIdx.x >> 6]};
-    const int rw[1] = {row};
-    const bool ok[1] = {true};
-    sample_rows<1, F16, LT>(lg, mk, pr, A, temp, deterministic, seed, step, row0, rw, ok, lane, act, logp);
+    const auto rowfn = [&](int, const LT*& lg, const uint8_t*& mk, float*& pr, int& rw, bool& ok) {
+        lg = logits + (int64_t)row * A;
+        mk = masks + (int64_t)row * A;
+        pr = probs[threadIdx.x >> 6];
+        rw = row;
+        ok = true;
+    };
+    sample_rows_looped<1, F16, LT>(rowfn, A, temp, deterministic, seed, step, row0, lane, act, logp);
 }
 
 // PPO policy loss + entropy and its gradient w.r.t. the fp32 training logits.
@@ -359,66 +239,228 @@ __device__ __forceinline__ float grp_max(float v) {
 // Its gradient g_guide sign(c - gp) (sign(0) = 0, torch's abs backward) joins d[k] before the clamp gate, so the
 // softmax backward, the 1 / temp factor, dlogits, the bias partials and the H3 amax all see it; the metric
 // (RLGPU_M_GUIDING_LOSS) is the block's sum of |gp - c| over n A.  Masked columns hold 1e-11 on both sides: exactly 0.
-// GUIDE != 0 always has the OPT = true semantics.  The two kernels share their statements as policy_loss_body.inc, every
-// guided one behind if constexpr: the unguided instances keep their instruction streams.
-template <int K, bool OPT>
+// GUIDE != 0 always has the OPT = true semantics.  Every guided statement is behind if constexpr (GUIDE != 0), which
+// emits nothing for GUIDE = 0: the unguided instances take guide = nullptr, g_guide = 0 and never read them.  The body
+// stays one flat text: with its statements moved into __forceinline__ helpers the instances' register allocation and
+// operand order moved ("Guiding policy").
+template <int K, bool OPT, int GUIDE = 0>
 __global__ void __launch_bounds__(256) policy_loss(const float* logits, const uint8_t* masks, const int32_t* actions,
                                                   const float* old_logp, const float* adv, const int32_t* idx, int64_t start,
                                                   int n, int A, const float* adv_stats, float bsr, float clip_range,
                                                   float ent_scale, float inv_log_a, float temp, int mask_entropy,
                                                   float* dlogits, int ldd, float* metrics, float* bias_part,
-                                                  float* amax) {
-    constexpr int GUIDE = 0;
-    [[maybe_unused]] const uint16_t* const guide = nullptr;  // named by the body's discarded guided statements
-    [[maybe_unused]] const float g_guide = 0.f;
-#include "policy_loss_body.inc"
-}
-// the guided loss: policy_loss<K, true> plus the guide term on `guide`, 16-bit logits [*, A] in the format F16 names
-template <int K, bool F16>
-__global__ void __launch_bounds__(256) policy_loss_guided(const float* logits, const uint8_t* masks, const int32_t* actions,
-                                                         const float* old_logp, const float* adv, const int32_t* idx,
-                                                         int64_t start, int n, int A, const float* adv_stats, float bsr,
-                                                         float clip_range, float ent_scale, float inv_log_a, float temp,
-                                                         int mask_entropy, float* dlogits, int ldd, float* metrics,
-                                                         float* bias_part, float* amax, const uint16_t* guide, float g_guide) {
-    constexpr bool OPT = true;
-    constexpr int GUIDE = F16 ? 2 : 1;
-#include "policy_loss_body.inc"
+                                                  float* amax, const uint16_t* guide, float g_guide) {
+    static_assert(GUIDE == 0 || OPT, "a guided instance has the options' semantics");
+    __shared__ float red[16][GUIDE ? 6 : 5];
+    __shared__ float colred[16][16 * K];  // per (wave, lane group) column sums of dlogits
+    uint32_t vmax = 0;  // max |dlogits| (H3 operand scale, when amax is given)
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, grp = lane >> 4, i = lane & 15;
+    const float mean = adv_stats[0], sd = adv_stats[1];
+    float m_ent = 0.f, m_kl = 0.f, m_pl = 0.f, m_ratio = 0.f, m_clip = 0.f;
+    [[maybe_unused]] float m_guide = 0.f;  // this lane's sum of |gp - c| over its columns of the valid rows (GUIDE)
+    float col[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) col[k] = 0.f;
+    const float g_pl = -bsr / (float)n;
+    const float g_ent_a = -ent_scale * bsr * inv_log_a / (float)n;  // d loss / d H_i (H_i unnormalised)
+    const float inv_temp = 1.f / temp;  // d z / d logit (OPT)
+#pragma unroll
+    for (int pass = 0; pass < PL_PASSES; pass++) {
+        const int row = blockIdx.x * PL_ROWS + (w * PL_PASSES + pass) * 4 + grp;
+        const bool valid = row < n;
+        const int rowc = valid ? row : n - 1;
+        const int64_t sidx = idx ? (int64_t)idx[start + rowc] : start + rowc;
+        const float* lg = logits + (int64_t)rowc * A;
+        const uint8_t* mk = masks + sidx * A;
+        float z[K], legal_l = 0.f;
+        bool in[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const int a = i + 16 * k;
+            in[k] = a < A;
+            if constexpr (OPT) {
+                const bool on = in[k] && mk[a] != 0;
+                z[k] = in[k] ? lg[a] / temp + (on ? 0.f : kDisabledLogit) : -INFINITY;
+                legal_l += on ? 1.f : 0.f;
+            } else {
+                z[k] = in[k] ? lg[a] + (mk[a] ? 0.f : kDisabledLogit) : -INFINITY;
+            }
+        }
+        // maskEntropy: the row's entropy over log(its legal actions) (PPOLearner.cpp:426-428), one legal action
+        // dividing by log 1 = 0 as the reference does; otherwise the launch constant 1 / log A
+        float inv_log = inv_log_a, g_ent = g_ent_a;
+        if constexpr (OPT)
+            if (mask_entropy) {
+                inv_log = 1.f / logf(grp_sum(legal_l));
+                g_ent = -ent_scale * bsr * inv_log / (float)n;
+            }
+        const int a_raw = actions[sidx];
+        const float old = old_logp[sidx], advr = adv[sidx];
+        float m = z[0];
+#pragma unroll
+        for (int k = 1; k < K; k++) m = fmaxf(m, z[k]);
+        m = grp_max(m);
+        float e[K], esum = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            e[k] = in[k] ? expf(z[k] - m) : 0.f;
+            esum += e[k];
+        }
+        const float sum = grp_sum(esum);
+        float p[K], c[K], lgc[K], ent_l = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            p[k] = e[k] / sum;
+            c[k] = fminf(fmaxf(p[k], kMinProb), 1.f);
+            lgc[k] = in[k] ? logf(c[k]) : 0.f;
+            ent_l += in[k] ? lgc[k] * c[k] : 0.f;
+        }
+        const float ent = -grp_sum(ent_l);
+        // the guide's clamped probabilities of the row, kept only as sign(c - gp) and the lane's sum of |gp - c|
+        [[maybe_unused]] float sg[K];
+        if constexpr (GUIDE != 0) {
+            const uint16_t* gl = guide + sidx * A;
+            float zg[K];
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const int a = i + 16 * k;
+                const bool on = in[k] && mk[a] != 0;
+                zg[k] = in[k] ? mlp::h2f<GUIDE == 2>(gl[a]) / temp + (on ? 0.f : kDisabledLogit) : -INFINITY;
+            }
+            float mg = zg[0];
+#pragma unroll
+            for (int k = 1; k < K; k++) mg = fmaxf(mg, zg[k]);
+            mg = grp_max(mg);
+            float gsum_l = 0.f;
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                zg[k] = in[k] ? expf(zg[k] - mg) : 0.f;
+                gsum_l += zg[k];
+            }
+            const float gsum = grp_sum(gsum_l);
+            float gabs_l = 0.f;
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const float gp = fminf(fmaxf(zg[k] / gsum, kMinProb), 1.f);
+                sg[k] = c[k] > gp ? 1.f : (c[k] < gp ? -1.f : 0.f);
+                gabs_l += in[k] ? fabsf(gp - c[k]) : 0.f;
+            }
+            if (valid) m_guide += gabs_l;
+        }
+        const int a = a_raw < 0 ? 0 : (a_raw > A - 1 ? A - 1 : a_raw);
+        // the action's clamped probability: lane a % 16 of the group holds it in slot a / 16
+        float mine = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; k++)
+            if (a == i + 16 * k) mine = c[k];
+        const float pa = __shfl(mine, (lane & ~15) | (a & 15), 64);
+        const float lp = logf(pa);
+        const float ratio = expf(lp - old);
+        const float advn = (advr - mean) / (sd + 1e-8f);
+        const float clipped = fminf(fmaxf(ratio, 1.f - clip_range), 1.f + clip_range);
+        const float s1 = ratio * advn, s2 = clipped * advn;
+        const float pl = fminf(s1, s2);
+        // ---- backward (torch semantics: min() ties split the gradient, clamp passes inside [lo, hi])
+        const float g_s1 = s1 < s2 ? g_pl : (s1 == s2 ? g_pl * 0.5f : 0.f);
+        const float g_s2 = s2 < s1 ? g_pl : (s1 == s2 ? g_pl * 0.5f : 0.f);
+        const float in_rng = (ratio >= 1.f - clip_range && ratio <= 1.f + clip_range) ? 1.f : 0.f;
+        const float g_ratio = g_s1 * advn + g_s2 * advn * in_rng;
+        const float g_lp = g_ratio * ratio;
+        float d[K], dot_l = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            d[k] = in[k] ? -g_ent * (lgc[k] + 1.f) : 0.f;
+            if (a == i + 16 * k) d[k] += g_lp / c[k];
+            if constexpr (GUIDE != 0) d[k] += in[k] ? g_guide * sg[k] : 0.f;
+            d[k] = (p[k] >= kMinProb && p[k] <= 1.f) ? d[k] : 0.f;
+            dot_l += in[k] ? d[k] * p[k] : 0.f;
+        }
+        const float dot = grp_sum(dot_l);
+        if (valid) {
+            // dlogits rows of ldd >= A floats: the columns [A, ldd) are written as zeros, so the
+            // output layer's GEMMs read 16-byte vectors across the row end
+            float* dl = dlogits + (int64_t)row * ldd;
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                if (!in[k]) {
+                    if (i + 16 * k < ldd) dl[i + 16 * k] = 0.f;
+                    continue;
+                }
+                const float gk = OPT ? p[k] * (d[k] - dot) * inv_temp : p[k] * (d[k] - dot);
+                dl[i + 16 * k] = gk;
+                col[k] += gk;
+                const uint32_t b = mlp::abs_bits(gk);
+                vmax = b > vmax ? b : vmax;
+            }
+            const float lr = lp - old;
+            m_ent += ent * inv_log;
+            m_kl += expf(lr) - 1.f - lr;
+            m_pl += -pl;
+            m_ratio += ratio;
+            m_clip += fabsf(ratio - 1.f) > clip_range ? 1.f : 0.f;
+        }
+    }
+    const int slot = w * 4 + grp;
+#pragma unroll
+    for (int k = 0; k < K; k++) colred[slot][i + 16 * k] = col[k];
+    if constexpr (GUIDE != 0) m_guide = grp_sum(m_guide);
+    if (i == 0) {
+        if constexpr (GUIDE != 0) red[slot][5] = m_guide;
+        red[slot][0] = m_ent;
+        red[slot][1] = m_kl;
+        red[slot][2] = m_pl;
+        red[slot][3] = m_ratio;
+        red[slot][4] = m_clip;
+    }
+    __syncthreads();
+    if (bias_part)  // output-bias gradient partials of this block's rows: part[blk][A]
+        for (int c2 = threadIdx.x; c2 < A; c2 += 256) {
+            float t = 0.f;
+            for (int q = 0; q < 16; q++) t += colred[q][c2];
+            bias_part[(int64_t)blockIdx.x * A + c2] = t;
+        }
+    if (threadIdx.x < 5 && metrics) {
+        const int mslot[5] = {0, 1, 2, 4, 5};  // entropy, KL, policy loss, ratio, clip fraction
+        float v = 0.f;
+        for (int q = 0; q < 16; q++) v += red[q][threadIdx.x];
+        atomicAdd(&metrics[mslot[threadIdx.x]], v / (float)n);
+    }
+    if constexpr (GUIDE != 0)
+        if (threadIdx.x == 5 && metrics) {  // mean over all n A elements
+            float v = 0.f;
+            for (int q = 0; q < 16; q++) v += red[q][5];
+            atomicAdd(&metrics[kGuidingLossSlot], v / ((float)n * (float)A));
+        }
+    if (amax) mlp::h3_amax_commit(amax, vmax);
 }
 
-// the instantiation with ceil(A / 16) actions per lane (A = 90: 6 of the 8 slots PL_K allows), with the policy
-// options (opt) or without them
-template <bool OPT>
-inline decltype(&policy_loss<PL_K, OPT>) policy_loss_any(int A) {
+// f(std::integral_constant<int, K>) with K = ceil(A / 16) actions per lane (A = 90: 6 of the 8 slots PL_K allows):
+// a run-time action count as the template argument of one launch expression
+template <class F>
+inline void with_actions_per_lane(int A, F&& f) {
     switch ((A + 15) / 16) {
-        case 1: return &policy_loss<1, OPT>;
-        case 2: return &policy_loss<2, OPT>;
-        case 3: return &policy_loss<3, OPT>;
-        case 4: return &policy_loss<4, OPT>;
-        case 5: return &policy_loss<5, OPT>;
-        case 6: return &policy_loss<6, OPT>;
-        case 7: return &policy_loss<7, OPT>;
-        default: return &policy_loss<PL_K, OPT>;
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        default: return f(std::integral_constant<int, PL_K>{});
     }
 }
-inline decltype(&policy_loss<PL_K, false>) policy_loss_any(int A, bool opt) {
-    return opt ? policy_loss_any<true>(A) : policy_loss_any<false>(A);
-}
-template <bool F16>
-inline decltype(&policy_loss_guided<PL_K, F16>) policy_loss_guided_any(int A) {
-    switch ((A + 15) / 16) {
-        case 1: return &policy_loss_guided<1, F16>;
-        case 2: return &policy_loss_guided<2, F16>;
-        case 3: return &policy_loss_guided<3, F16>;
-        case 4: return &policy_loss_guided<4, F16>;
-        case 5: return &policy_loss_guided<5, F16>;
-        case 6: return &policy_loss_guided<6, F16>;
-        case 7: return &policy_loss_guided<7, F16>;
-        default: return &policy_loss_guided<PL_K, F16>;
-    }
-}
-inline decltype(&policy_loss_guided<PL_K, false>) policy_loss_guided_any(int A, bool f16) {
-    return f16 ? policy_loss_guided_any<true>(A) : policy_loss_guided_any<false>(A);
+// the policy-loss instance for A actions: without the policy options, with them (opt), or with a guide (guide = 1:
+// bf16 guide logits, 2: fp16; implies opt)
+using policy_loss_fn = decltype(&policy_loss<PL_K, false, 0>);
+inline policy_loss_fn policy_loss_any(int A, bool opt, int guide) {
+    policy_loss_fn fn = nullptr;
+    with_actions_per_lane(A, [&](auto K) {
+        fn = guide == 2   ? &policy_loss<K(), true, 2>
+             : guide == 1 ? &policy_loss<K(), true, 1>
+             : opt        ? &policy_loss<K(), true, 0>
+                          : &policy_loss<K(), false, 0>;
+    });
+    return fn;
 }
 
 // Critic MSE: loss = mean((v - t)^2) * bsr ; dv = 2 (v - t) / n * bsr.

@@ -244,17 +244,11 @@ __global__ void __launch_bounds__(256) transfer_loss(const float* logits, const 
     if (amax) mlp::h3_amax_commit(amax, vmax);
 }
 
-inline decltype(&transfer_loss<PL_K>) transfer_loss_any(int A) {
-    switch ((A + 15) / 16) {
-        case 1: return &transfer_loss<1>;
-        case 2: return &transfer_loss<2>;
-        case 3: return &transfer_loss<3>;
-        case 4: return &transfer_loss<4>;
-        case 5: return &transfer_loss<5>;
-        case 6: return &transfer_loss<6>;
-        case 7: return &transfer_loss<7>;
-        default: return &transfer_loss<PL_K>;
-    }
+using transfer_loss_fn = decltype(&transfer_loss<PL_K>);
+inline transfer_loss_fn transfer_loss_any(int A) {
+    transfer_loss_fn fn = nullptr;
+    with_actions_per_lane(A, [&](auto K) { fn = &transfer_loss<K()>; });
+    return fn;
 }
 
 // The policy-only optimiser step (ModelSet::StepOptims after SetOptimLR(tlConfig.lr), with no clip_grad_norm_ before it,

@@ -170,6 +170,40 @@ def test_sampler_bit_exact_vs_oracle(gpu, monkeypatch, kw, fp16, fused, chunk):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("f32", [False, True], ids=["logits16", "logits32"])
+@pytest.mark.parametrize("A", [2, 3, 9, 128])
+def test_layered_sampler_small_action_counts(gpu, monkeypatch, A, f32):
+    """The layered sampler (sample_actions, RLGPU_FUSED_INFER=0) away from A = 90 and thousands of rows: one lane with
+    a single column (A = 2: lane 0 holds both, A = 3: lane 1 holds one), only the running sum's tail loop (A < 8), an
+    unrolled group of 8 plus a tail (A = 9) and kMaxA (A = 128); 5 rows, so the second block is partial and three of
+    its waves return early.  16-bit and fp32 logits; actions equal and log probs bit-equal to the oracle on the
+    handle's own logits."""
+    import torch
+    from rlgpu.ppo import PPO
+    monkeypatch.setenv("RLGPU_FUSED_INFER", "0")
+    n = 5
+    p = PPO(obs_size=24, num_actions=A, policy_layers=(48,), critic_layers=(8,), max_rows=8, seed=13,
+            infer_fp16=2 if f32 else False)
+    rng = np.random.default_rng(100 + A)
+    obs = rng.standard_normal((n, 24)).astype(np.float32)
+    masks = (rng.random((n, A)) < 0.6).astype(np.uint8)
+    masks[:, A - 1] = 1
+    masks[0, :A - 1] = 0  # row 0: exactly one legal action
+    o, m = torch.from_numpy(obs).to(gpu), torch.from_numpy(masks).to(gpu)
+    logits = p.forward(0, o).cpu().numpy() if f32 else _gpu_logits16(p, o, False)
+    assert logits.shape == (n, A) and logits.dtype == (np.float32 if f32 else np.uint16)
+    for det in (True, False):
+        for step in (0, 2**31 + 5):
+            a, lp = p.infer_actions(o, m, step=step, deterministic=det)
+            wa, wlp = oracle.sample_actions(logits, masks, det, p.cfg.seed, step, 0)
+            ga, glp = a.cpu().numpy(), lp.cpu().numpy()
+            print("A=%d f32=%d det=%d step=%d actions %s / %s logp %s / %s" % (A, f32, det, step, ga, wa, glp, wlp))
+            np.testing.assert_array_equal(ga, wa)
+            np.testing.assert_array_equal(glp.view(np.uint32), wlp.view(np.uint32))
+            assert (masks[np.arange(n), ga] == 1).all() and ga[0] == A - 1 and np.isfinite(glp).all()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("kw", [dict(), dict(shared_layers=(384, 384), policy_layers=(384,) * 3, critic_layers=(384,) * 3)],
                          ids=["c2", "shared-head"])
 def test_fp32_inference_bit_exact_vs_oracle(gpu, kw):
