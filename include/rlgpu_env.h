@@ -10,8 +10,9 @@
  *     ResetArena(int) / Reset()            EnvSet.cpp:275-354  -> rlgpu_envset_reset_arena / _reset
  *     state.{obs,actionMasks,rewards,terminals,arenaPlayerStartIdx}
  *                                          EnvSet.h:35-65      -> rlgpu_envset_buffers
- * The EnvCreateFn's plugin set (EnvCreateResult, EnvSet.h:14-24) is AdvancedObs, DefaultAction and
- * KickoffState, plus a device registry of weighted rewards and terminal conditions
+ * The EnvCreateFn's plugin set (EnvCreateResult, EnvSet.h:14-24) is an obs builder (AdvancedObs by default,
+ * DefaultObs, DefaultObsPadded), DefaultAction and a state setter (KickoffState by default), plus a device
+ * registry of weighted rewards and terminal conditions
  * (rlgpu_reward_spec / rlgpu_terminal_spec lists in rlgpu_envset_config; NULL lists = src/ExampleMain.cpp:
  * 128-226: the 13 weighted rewards and NoTouchCondition(8) + ScoreLimitCondition(3)).
  *
@@ -40,7 +41,13 @@ extern "C" {
 #define RLGPU_MANIFOLDS 12    /* contact-manifold slots per arena per tick (build limit, overflow counted) */
 #define RLGPU_MAX_SOLVER_ROWS 14 /* contact rows per arena per tick (build limit, overflow counted) */
 #define RLGPU_MAX_MESH_OBJECTS 32 /* static collision meshes per arena (SOCCAR loads 16, HOOPS 12) */
-#define RLGPU_OBS 167         /* AdvancedObs 9+8+34+29*4 (AdvancedObs.cpp:193-270) */
+#define RLGPU_OBS 167         /* AdvancedObs 9+8+34+29*4 (AdvancedObs.cpp:193-270): that builder's width, and the
+                                 widest row an env set builds (the capacity of the kernel's staging rows); a
+                                 set's own width is rlgpu_envset_obs_size */
+#define RLGPU_OBS_ADVANCED 0       /* EnvCreateResult::obsBuilder: AdvancedObs (zero: the default) */
+#define RLGPU_OBS_DEFAULT 1        /* DefaultObs(posCoef, velCoef, angVelCoef), 9+8+34+19*4 = 127 floats */
+#define RLGPU_OBS_DEFAULT_PADDED 2 /* DefaultObsPadded(maxPlayers, ...), 51 + 19*2*maxPlayers floats */
+#define RLGPU_OBS_DEFAULT_SIZE 127
 #define RLGPU_ACTIONS 90      /* DefaultAction table (DefaultAction.cpp:3-89) */
 #define RLGPU_REWARDS 13      /* ExampleMain reward list (src/ExampleMain.cpp:132-177) */
 #define RLGPU_MAX_REWARDS 32  /* weighted rewards per env set (device registry) */
@@ -252,6 +259,22 @@ typedef struct {
      * data-parallel job passes r x num_arenas, so its arenas are the ones a single device holding every
      * arena would step (0 for one device) */
     int32_t arena_offset;
+    /* EnvCreateResult::obsBuilder (RLGPU_OBS_*): AdvancedObs (0, the default), DefaultObs
+     * (RG/ObsBuilders/DefaultObs.cpp) or DefaultObsPadded (DefaultObsPadded.cpp) with obs_max_players slots per
+     * team (2 or 3 in 2v2: 1 has too few teammate slots, as the reference says at its first BuildObs; 4 and more
+     * do not fit the kernel's staging rows).  obs_pos_coef / obs_vel_coef / obs_ang_vel_coef are DefaultObs's
+     * constructor arguments; all five zero selects its defaults (1/4096, 1/5120, 1/2044), 1/2300, 1/5.5.  A
+     * non-finite coefficient is RLGPU_ERR_INVALID_ARG.  DefaultObsPadded's shuffles are every order equally
+     * likely and independent per row, drawn from a stream of their own: not
+     * std::shuffle's permutations, which are implementation-defined.  The fields are read only for the builders
+     * that have them.
+     * Position: these seven fields stand between arena_offset and state_setter, not at the struct's end.  Code that
+     * fills the struct by member name (or zero-initialises it and assigns) is unaffected; code that initialises it
+     * by position beyond arena_offset must be updated, and rlgpu_envset_config_size() tells a stale mirror apart. */
+    int32_t obs_builder;
+    int32_t obs_max_players;
+    float obs_pos_coef[3];
+    float obs_vel_coef, obs_ang_vel_coef;
     /* EnvCreateResult::stateSetter (RLGPU_SS_*): KickoffState (RG/StateSetters/KickoffState.h), or
      * FuzzedKickoffState (FuzzedKickoffState.h:7-26: the kickoff, then every car's position moved by
      * RandFloat(-0.1, 0.1) uu per axis through CarState, RS/Sim/Car/Car.cpp:23-36) -- the skill tracker's
@@ -270,24 +293,24 @@ typedef struct {
 
 /* Experience-append destinations of the fused step (Learner.cpp:823-861); any may be NULL. */
 typedef struct {
-    float* obs;          /* [players][OBS] obs after the step (post-reset): rollout row t+1 */
+    float* obs;          /* [players][obs_size] obs after the step (post-reset): rollout row t+1 */
     uint8_t* masks;      /* [players][ACTIONS] masks after the step (post-reset) */
     float* rewards;      /* [players] */
     int8_t* terminals;   /* [players] trajectory codes 0 / 1 NORMAL / 2 TRUNCATED (incl. max length) */
-    float* trunc_obs;    /* [players][OBS] obs before the reset, written where the code is 2 */
+    float* trunc_obs;    /* [players][obs_size] obs before the reset, written where the code is 2 */
 } rlgpu_step_outputs;
 
 typedef struct rlgpu_envset rlgpu_envset;
 
 /* Device views of EnvState (EnvSet.h:35-65).  Valid until rlgpu_envset_destroy. */
 typedef struct {
-    float* obs;              /* [num_players][RLGPU_OBS] */
+    float* obs;              /* [num_players][obs_size] (rlgpu_envset_obs_size) */
     uint8_t* action_masks;   /* [num_players][RLGPU_ACTIONS] */
     float* rewards;          /* [num_players] */
     uint8_t* terminals;      /* [num_arenas]: 0, 1 NORMAL, 2 TRUNCATED */
     float* last_rewards;     /* [num_arenas][num_rewards]: each reward's value for player 0 (if save_rewards;
                                 EnvState::lastRewards, EnvSet.cpp:224-242) */
-    float* trunc_obs;        /* [num_players][RLGPU_OBS] pre-reset obs of truncated arenas */
+    float* trunc_obs;        /* [num_players][obs_size] pre-reset obs of truncated arenas */
     int32_t num_players;
     int32_t num_arenas;
     int32_t num_rewards;     /* length of the reward list */
@@ -298,6 +321,12 @@ typedef struct {
 int rlgpu_envset_create(const rlgpu_envset_config* cfg, rlgpu_envset** out);
 int rlgpu_envset_destroy(rlgpu_envset* env);
 int rlgpu_envset_buffers_get(rlgpu_envset* env, rlgpu_envset_buffers* out);
+/* The width of the set's obs rows: what its obs builder makes (167 / 127 / 51 + 38 x obs_max_players); -1 for NULL. */
+int rlgpu_envset_obs_size(rlgpu_envset* env);
+/* The same for a builder kind and DefaultObsPadded's maxPlayers (ignored by the other kinds), on the host alone:
+ * 167, 127 or 51 + 38 x max_players; -1 and a message naming the value (rlgpu_last_error) for an unknown kind or
+ * a refused max_players (1: too many teammates in 2v2; >= 4: wider than the kernel's staging rows). */
+int rlgpu_obs_builder_size(int32_t kind, int32_t max_players);
 
 /* EnvSet::Reset(): reset arenas whose terminal flag is set, rebuild their obs/masks. */
 int rlgpu_envset_reset(rlgpu_envset* env, void* stream);
@@ -330,16 +359,16 @@ int rlgpu_envset_step_range(rlgpu_envset* env, int32_t first, int32_t count, con
  * rlgpu_envset_step leave, bit for bit.  Row 0 of obs / masks is the caller's (the previous rollout's row T).
  * Eligible (rlgpu_envset_collect_loop_ok, else RLGPU_ERR_UNSUPPORTED): the msvc_x64 arithmetic (the one the loop
  * kernel is built for), action_delay > 0, no per-phase profile, and a policy that
- * rlgpu_ppo_wave_infer accepts with RLGPU_OBS inputs and RLGPU_ACTIONS outputs.  The env timing figure of such a
+ * rlgpu_ppo_wave_infer accepts with the set's obs_size inputs and RLGPU_ACTIONS outputs.  The env timing figure of such a
  * launch includes the in-workgroup inference. */
 typedef struct {
-    float* obs;          /* [steps + 1][players][RLGPU_OBS] */
+    float* obs;          /* [steps + 1][players][obs_size] */
     uint8_t* masks;      /* [steps + 1][players][RLGPU_ACTIONS] */
     int32_t* actions;    /* [steps][players] */
     float* logp;         /* [steps][players] */
     float* rewards;      /* [steps][players] */
     int8_t* terminals;   /* [steps][players] trajectory codes */
-    float* trunc_obs;    /* [steps][players][RLGPU_OBS] (rows of code 2), may be NULL */
+    float* trunc_obs;    /* [steps][players][obs_size] (rows of code 2), may be NULL */
 } rlgpu_collect_rollout;
 struct rlgpu_ppo;
 int rlgpu_envset_collect_loop_ok(rlgpu_envset* env, struct rlgpu_ppo* policy);
@@ -349,7 +378,7 @@ int rlgpu_envset_sync(rlgpu_envset* env, void* stream);
 /* Output-only rows (default off): a fused step given `out` rows for obs / masks / truncation obs writes those
  * rows only there, not also into the set's own buffers (rlgpu_envset_buffers obs / masks / trunc_obs), which
  * then keep the last step that had no such output.  One copy of the 3 KB of rows per env step instead of two
- * (obs 2,672 B + masks 360 B per arena); the C++ Learner turns it on for its own set, whose rollout rows are the
+ * (AdvancedObs: obs 2,672 B + masks 360 B per arena); the C++ Learner turns it on for its own set, whose rollout rows are the
  * only ones it reads.  A step without `out` (or with a NULL row pointer) writes the set's buffers as always. */
 int rlgpu_envset_set_output_only(rlgpu_envset* env, int32_t enable);
 

@@ -91,6 +91,13 @@ typedef struct {
     int32_t state_setter_flags;
     const rlgpu_state_setter_spec* state_setters;
     int32_t n_state_setters;
+    /* EnvCreateResult::obsBuilder of the training arenas (rlgpu_envset_config.obs_builder ..., passed to the env
+     * set as they are; all zero = AdvancedObs).  The builder's width (rlgpu_obs_builder_size) times frame_stack
+     * is the models' input width; an old-version, guiding or teacher policy must have it. */
+    int32_t obs_builder;
+    int32_t obs_max_players;
+    float obs_pos_coef[3];
+    float obs_vel_coef, obs_ang_vel_coef;
     /* Experience scheduling.  RLGPU_EXP_ROLLOUT (0, default): a fixed [T, P] rollout trained in full,
      * the unfinished tail bootstrapped from V(obs_T) (the engine's fast path, BASELINE configs).
      * RLGPU_EXP_TRAJECTORIES (1): the reference's -- steps are kept per player until the trajectory

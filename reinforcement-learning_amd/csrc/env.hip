@@ -381,7 +381,72 @@ void state_setters_from(const rlgpu_envset_config* cfg, rl::Plugins& p) {
     }
     p.ss_total = total;
 }
+
+// the width of an obs builder's rows, or a thrown Error naming what is refused (rlgpu_obs_builder_size)
+int obs_builder_width(int kind, int max_players) {
+    if (kind == RLGPU_OBS_ADVANCED) return RLGPU_OBS;
+    if (kind == RLGPU_OBS_DEFAULT) return RLGPU_OBS_DEFAULT_SIZE;
+    if (kind != RLGPU_OBS_DEFAULT_PADDED)
+        throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "unknown obs builder " + std::to_string(kind) + " (RLGPU_OBS_ADVANCED, "
+                                                  "RLGPU_OBS_DEFAULT or RLGPU_OBS_DEFAULT_PADDED)");
+    if (max_players < 2)
+        throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED,
+                           "DefaultObsPadded: maxPlayers " + std::to_string(max_players) + " leaves " +
+                               std::to_string(max_players - 1) + " teammate slots, and a 2v2 player has one teammate "
+                               "(the reference: \"Too many teammates for Obs\")");
+    if (51 + 38 * (int64_t)max_players > RLGPU_OBS)
+        throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED,
+                           "DefaultObsPadded: maxPlayers " + std::to_string(max_players) + " makes rows of " +
+                               std::to_string(51 + 38 * (int64_t)max_players) + " floats, and the env kernel's staging "
+                               "rows hold " + std::to_string(RLGPU_OBS) + " (maxPlayers 2 or 3)");
+    return 51 + 38 * max_players;
+}
+
+// the obs builder streams' Philox key: splitmix64(seed ^ splitmix64(kObsShuffleStream << 48)), the numbering of
+// rlgpu_host_uniform's streams (1 self-play picks, 2 skill runs, 3 the obs statistic's rows)
+constexpr uint64_t kObsShuffleStream = 4;
+uint64_t obs_shuffle_key(uint64_t seed) {
+    auto mix = [](uint64_t x) {  // splitmix64
+        x += 0x9E3779B97F4A7C15ull;
+        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+        return x ^ (x >> 31);
+    };
+    return mix(seed ^ mix(kObsShuffleStream << 48));
+}
+
+// the config's obs builder as the kernel reads it (Plugins::obs_*), validated
+void obs_builder_from(const rlgpu_envset_config* cfg, rl::Plugins& p) {
+    p.obs_kind = cfg->obs_builder;
+    p.obs_w = obs_builder_width(cfg->obs_builder, cfg->obs_max_players);
+    p.obs_max_players = cfg->obs_builder == RLGPU_OBS_DEFAULT_PADDED ? cfg->obs_max_players : 2;
+    const float c[5] = {cfg->obs_pos_coef[0], cfg->obs_pos_coef[1], cfg->obs_pos_coef[2], cfg->obs_vel_coef,
+                        cfg->obs_ang_vel_coef};
+    bool all_zero = true;
+    for (int i = 0; i < 5; i++) {  // AdvancedObs has no coefficients: its fields are not read
+        if (cfg->obs_builder == RLGPU_OBS_ADVANCED) break;
+        RLGPU_REQUIRE(std::isfinite(c[i]), std::string("rlgpu_envset_create: the obs builder's ") +
+                                               (i < 3 ? "obs_pos_coef[" + std::to_string(i) + "]"
+                                                      : std::string(i == 3 ? "obs_vel_coef" : "obs_ang_vel_coef")) +
+                                               " is not finite");
+        all_zero = all_zero && c[i] == 0.f;
+    }
+    // CommonValues SIDE_WALL_X 4096, BACK_WALL_Y 5120, CEILING_Z 2044, CAR_MAX_SPEED 2300, CAR_MAX_ANG_VEL 5.5
+    const float def[5] = {1 / 4096.f, 1 / 5120.f, 1 / 2044.f, 1 / 2300.f, 1 / 5.5f};
+    for (int i = 0; i < 3; i++) p.obs_pos_coef[i] = all_zero ? def[i] : c[i];
+    p.obs_vel_coef = all_zero ? def[3] : c[3];
+    p.obs_ang_vel_coef = all_zero ? def[4] : c[4];
+    const uint64_t key = obs_shuffle_key(cfg->seed);
+    p.obs_key[0] = (uint32_t)key;
+    p.obs_key[1] = (uint32_t)(key >> 32);
+}
 }  // namespace
+
+extern "C" int rlgpu_obs_builder_size(int32_t kind, int32_t max_players) {
+    int w = -1;
+    const int rc = rlgpu::guarded([&] { w = obs_builder_width(kind, max_players); });
+    return rc == 0 ? w : -1;
+}
 
 extern "C" int rlgpu_envset_default_plugins(rlgpu_reward_spec* rewards, int32_t* n_rewards, rlgpu_terminal_spec* terminals,
                                             int32_t* n_terminals) {
@@ -481,12 +546,12 @@ rl::StepArgs placed(rlgpu_envset* e, rl::StepArgs g, Range r) {
     const size_t a0 = (size_t)r.first, p0 = a0 * 4, nr = (size_t)e->plug.nr;
     g.arenas = e->d_arenas + a0 * rl::kRec;
     g.n = r.count;
-    g.obs = e->d_obs + p0 * RLGPU_OBS;
+    g.obs = e->d_obs + p0 * (size_t)e->plug.obs_w;
     g.masks = e->d_masks + p0 * RLGPU_ACTIONS;
     g.rewards = e->d_rewards + p0;
     g.terminals = e->d_terminals + a0;
     g.last_rewards = e->cfg.save_rewards ? e->d_last_rewards + a0 * nr : nullptr;
-    g.trunc_obs = e->d_trunc_obs + p0 * RLGPU_OBS;
+    g.trunc_obs = e->d_trunc_obs + p0 * (size_t)e->plug.obs_w;
     g.seed = e->cfg.seed;
     g.max_episode_steps = e->cfg.max_episode_steps;
     g.prof = e->d_prof;
@@ -589,6 +654,7 @@ extern "C" int rlgpu_envset_create(const rlgpu_envset_config* cfg, rlgpu_envset*
                       "rlgpu_envset_create: unknown arithmetic mode " + std::to_string(cfg->arith) + " (RLGPU_ARITH_*)");
         rl::Plugins plug = plugins_from(cfg);
         state_setters_from(cfg, plug);
+        obs_builder_from(cfg, plug);
         device_init(cfg->arith);
         // arena meshes (Arena::_SetupArenaCollisionShapes): triangle table + grid index in HBM
         std::vector<float> builtin;
@@ -648,8 +714,8 @@ extern "C" int rlgpu_envset_create(const rlgpu_envset_config* cfg, rlgpu_envset*
                 for (int p = 0; p < RLGPU_PADS; p++) s->pads[p].is_active = 1;
             }
             e->d_arenas = e->alloc_copy(host);
-            e->d_obs = e->alloc<float>(P * RLGPU_OBS);
-            e->d_trunc_obs = e->alloc_zero<float>(P * RLGPU_OBS);
+            e->d_obs = e->alloc<float>(P * (size_t)plug.obs_w);
+            e->d_trunc_obs = e->alloc_zero<float>(P * (size_t)plug.obs_w);
             e->d_rewards = e->alloc_zero<float>(P);
             e->d_last_rewards = e->alloc_zero<float>((size_t)n * std::max(plug.nr, 1));
             e->d_masks = e->alloc<uint8_t>(P * RLGPU_ACTIONS);
@@ -791,6 +857,8 @@ extern "C" int rlgpu_envset_buffers_get(rlgpu_envset* e, rlgpu_envset_buffers* o
     });
 }
 
+extern "C" int rlgpu_envset_obs_size(rlgpu_envset* e) { return e ? e->plug.obs_w : -1; }
+
 extern "C" int rlgpu_envset_reset(rlgpu_envset* e, void* stream) {
     return rlgpu::guarded([&] {
         RLGPU_REQUIRE(e, "null envset");
@@ -843,7 +911,7 @@ extern "C" int rlgpu_envset_step_range(rlgpu_envset* e, int32_t first, int32_t c
 
 extern "C" int rlgpu_envset_collect_loop_ok(rlgpu_envset* e, rlgpu_ppo* policy) {
     return e && policy && e->cfg.arith == RLGPU_ARITH_MSVC_X64 && e->cfg.action_delay > 0 && !e->d_prof &&
-           rlgpu::ppo_wave_policy(policy, RLGPU_OBS, RLGPU_ACTIONS);
+           rlgpu::ppo_wave_policy(policy, e->plug.obs_w, RLGPU_ACTIONS);
 }
 
 extern "C" int rlgpu_envset_collect_loop(rlgpu_envset* e, rlgpu_ppo* policy, int32_t steps, const rlgpu_collect_rollout* ro,
@@ -857,7 +925,7 @@ extern "C" int rlgpu_envset_collect_loop(rlgpu_envset* e, rlgpu_ppo* policy, int
                                                       "profile, a policy on the one-wave inference kernel)");
         const int64_t P = e->num_players;
         // step 0's fused step with its append (rollout row 1 / row 0); the kernel moves the rows on per step
-        const rlgpu_step_outputs out{ro->obs + P * RLGPU_OBS, ro->masks + P * RLGPU_ACTIONS, ro->rewards, ro->terminals,
+        const rlgpu_step_outputs out{ro->obs + P * e->plug.obs_w, ro->masks + P * RLGPU_ACTIONS, ro->rewards, ro->terminals,
                                      ro->trunc_obs};
         rl::CollectArgs c;
         std::memset(&c, 0, sizeof c);

@@ -1,5 +1,6 @@
 // env_builders.hpp -- the RLGymCPP layer of the env kernel: GameState snapshot, terminal
-// conditions, the ExampleMain reward list, AdvancedObs and DefaultAction masks, the state setters' reset.
+// conditions, the ExampleMain reward list, the obs builders (AdvancedObs, DefaultObs, DefaultObsPadded) and
+// DefaultAction masks, the state setters' reset.
 #pragma once
 #include "env_contacts.hpp"
 
@@ -64,12 +65,12 @@ DEV void add_player_obs(float* o, const PView& pl, bool inv, v3 bp, v3 bv) {
     o[28] = pl.has_jumped ? 1.0f : 0.0f;
 }
 
-// AdvancedObs::BuildObs + DefaultAction::GetActionMask of the arena's 4 players into LDS rows, on its 16 lanes with
-// one code path (AdvancedObs.cpp, DefaultAction masks): the 29-float player blocks of every row on lanes 4 j + pi
-// (j: self, teammate, first opponent, second opponent), then the ball / previous-action, boost-pad and mask
+// AdvancedObs::BuildObs of the arena's 4 players into LDS rows, on its 16 lanes with
+// one code path (AdvancedObs.cpp): the 29-float player blocks of every row on lanes 4 j + pi
+// (j: self, teammate, first opponent, second opponent), then the ball / previous-action and boost-pad
 // elements dealt over the lanes.  Every element is the same expression as in a per-player build; only the lane
 // that writes it differs.
-DEV void build_obs_rows(ArenaLDS* A, int l) {
+DEV void advanced_obs_rows(ArenaLDS* A, int l) {
     {
         const int pi = l & 3, j = l >> 2;
         const bool inv = pi & 1;  // the player's team (orange = index & 1)
@@ -104,6 +105,10 @@ DEV void build_obs_rows(ArenaLDS* A, int l) {
         const float timer = A->s.pads[tim_idx].cooldown;
         A->u.out.obs[p][17 + k] = active ? 1.0f : 1.0f / (1.0f + timer);
     }
+}
+
+// DefaultAction::GetActionMask of the arena's 4 players into LDS rows, dealt over its 16 lanes
+DEV void action_mask_rows(ArenaLDS* A, int l) {
     // action masks: 4 x 90 bytes; the players' flags packed 3 bits each (no run-time register index)
     uint32_t fl = 0;
 #pragma unroll
@@ -121,6 +126,101 @@ DEV void build_obs_rows(ArenaLDS* A, int l) {
         if (f & 4) r |= (bits >> 2) & 1;                         // can jump (or turtled): the jump actions on
         A->u.out.masks[p][k] = (uint8_t)(r & 1);
     }
+}
+
+// DefaultObs::AddPlayerToObs (DefaultObs.cpp:4-17): 19 floats
+DEV void add_player_default_obs(float* o, const PView& pl, bool inv, const Plugins* B) {
+    const v3 pos = inv_if(pl.pos, inv), vel = inv_if(pl.vel, inv), ang = inv_if(pl.ang, inv);
+    const v3 f = inv_if(pl.fwd, inv), u = inv_if(pl.up, inv);
+    const float vc = B->obs_vel_coef, ac = B->obs_ang_vel_coef;
+    o[0] = pos.x * B->obs_pos_coef[0]; o[1] = pos.y * B->obs_pos_coef[1]; o[2] = pos.z * B->obs_pos_coef[2];
+    o[3] = f.x; o[4] = f.y; o[5] = f.z;
+    o[6] = u.x; o[7] = u.y; o[8] = u.z;
+    o[9] = vel.x * vc; o[10] = vel.y * vc; o[11] = vel.z * vc;
+    o[12] = ang.x * ac; o[13] = ang.y * ac; o[14] = ang.z * ac;
+    o[15] = pl.boost / 100.f;
+    o[16] = pl.on_ground ? 1.0f : 0.0f;
+    o[17] = pl.hfj ? 1.0f : 0.0f;
+    o[18] = pl.demoed ? 1.0f : 0.0f;
+}
+
+// DefaultObs::BuildObs (DefaultObs.cpp:19-54) and DefaultObsPadded::BuildObs (DefaultObsPadded.cpp:4-68) of the
+// arena's 4 players into LDS rows packed at stride obs_w (<= RLGPU_OBS, so the 4 rows fit the staging array), on
+// its 16 lanes as advanced_obs_rows deals them: the 19-float player blocks on lanes 4 j + pi, the head, the pads
+// and the padded lists' zero blocks strided.  A row: ball pos / vel / angVel times the coefficients 9, prevAction 8,
+// (float)GetBoostPads(inv)[i] 34, self 19, then the teammate list (maxPlayers - 1 slots) and the opponent list
+// (maxPlayers slots) of 19 floats each; DefaultObs is the padded row of maxPlayers 2 in state.players order.
+// DefaultObsPadded shuffles each list, Fisher-Yates from the back with j = (draw * (i + 1)) >> 32 on draws that are
+// a pure function of (key, global player, tick count, draw index) -- DESIGN.md section 6.16: no draw touches the
+// arena's rng_counter, and a rebuild of the same record gives the same rows.  Not inlined: the step kernels'
+// register budget is the tick loop's, and the AdvancedObs path keeps its code.
+__device__ __noinline__ void default_obs_rows(ArenaLDS* A, const Plugins* B, int l, int arena) {
+    const int w = B->obs_w, mp = B->obs_max_players;
+    float* rows = &A->u.out.obs[0][0];
+    const uint32_t tick = (uint32_t)A->s.env.tick_count;
+    {
+        const int pi = l & 3, j = l >> 2;
+        const bool inv = pi & 1;
+        const int opp = (pi & 1) ^ 1;
+        const int who = j == 0 ? pi : (j == 1 ? pi ^ 2 : (j == 2 ? opp : opp + 2));
+        // the row's two lists after the shuffles: t0 the item at the teammate list's position 0 (item 0 the
+        // teammate, 1 a zero block), o0 / o1 the items at the opponent list's positions 0 and 1 (items 0, 1 the
+        // opponents, 2 a zero block); the last position holds the item that is left
+        int t0 = 0, o0 = 0, o1 = 1;
+        if (B->obs_kind == RLGPU_OBS_DEFAULT_PADDED) {
+            const uint64_t key = (uint64_t)B->obs_key[0] | (uint64_t)B->obs_key[1] << 32;
+            const uint32_t c0 = (uint32_t)arena * 4u + (uint32_t)pi, c1 = tick << 2;
+            if (mp == 3) {
+                if ((((uint64_t)philox0(key, c0, c1 | 0u) * 2u) >> 32) == 0) t0 = 1;  // i = 1
+                const int s = (int)(((uint64_t)philox0(key, c0, c1 | 1u) * 3u) >> 32);  // i = 2
+                if (s == 0) o0 = 2;
+                if (s == 1) o1 = 2;
+            }
+            if ((((uint64_t)philox0(key, c0, c1 | 2u) * 2u) >> 32) == 0) {  // i = 1
+                const int t = o0;
+                o0 = o1;
+                o1 = t;
+            }
+        }
+        int slot = 0;  // the block's 19-float slot after the head: self, teammates, opponents
+        if (j == 1) slot = 1 + (t0 == 0 ? 0 : 1);
+        if (j >= 2) slot = mp + (o0 == j - 2 ? 0 : (o1 == j - 2 ? 1 : 2));
+        add_player_default_obs(rows + pi * w + 51 + 19 * slot, view_player(A, who), inv, B);
+        if (mp == 3 && j < 2) {  // the lists' zero blocks: lane j = 0 the teammates', j = 1 the opponents'
+            const int z = j == 0 ? 1 + (t0 == 1 ? 0 : 1) : mp + (o0 == 2 ? 0 : (o1 == 2 ? 1 : 2));
+            float* o = rows + pi * w + 51 + 19 * z;
+            for (int k = 0; k < 19; k++) o[k] = 0.f;
+        }
+    }
+    // ball and previous action: 4 x 17 elements
+    for (int e = l; e < 4 * 17; e += kTeam) {
+        const int p = e / 17, k = e - 17 * (e / 17);
+        float* o = rows + p * w;
+        if (k < 9) {
+            const int q = k / 3, c = k - 3 * (k / 3);  // q: position, velocity, angular velocity
+            const float* src = q == 0 ? A->s.ball.pos : (q == 1 ? A->s.ball.vel : A->s.ball.angvel);
+            float x = q < 2 ? src[c] * kBT2UU : src[c];
+            if ((p & 1) && c < 2) x = -x;  // inv_if
+            const float sc = q == 0 ? B->obs_pos_coef[c] : (q == 1 ? B->obs_vel_coef : B->obs_ang_vel_coef);
+            o[k] = x * sc;
+        } else {
+            o[k] = A->s.env.prev_action[p][k - 9];
+        }
+    }
+    // boost pads: 4 x 34 elements, the active bit through the pad index map (GameState.cpp:109-126)
+    for (int e = l; e < 4 * RLGPU_PADS; e += kTeam) {
+        const int p = e / RLGPU_PADS, k = e - RLGPU_PADS * (e / RLGPU_PADS);
+        const int idx = (p & 1) ? C.pad_map[RLGPU_PADS - k - 1] : C.pad_map[k];
+        rows[p * w + 17 + k] = A->s.pads[idx].is_active ? 1.0f : 0.0f;
+    }
+}
+
+// The set's obs builder (Plugins::obs_kind, uniform over the launch) and DefaultAction's masks of the arena's 4
+// players into LDS rows; `arena` is the arena's global index.
+DEV void build_obs_rows(ArenaLDS* A, const Plugins* B, int l, int arena) {
+    if (B->obs_kind != RLGPU_OBS_ADVANCED) default_obs_rows(A, B, l, arena);
+    else advanced_obs_rows(A, l);
+    action_mask_rows(A, l);
 }
 
 // KickoffProximityReward2v2Enhanced (KickoffProximityReward2v2Enhanced.h:14-366).  goer = goerReward (:9, used at

@@ -95,6 +95,13 @@ struct Plugins {
     rlgpu_state_setter_spec ss[RLGPU_MAX_STATE_SETTERS];
     float ss_cum[RLGPU_MAX_STATE_SETTERS];
     float ss_total;
+    // the obs builder (rlgpu_envset_config obs_builder ...): its kind (RLGPU_OBS_*), the row width obs_w (the
+    // stride of every obs array of the set and of the rows in LDS), DefaultObsPadded's maxPlayers, DefaultObs's
+    // coefficients and the Philox key of DefaultObsPadded's shuffles.  Per set, not in
+    // EnvConst: the constant buffer is one per device, and sets with different builders live side by side.
+    int obs_kind, obs_w, obs_max_players;
+    float obs_pos_coef[3], obs_vel_coef, obs_ang_vel_coef;
+    uint32_t obs_key[2];  // low, high word
 };
 
 struct WheelT {

@@ -411,12 +411,14 @@ DEV void tick(ArenaLDS* A, const MeshView& M, int l, bool valid, uint64_t seed, 
     P.mark(10);
 }
 
-// copy the 4 obs rows (and mask rows) of this arena from LDS to [players x OBS] outputs
-DEV void copy_rows(ArenaLDS* A, int l, int arena, float* obs, uint8_t* masks) {
+// copy the 4 obs rows (and mask rows) of this arena from LDS to [players x obs_w] outputs (the rows are packed at the
+// set's width in LDS too: one contiguous copy)
+DEV void copy_rows(ArenaLDS* A, const Plugins* B, int l, int arena, float* obs, uint8_t* masks) {
     if (obs) {
+        const int w4 = 4 * B->obs_w;
         const float* src = &A->u.out.obs[0][0];
-        float* dst = obs + (size_t)arena * 4 * RLGPU_OBS;
-        for (int k = l; k < 4 * RLGPU_OBS; k += kTeam) dst[k] = src[k];
+        float* dst = obs + (size_t)arena * w4;
+        for (int k = l; k < w4; k += kTeam) dst[k] = src[k];
     }
     if (masks) {
         const uint8_t* msrc = &A->u.out.masks[0][0];
@@ -460,11 +462,11 @@ __global__ void __launch_bounds__(kWG) RLGPU_ENV_COLLECT_KERNEL(CollectArgs c) {
         StepArgs s = c.g;
         const int64_t tp = (int64_t)t * P;
         s.actions = c.g.actions + tp;
-        if (s.out_obs) s.out_obs = c.g.out_obs + tp * RLGPU_OBS;
+        if (s.out_obs) s.out_obs = c.g.out_obs + tp * c.g.plug->obs_w;
         if (s.out_masks) s.out_masks = c.g.out_masks + tp * RLGPU_ACTIONS;
         if (s.out_rew) s.out_rew = c.g.out_rew + tp;
         if (s.out_term) s.out_term = c.g.out_term + tp;
-        if (s.out_trunc) s.out_trunc = c.g.out_trunc + tp * RLGPU_OBS;
+        if (s.out_trunc) s.out_trunc = c.g.out_trunc + tp * c.g.plug->obs_w;
         // ExampleMain's every-4th-call flag: the set's call counter at launch plus this step (env.hip launch())
         if (s.metrics) s.metrics_players = (c.metric_calls + t + 1) % 4 == 0;
         {

@@ -183,25 +183,25 @@
             A->s.env.last_tick_count = A->s.env.tick_count;
         }
         const bool fused_reset = g.reset_mode == kResetTerminated && valid && term != 0;
-        if (valid) build_obs_rows(A, l);
+        if (valid) build_obs_rows(A, g.plug, l, arena + g.arena_offset);
         sync(); P.mark(13);
         if (valid) {
-            copy_rows(A, l, arena, g.obs, g.masks);
-            if (!fused_reset) copy_rows(A, l, arena, g.out_obs, g.out_masks);
+            copy_rows(A, g.plug, l, arena, g.obs, g.masks);
+            if (!fused_reset) copy_rows(A, g.plug, l, arena, g.out_obs, g.out_masks);
             if (tj == 2) {
-                copy_rows(A, l, arena, g.trunc_obs, nullptr);
-                copy_rows(A, l, arena, g.out_trunc, nullptr);
+                copy_rows(A, g.plug, l, arena, g.trunc_obs, nullptr);
+                copy_rows(A, g.plug, l, arena, g.out_trunc, nullptr);
             }
         }
         sync(); P.mark(13);
         if (g.reset_mode == kResetTerminated) {
             if (fused_reset && l == 0) state_reset(A, g.plug, g.seed, arena + g.arena_offset);
             sync(); P.mark(14);
-            if (fused_reset) build_obs_rows(A, l);
+            if (fused_reset) build_obs_rows(A, g.plug, l, arena + g.arena_offset);
             sync(); P.mark(14);
             if (fused_reset) {
-                copy_rows(A, l, arena, g.obs, g.masks);
-                copy_rows(A, l, arena, g.out_obs, g.out_masks);
+                copy_rows(A, g.plug, l, arena, g.obs, g.masks);
+                copy_rows(A, g.plug, l, arena, g.out_obs, g.out_masks);
             }
             sync(); P.mark(14);
         }
@@ -221,9 +221,9 @@
         }
         sync(); P.mark(14);
         bool rebuild = do_reset || (valid && g.reset_mode == kRebuildObs);
-        if (rebuild) build_obs_rows(A, l);
+        if (rebuild) build_obs_rows(A, g.plug, l, arena + g.arena_offset);
         sync(); P.mark(14);
-        if (rebuild) copy_rows(A, l, arena, g.obs, g.masks);
+        if (rebuild) copy_rows(A, g.plug, l, arena, g.obs, g.masks);
         sync(); P.mark(14);
     }
     // ---- write the records back

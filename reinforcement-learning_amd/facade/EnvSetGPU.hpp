@@ -14,7 +14,7 @@
 //   values (rlgpu_envset_reward_values) and the host values, then written back to state.rewards /
 //   state.terminals.  The fallback is counted (fallbackStats) and announced once on stderr; with no host
 //   plugin nothing crosses the bus.
-// * obs / masks stay on the device (AdvancedObs and DefaultAction are the kernels'); ResetArena re-runs the
+// * obs / masks stay on the device (AdvancedObs / DefaultObs / DefaultObsPadded and DefaultAction are the kernels'); ResetArena re-runs the
 //   host plugins' Reset(initialState) on the arena's new GameState (EnvSet.cpp:275-303).
 //
 // Builds against this repository's RLGC.hpp or, with RLGPU_FACADE_RLGC_HEADER naming a header that pulls in
@@ -66,6 +66,20 @@ struct PluginPlan {
         c.state_setter_flags = stateSetterFlags;
         c.state_setters = stateSetters.empty() ? nullptr : stateSetters.data();
         c.n_state_setters = (int32_t)stateSetters.size();
+    }
+    // EnvCreateResult::obsBuilder: RLGPU_OBS_*, DefaultObsPadded's maxPlayers, DefaultObs's coefficients (posCoef
+    // x, y, z, velCoef, angVelCoef; read for the DefaultObs kinds only) and the row width
+    int32_t obsBuilder = RLGPU_OBS_ADVANCED, obsMaxPlayers = 0;
+    float obsCoef[5] = {0, 0, 0, 0, 0};
+    int obsSize = RLGPU_OBS;
+    // rlgpu_envset_config / rlgpu_learner_config obs builder fields
+    template <class Cfg>
+    void FillObsBuilder(Cfg& c) const {
+        c.obs_builder = obsBuilder;
+        c.obs_max_players = obsMaxPlayers;
+        for (int i = 0; i < 3; i++) c.obs_pos_coef[i] = obsCoef[i];
+        c.obs_vel_coef = obsCoef[3];
+        c.obs_ang_vel_coef = obsCoef[4];
     }
     int NumHostRewards() const {
         int n = 0;
@@ -204,16 +218,35 @@ inline bool SameSpec(const rlgpu_reward_spec& a, const rlgpu_reward_spec& b) {
 }  // namespace detail
 
 // One arena's EnvCreateResult.  Throws std::invalid_argument for what neither side can run: a builder other
-// than AdvancedObs / DefaultAction / the device state setters (the kernels' own), a registry class with a field the
+// than AdvancedObs / DefaultObs / DefaultObsPadded / DefaultAction / the device state setters (the kernels' own), a registry class with a field the
 // registry cannot hold, or lists longer than RLGPU_MAX_REWARDS / RLGPU_MAX_TERMINALS.
 inline PluginPlan TranslatePlugins(const EnvCreateResult& r) {
-    if (r.obsBuilder && typeid(*r.obsBuilder) != typeid(AdvancedObs))
-        throw std::invalid_argument(std::string("EnvCreateResult: obs builder ") + typeid(*r.obsBuilder).name() +
-                                    " (the kernels build AdvancedObs)");
     if (r.actionParser && typeid(*r.actionParser) != typeid(DefaultAction))
         throw std::invalid_argument(std::string("EnvCreateResult: action parser ") + typeid(*r.actionParser).name() +
                                     " (the kernels parse DefaultAction)");
     PluginPlan p;
+    if (r.obsBuilder && typeid(*r.obsBuilder) != typeid(AdvancedObs)) {
+        // the exact class, not a subclass: an override of AddPlayerToObs / BuildObs has no device code
+        const std::type_info& t = typeid(*r.obsBuilder);
+        if (t != typeid(DefaultObs) && t != typeid(DefaultObsPadded))
+            throw std::invalid_argument(std::string("EnvCreateResult: obs builder ") + t.name() +
+                                        " (the kernels build AdvancedObs, DefaultObs and DefaultObsPadded)");
+        auto* d = static_cast<DefaultObs*>(r.obsBuilder);
+        p.obsBuilder = t == typeid(DefaultObsPadded) ? RLGPU_OBS_DEFAULT_PADDED : RLGPU_OBS_DEFAULT;
+        if (p.obsBuilder == RLGPU_OBS_DEFAULT_PADDED) p.obsMaxPlayers = static_cast<DefaultObsPadded*>(d)->maxPlayers;
+        const float c[5] = {d->posCoef.x, d->posCoef.y, d->posCoef.z, d->velCoef, d->angVelCoef};
+        bool zero = true;
+        for (int i = 0; i < 5; i++) {
+            if (!std::isfinite(c[i])) throw std::invalid_argument(std::string("EnvCreateResult: obs builder ") + t.name() + " has a coefficient that is not finite");
+            p.obsCoef[i] = c[i];
+            zero = zero && c[i] == 0.f;
+        }
+        if (zero)
+            throw std::invalid_argument(std::string("EnvCreateResult: obs builder ") + t.name() +
+                                        " has all coefficients zero, which rlgpu_envset_config reads as the defaults");
+        p.obsSize = rlgpu_obs_builder_size(p.obsBuilder, p.obsMaxPlayers);
+        if (p.obsSize < 0) throw std::invalid_argument(std::string("EnvCreateResult: ") + rlgpu_last_error());
+    }
     if (r.stateSetter) {
         const char* const kDevice = " (the kernels reset to KickoffState, FuzzedKickoffState, RandomState or a CombinedState of those)";
         rlgpu_state_setter_spec s{};
@@ -275,6 +308,8 @@ inline void RequireSamePlan(const PluginPlan& a, const PluginPlan& b, int index)
     bool same = a.rewardSlot == b.rewardSlot && a.hostTerminals == b.hostTerminals && a.stateSetter == b.stateSetter &&
                 a.deviceRewards.size() == b.deviceRewards.size() && a.deviceTerminals.size() == b.deviceTerminals.size();
     same = same && a.stateSetterFlags == b.stateSetterFlags && a.stateSetters.size() == b.stateSetters.size();
+    same = same && a.obsBuilder == b.obsBuilder && a.obsMaxPlayers == b.obsMaxPlayers;
+    for (int i = 0; same && i < 5; i++) same = a.obsCoef[i] == b.obsCoef[i];
     for (size_t i = 0; same && i < a.stateSetters.size(); i++)
         same = a.stateSetters[i].type == b.stateSetters[i].type && a.stateSetters[i].weight == b.stateSetters[i].weight &&
                a.stateSetters[i].flags == b.stateSetters[i].flags;
@@ -461,8 +496,10 @@ class EnvSetGPU {
         cfg.arith = o.arith;
         cfg.arena_offset = o.arenaOffset;
         plan.FillStateSetter(cfg);
+        plan.FillObsBuilder(cfg);
         RlgpuCheck(rlgpu_envset_create(&cfg, &h), "EnvSet");
         RlgpuCheck(rlgpu_envset_buffers_get(h, &state), "EnvSet buffers");
+        obsSize = plan.obsSize;
         InitHost();
     }
     // Attached to a device env set made by someone else from this plan's registry lists (the trainer facade: the
@@ -473,6 +510,8 @@ class EnvSetGPU {
         if (!h) throw std::invalid_argument("EnvSetGPU: null env set to attach to");
         RlgpuCheck(rlgpu_envset_buffers_get(h, &state), "EnvSet buffers");
         if (state.num_arenas != c.numArenas) throw std::invalid_argument("EnvSetGPU: attached env set has another arena count");
+        obsSize = plan.obsSize;
+        if (rlgpu_envset_obs_size(h) != obsSize) throw std::invalid_argument("EnvSetGPU: attached env set has another obs builder");
         InitHost();
     }
 

@@ -601,6 +601,9 @@ class PolicyVersionManager {
     void LoadRunningStatsFromJSON(const detail::Json& j) {
         if (skillConfig.enabled && j.Has("skill_ratings")) curRatings.ReadFromJSON(j["skill_ratings"]);
     }
+    // the skill env set's row width (0 without one) and the env steps its matches have run so far
+    int SkillObsSize() const { return skillEnv ? rlgpu_envset_obs_size(skillEnv) : 0; }
+    uint64_t SkillSteps() const { return skillSteps; }
 
   private:
     Learner* L;
@@ -822,6 +825,8 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
         c.mesh_object_ntris = meshObjects_.data();
     }
     plan.FillStateSetter(c);
+    plan.FillObsBuilder(c);
+    obsSize = plan.obsSize;
     RLGC::RlgpuCheck(rlgpu_learner_create(&c, options.world > 1 ? options.collective : nullptr, stream_, &h_), "Learner");
     rlgpu_envset* env = nullptr;
     RLGC::RlgpuCheck(rlgpu_learner_handles(h_, &env, &ppo_), "Learner handles");
@@ -829,7 +834,7 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
     if (plan.HasHost() || stepCallback) RLGC::RlgpuCheck(rlgpu_learner_set_step_hook(h_, &Learner::HookThunk, this), "step hook");
 
     // the PPO handle's models (PPOLearner::MakeModels): shared head feeds policy and critic
-    const int feat = c.n_shared_layers ? config.ppo.sharedHead.layerSizes.back() : RLGPU_OBS;
+    const int feat = c.n_shared_layers ? config.ppo.sharedHead.layerSizes.back() : obsSize;
     const bool ln = c.no_layer_norm == 0;
     const char* an = at == ModelActivationType::RELU      ? "relu"
                      : at == ModelActivationType::SIGMOID ? "sigmoid"
@@ -837,7 +842,7 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
                                                           : "leaky_relu";
     models.push_back({0, "policy", feat, RLGPU_ACTIONS, config.ppo.policy.layerSizes, ln, an});
     models.push_back({1, "critic", feat, 1, config.ppo.critic.layerSizes, ln, an});
-    if (c.n_shared_layers) models.push_back({2, "shared_head", RLGPU_OBS, 0, config.ppo.sharedHead.layerSizes, ln, an});
+    if (c.n_shared_layers) models.push_back({2, "shared_head", obsSize, 0, config.ppo.sharedHead.layerSizes, ln, an});
     std::printf("Model parameter counts:\n");
     int64_t total = 0;
     for (int m : {0, 1, 2}) {
@@ -1026,17 +1031,35 @@ inline void Learner::FinishReport(Report& report, const rlgpu_learner_report& re
 inline rlgpu_ppo* Learner::MakeTeacher(const TransferLearnConfig& tl) const {
     auto bad = [](const std::string& what) { throw std::invalid_argument("TransferLearnConfig: " + what); };
     // what remains for anything but the engine's own builder / parser: their host-side evaluation per player and step
-    static const char* kGap = ": the engine evaluates the old obs builder, action parser and action map only as its own "
-                              "AdvancedObs / DefaultAction without a map; what remains is the host-side evaluation of the old "
+    static const char* kGap = ": the engine evaluates the old obs builder, action parser and action map only as the env's own "
+                              "obs builder / DefaultAction without a map; what remains is the host-side evaluation of the old "
                               "builders (the C ABI, rlgpu_ppo_teacher_probs, already takes teacher rows and maps)";
     if (tl.mapActsFn) throw std::runtime_error(std::string("GGL::Learner::StartTransferLearn: mapActsFn is set") + kGap);
     if (!tl.makeOldObsFn || !tl.makeOldActFn) bad("makeOldObsFn and makeOldActFn must be set");
     {
         std::unique_ptr<RLGC::ObsBuilder> ob(tl.makeOldObsFn());
         std::unique_ptr<RLGC::ActionParser> ap(tl.makeOldActFn());
-        if (!ob || typeid(*ob) != typeid(RLGC::AdvancedObs))
+        // the teacher reads the rollout's own rows: its builder must be the env's (class, maxPlayers, coefficients).  A
+        // class without device code is refused with the gap's message, before anything is translated
+        const auto refuse = [&](const char* why) {
             throw std::runtime_error(std::string("GGL::Learner::StartTransferLearn: old obs builder ") +
-                                     (ob ? typeid(*ob).name() : "(null)") + kGap);
+                                     (ob ? typeid(*ob).name() : "(null)") + why + kGap);
+        };
+        if (!ob || (typeid(*ob) != typeid(RLGC::AdvancedObs) && typeid(*ob) != typeid(RLGC::DefaultObs) &&
+                    typeid(*ob) != typeid(RLGC::DefaultObsPadded)))
+            refuse("");
+        RLGC::EnvCreateResult oldEnv;
+        oldEnv.obsBuilder = ob.get();
+        RLGC::PluginPlan o;
+        try {
+            o = RLGC::TranslatePlugins(oldEnv);
+        } catch (const std::invalid_argument& e) {  // a refused maxPlayers or coefficient
+            refuse((std::string(" (") + e.what() + ")").c_str());
+        }
+        const RLGC::PluginPlan& e = envSet->plan;
+        bool sameObs = o.obsBuilder == e.obsBuilder && o.obsMaxPlayers == e.obsMaxPlayers;
+        for (int i = 0; sameObs && i < 5; i++) sameObs = o.obsCoef[i] == e.obsCoef[i];
+        if (!sameObs) refuse(" is not the env's");
         if (!ap || typeid(*ap) != typeid(RLGC::DefaultAction))
             throw std::runtime_error(std::string("GGL::Learner::StartTransferLearn: old action parser ") +
                                      (ap ? typeid(*ap).name() : "(null)") + kGap);
@@ -1074,9 +1097,9 @@ inline rlgpu_ppo* Learner::MakeTeacher(const TransferLearnConfig& tl) const {
                          : at == ModelActivationType::SIGMOID ? "sigmoid"
                          : at == ModelActivationType::TANH    ? "tanh"
                                                               : "leaky_relu";
-        const int feat = sh ? os.layerSizes.back() : RLGPU_OBS;
+        const int feat = sh ? os.layerSizes.back() : obsSize;
         std::vector<ModelSpec> old{{0, "policy", feat, RLGPU_ACTIONS, op.layerSizes, op.addLayerNorm, an}};
-        if (sh) old.push_back({2, "shared_head", RLGPU_OBS, 0, os.layerSizes, op.addLayerNorm, an});
+        if (sh) old.push_back({2, "shared_head", obsSize, 0, os.layerSizes, op.addLayerNorm, an});
         float* params = nullptr;
         RLGC::RlgpuCheck(rlgpu_ppo_buffers(t, &params, nullptr, nullptr), "teacher buffers");
         for (const ModelSpec& m : old) {  // Model::Load with allowNotExist = false
@@ -1214,7 +1237,7 @@ inline void Learner::SaveStats(const std::filesystem::path& path) {
              ", \"count\": " + std::to_string(st.return_n) + "}";
     if (config.standardizeObs) {  // BatchedWelfordStat::ToJSON (Learner.cpp:184-185): vars = the running m2
         int64_t n = 0;
-        std::vector<double> mean(RLGPU_OBS), m2(RLGPU_OBS);
+        std::vector<double> mean(obsSize), m2(obsSize);
         RLGC::RlgpuCheck(rlgpu_learner_get_obs_stat(h_, &n, mean.data(), m2.data()), "obs stat");
         auto list = [](const std::vector<double>& v) {
             std::string o = "[";
@@ -1250,8 +1273,8 @@ inline void Learner::LoadStats(const std::filesystem::path& path) {
         std::vector<double> mean, m2;
         for (auto& x : o["means"].arr) mean.push_back(x.Num());
         for (auto& x : o["vars"].arr) m2.push_back(x.Num());
-        if (mean.size() != (size_t)RLGPU_OBS || m2.size() != (size_t)RLGPU_OBS)
-            throw std::runtime_error(path.string() + ": obs_stat does not hold " + std::to_string(RLGPU_OBS) + " means and vars");
+        if (mean.size() != (size_t)obsSize || m2.size() != (size_t)obsSize)
+            throw std::runtime_error(path.string() + ": obs_stat does not hold " + std::to_string(obsSize) + " means and vars");
         RLGC::RlgpuCheck(rlgpu_learner_set_obs_stat(h_, o["count"].Int(), mean.data(), m2.data()), "obs stat");
     }
     if (versionMgr) versionMgr->LoadRunningStatsFromJSON(j);
@@ -1480,6 +1503,7 @@ inline PolicyVersionManager::PolicyVersionManager(Learner* learner, std::filesys
         ec.n_terminals = 1;
         ec.arith = L->options.arith;
         ec.state_setter = RLGPU_SS_FUZZED_KICKOFF;
+        L->envSet->plan.FillObsBuilder(ec);  // the policies' inputs: the training arenas' builder and width
         if (!L->meshTris_.empty()) {
             ec.mesh_tris = L->meshTris_.data();
             ec.mesh_ntris = (int32_t)(L->meshTris_.size() / 9);
@@ -1487,6 +1511,9 @@ inline PolicyVersionManager::PolicyVersionManager(Learner* learner, std::filesys
             ec.mesh_object_ntris = L->meshObjects_.data();
         }
         RLGC::RlgpuCheck(rlgpu_envset_create(&ec, &skillEnv), "skill env set");
+        if (rlgpu_envset_obs_size(skillEnv) != L->obsSize)
+            throw std::logic_error("skill env set: obs rows of " + std::to_string(rlgpu_envset_obs_size(skillEnv)) +
+                                   " floats, the policy reads " + std::to_string(L->obsSize));
         const int P = 4 * skillConfig.numArenas;
         detail::HipOk(hipMalloc(&dSkillActs, (size_t)P * 4), "skill actions");
         detail::HipOk(hipMalloc(&dOldRows, (size_t)P), "skill rows");

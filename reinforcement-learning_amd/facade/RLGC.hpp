@@ -421,7 +421,25 @@ class StateSetter {
     virtual ~StateSetter() {}
 };
 class AdvancedObs : public ObsBuilder {};
-class DefaultObs : public ObsBuilder {};        // RG/ObsBuilders/DefaultObs.h (declared; the kernels build AdvancedObs)
+// RG/ObsBuilders/DefaultObs.h (RLGPU_OBS_DEFAULT): the constructor's defaults are 1 / CommonValues::SIDE_WALL_X,
+// BACK_WALL_Y, CEILING_Z, CAR_MAX_SPEED and CAR_MAX_ANG_VEL.  The row is built on the device; a subclass (an
+// AddPlayerToObs override) has no device code and is refused by name.
+class DefaultObs : public ObsBuilder {
+  public:
+    Vec posCoef;
+    float velCoef, angVelCoef;
+    DefaultObs(Vec posCoef = Vec(1 / 4096.f, 1 / 5120.f, 1 / 2044.f), float velCoef = 1 / 2300.f, float angVelCoef = 1 / 5.5f)
+        : posCoef(posCoef), velCoef(velCoef), angVelCoef(angVelCoef) {}
+};
+// RG/ObsBuilders/DefaultObsPadded.h (RLGPU_OBS_DEFAULT_PADDED): maxPlayers - 1 teammate and maxPlayers opponent
+// slots, each list shuffled per row (every order equally likely; not std::shuffle's own permutations)
+class DefaultObsPadded : public DefaultObs {
+  public:
+    int maxPlayers;
+    DefaultObsPadded(int maxPlayers, Vec posCoef = Vec(1 / 4096.f, 1 / 5120.f, 1 / 2044.f), float velCoef = 1 / 2300.f,
+                     float angVelCoef = 1 / 5.5f)
+        : DefaultObs(posCoef, velCoef, angVelCoef), maxPlayers(maxPlayers) {}
+};
 class DefaultAction : public ActionParser {};
 class KickoffState : public StateSetter {};
 class RandomState : public StateSetter {        // RG/StateSetters/RandomState.h (RLGPU_SS_RANDOM)

@@ -23,6 +23,7 @@
 //               [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] [--self-play] [--fp32-inference]
 //               [--policy-temperature X] [--mask-entropy] [--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm]
 //               [--guiding-policy DIR [--guiding-strength X]] [--state-setter kickoff|random|combined:K:R]
+//               [--obs advanced|default|padded:N] [--skill-tracker N:T]
 //               [--rank r --world N --rccl-id FILE [--rccl-nonce STR]]
 #include <execinfo.h>
 #include <signal.h>
@@ -52,6 +53,24 @@ static void ParseStateSetter(const char* v) {
     else throw std::invalid_argument(std::string("--state-setter ") + v + " (kickoff, random or combined:K:R)");
 }
 
+static int gObs = 0, gObsMaxPlayers = 0;  // --obs: 0 advanced, 1 default, 2 padded:N
+
+static void ParseObs(const char* v) {
+    int n = 0, end = 0;
+    gObsMaxPlayers = 0;  // the last --obs holds alone
+    if (!std::strcmp(v, "advanced")) gObs = 0;
+    else if (!std::strcmp(v, "default")) gObs = 1;
+    else if (std::sscanf(v, "padded:%d%n", &n, &end) == 1 && v[end] == '\0') {  // the whole value, nothing after N
+        gObs = 2;
+        gObsMaxPlayers = n;
+    } else throw std::invalid_argument(std::string("--obs ") + v + " (advanced, default or padded:N)");
+}
+static ObsBuilder* MakeObs() {  // --obs: AdvancedObs (ExampleMain's), DefaultObs() or DefaultObsPadded(N)
+    if (gObs == 1) return new DefaultObs();
+    if (gObs == 2) return new DefaultObsPadded(gObsMaxPlayers);
+    return new AdvancedObs();
+}
+
 // src/ExampleMain.cpp:128-226 with registry classes only
 static EnvCreateResult EnvCreateFunc(int) {
     std::vector<WeightedReward> rewards = {
@@ -78,7 +97,7 @@ static EnvCreateResult EnvCreateFunc(int) {
         r.arena->AddCar(Team::ORANGE);
     }
     r.actionParser = new DefaultAction();
-    r.obsBuilder = new AdvancedObs();
+    r.obsBuilder = MakeObs();
     // --state-setter: kickoff (ExampleMain's), random = RandomState(true, true, false), or combined:K:R =
     // CombinedState{{KickoffState, K}, {RandomState(true, true, false), R}}
     if (gStateSetter == 1) r.stateSetter = new RandomState(true, true, false);
@@ -171,7 +190,7 @@ int main(int argc, char** argv) {
     // --transfer-learn DIR: Learner::StartTransferLearn from DIR's POLICY.lt (+ SHARED_HEAD.lt) instead of the PPO loop
     bool transferLearn = false, tlMapActs = false;
     TransferLearnConfig tl;
-    tl.makeOldObsFn = [] { return new AdvancedObs(); };
+    tl.makeOldObsFn = [] { return MakeObs(); };  // the teacher reads the env's rows
     tl.makeOldActFn = [] { return new DefaultAction(); };
     tl.oldPolicyConfig.layerSizes = {512, 512};
     auto intList = [](const std::string& v) {
@@ -203,6 +222,15 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(argv[i], "--policy-temperature")) cfg.ppo.policyTemperature = std::strtof(next(), nullptr);
             else if (!std::strcmp(argv[i], "--mask-entropy")) cfg.ppo.maskEntropy = true;
             else if (!std::strcmp(argv[i], "--state-setter")) ParseStateSetter(next());
+            else if (!std::strcmp(argv[i], "--obs")) ParseObs(next());
+            else if (!std::strcmp(argv[i], "--skill-tracker")) {  // LearnerConfig::skillTracker: N arenas, T s per run, every iteration
+                const char* v = next();
+                int end = 0;
+                if (std::sscanf(v, "%d:%f%n", &cfg.skillTracker.numArenas, &cfg.skillTracker.simTime, &end) != 2 || v[end] != '\0')
+                    throw std::invalid_argument(std::string("--skill-tracker ") + v + " (N:T, arenas and seconds per run)");
+                cfg.skillTracker.enabled = true;
+                cfg.skillTracker.updateInterval = 1;
+            }
             else if (!std::strcmp(argv[i], "--standardize-obs")) cfg.standardizeObs = true;  // LearnerConfig::standardizeObs
             else if (!std::strcmp(argv[i], "--min-obs-std")) cfg.minObsSTD = std::strtof(next(), nullptr);
             else if (!std::strcmp(argv[i], "--guiding-policy")) {  // PPOLearnerConfig::useGuidingPolicy / guidingPolicyPath
@@ -247,7 +275,7 @@ int main(int argc, char** argv) {
                                  "[--c2-model] [--seed S] [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] "
                                  "[--self-play] [--fp32-inference] [--policy-temperature X] [--mask-entropy] "
                                  "[--standardize-obs [--min-obs-std X]] [--state-setter kickoff|random|combined:K:R] "
-                                 "[--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm] [--guiding-policy DIR "
+                                 "[--obs advanced|default|padded:N] [--skill-tracker N:T] [--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm] [--guiding-policy DIR "
                                  "[--guiding-strength X]] [--transfer-learn DIR [--old-policy-layers a,b,..] [--old-shared-layers a,b,..] "
                                  "[--tl-lr X] [--tl-epochs N] [--tl-kl] [--tl-loss-scale X] [--tl-loss-exponent X] [--tl-map-acts]] "
                                  "[--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);
@@ -314,6 +342,9 @@ int main(int argc, char** argv) {
                                 report["Consumption Time"] - report["PPO Learn Time"], report["PPO Learn Time"],
                                 (unsigned long long)learner.totalTimesteps);
                     if (cfg.ppo.useGuidingPolicy) std::printf("  Guiding Loss: %.6g\n", report["Guiding Loss"]);
+                    if (learner.versionMgr && learner.versionMgr->SkillObsSize())  // the ELO matches against old versions
+                        std::printf("  Skill matches: %llu env steps so far on obs rows of %d floats\n",
+                                    (unsigned long long)learner.versionMgr->SkillSteps(), learner.versionMgr->SkillObsSize());
                     // the StepCallback's report (ExampleMain.cpp:233-283) over this iteration, from the device
                     double tot[RLGPU_NUM_STEP_METRICS];
                     uint64_t cnt[RLGPU_NUM_STEP_METRICS];

@@ -18,7 +18,7 @@
 #include "cu_partition.hpp"
 
 namespace {
-constexpr int OBS = RLGPU_OBS, ACT = RLGPU_ACTIONS;
+constexpr int ACT = RLGPU_ACTIONS;
 using clk = std::chrono::steady_clock;
 double secs(clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); }
 
@@ -224,7 +224,13 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     ec.state_setter_flags = cfg.state_setter_flags;
     ec.state_setters = cfg.state_setters;
     ec.n_state_setters = cfg.n_state_setters;
+    ec.obs_builder = cfg.obs_builder;
+    ec.obs_max_players = cfg.obs_max_players;
+    std::memcpy(ec.obs_pos_coef, cfg.obs_pos_coef, sizeof ec.obs_pos_coef);
+    ec.obs_vel_coef = cfg.obs_vel_coef;
+    ec.obs_ang_vel_coef = cfg.obs_ang_vel_coef;
     env_ = std::make_unique<RLGC::EnvSetGPU>(ec, s_);
+    OBS_ = rlgpu_envset_obs_size(env_->handle());  // the obs builder's row width
     // ExampleMain registers its StepCallback (ExampleMain.cpp:233-283, 592): restated on the device
     RlgpuCheck(rlgpu_envset_enable_step_metrics(env_->handle(), 1), "step metrics");
     // the rollout rows are the only obs / masks the Learner reads after a fused step (the stacked-frame and
@@ -232,7 +238,7 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     RlgpuCheck(rlgpu_envset_set_output_only(env_->handle(), 1), "output-only rows");
     K_ = cfg.frame_stack > 1 ? cfg.frame_stack : 1;
     RLGPU_REQUIRE(K_ <= 16, "Learner: frame_stack must be <= 16");
-    const int W = OBS * K_;
+    const int W = OBS_ * K_;
     rlgpu_ppo_config pc{};
     pc.obs_size = W;
     pc.num_actions = ACT;
@@ -311,10 +317,10 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     // rollout row 0 = the env's initial obs (stacked: the first frame repeated) / masks
     const rlgpu_envset_buffers& st = env_->state();
     if (K_ > 1) {
-        hist_.Reserve((int64_t)(K_ - 1) * P * OBS, s_);
-        lk::stack_frames(st.obs, nullptr, nullptr, hist_.p, K_, P, OBS, exp_.v.obs, nullptr, s_);
+        hist_.Reserve((int64_t)(K_ - 1) * P * OBS_, s_);
+        lk::stack_frames(st.obs, nullptr, nullptr, hist_.p, K_, P, OBS_, exp_.v.obs, nullptr, s_);
     } else {
-        hipCheck(hipMemcpyAsync(exp_.v.obs, st.obs, (size_t)P * OBS * 4, hipMemcpyDeviceToDevice, s_), "obs0");
+        hipCheck(hipMemcpyAsync(exp_.v.obs, st.obs, (size_t)P * OBS_ * 4, hipMemcpyDeviceToDevice, s_), "obs0");
     }
     hipCheck(hipMemcpyAsync(exp_.v.masks, st.action_masks, (size_t)P * ACT, hipMemcpyDeviceToDevice, s_), "masks0");
     // self-play team masks (team of player p is p % 2)
@@ -436,8 +442,8 @@ void Learner::CollectGrouped(int G) {
                                                     cfg_.deterministic != 0, (uint64_t)stats.rng_step,
                                                     old ? old + p0 : nullptr, v.actions + a, v.logp + a, gs_[g]),
                        "InferActions (group)");
-            rlgpu_step_outputs o{v.obs + (a + P) * OBS, v.masks + (a + P) * ACT, v.rewards + a, v.terms + a,
-                                 v.trunc_obs + a * OBS};
+            rlgpu_step_outputs o{v.obs + (a + P) * OBS_, v.masks + (a + P) * ACT, v.rewards + a, v.terms + a,
+                                 v.trunc_obs + a * OBS_};
             if (envTiming_) hipCheck(hipEventRecord(ev_[2 * ((size_t)t * G + g)], gs_[g]), "event");
             RlgpuCheck(rlgpu_envset_step_range(eh, g * Na, Na, v.actions + a, 1, &o, gs_[g]), "EnvSet step (group)");
             if (envTiming_) hipCheck(hipEventRecord(ev_[2 * ((size_t)t * G + g) + 1], gs_[g]), "event");
@@ -510,7 +516,7 @@ void Learner::Collect() {
     if (envTiming_) EnsureEvents((size_t)2 * T);
     for (int t = 0; t < T; t++) {
         const size_t r = (size_t)t * P;
-        ActAndStep(r, r + P, v.trunc_obs + r * OBS, v.trunc_obs + r * W, envTiming_ ? &ev_[2 * t] : nullptr);
+        ActAndStep(r, r + P, v.trunc_obs + r * OBS_, v.trunc_obs + r * W, envTiming_ ? &ev_[2 * t] : nullptr);
     }
 }
 
@@ -526,24 +532,24 @@ void Learner::ActAndStep(size_t row, size_t next, float* trunc, float* truncStac
     ppo_->InferActions(v.obs + row * W, v.masks + row * ACT, P, cfg_.deterministic != 0, (uint64_t)stats.rng_step,
                        v.actions + row, v.logp + row, OldRows());
     stats.rng_step++;
-    rlgpu_step_outputs o{K_ > 1 ? nullptr : v.obs + next * OBS, v.masks + next * ACT, v.rewards + row, v.terms + row,
+    rlgpu_step_outputs o{K_ > 1 ? nullptr : v.obs + next * OBS_, v.masks + next * ACT, v.rewards + row, v.terms + row,
                          K_ > 1 ? nullptr : trunc};
     if (timing) hipCheck(hipEventRecord(timing[0], s_), "event");
     StepEnv(v.actions + row, o);
     if (timing) hipCheck(hipEventRecord(timing[1], s_), "event");
-    if (K_ > 1) lk::stack_frames(st.obs, st.trunc_obs, v.terms + row, hist_.p, K_, P, OBS, v.obs + next * W, truncStacked, s_);
+    if (K_ > 1) lk::stack_frames(st.obs, st.trunc_obs, v.terms + row, hist_.p, K_, P, OBS_, v.obs + next * W, truncStacked, s_);
     // the appended row is the next step's policy input (the fused step holds the reset): the reference's "top of the
     // next step".  The pre-reset rows (`trunc`) stay raw, as traj.nextStates do (Learner.cpp:855-858)
     if (obsStd_) StandardizeObs(v.obs + next * W);
 }
 
-// One step of Learner.cpp:679-693 on [P][OBS] rows in place, two launches on s_: the statistic's increment from
+// One step of Learner.cpp:679-693 on [P][OBS_] rows in place, two launches on s_: the statistic's increment from
 // min(P, maxObsSamples) drawn rows (one workgroup; it leaves the coefficient table), then the row rewrite.
 void Learner::StandardizeObs(float* d_rows) {
     const int P = exp_.P;
-    lk::obs_stat_update(obsStat_.p, d_rows, P, OBS, std::min(P, obsSamples_), lk::obs_stat_key(cfg_.seed), obsMeanRange_,
+    lk::obs_stat_update(obsStat_.p, d_rows, P, OBS_, std::min(P, obsSamples_), lk::obs_stat_key(cfg_.seed), obsMeanRange_,
                         obsMinStd_, s_);
-    lk::obs_standardize_rows(d_rows, (int64_t)P * OBS, OBS, obsStat_.p, s_);
+    lk::obs_standardize_rows(d_rows, (int64_t)P * OBS_, OBS_, obsStat_.p, s_);
 }
 
 void Learner::SetObsStandardization(bool enable, float minStd, float maxMeanRange, int maxSamples) {
@@ -564,7 +570,7 @@ void Learner::SetObsStandardization(bool enable, float minStd, float maxMeanRang
     if (cfg_.world > 1)
         throw rlgpu::Error(RLGPU_ERR_UNSUPPORTED, "Learner: standardize_obs with world > 1 is not supported (per-rank "
                                                   "statistics would diverge)");
-    obsStat_.Reserve((int64_t)lk::obs_stat_bytes(OBS), s_, false, true);  // zero-filled: a fresh BatchedWelfordStat
+    obsStat_.Reserve((int64_t)lk::obs_stat_bytes(OBS_), s_, false, true);  // zero-filled: a fresh BatchedWelfordStat
     obsMinStd_ = minStd;
     obsMeanRange_ = maxMeanRange;
     obsSamples_ = maxSamples;
@@ -573,12 +579,12 @@ void Learner::SetObsStandardization(bool enable, float minStd, float maxMeanRang
 
 void Learner::GetObsStat(int64_t* count, double* means, double* m2s) {
     if (!obsStd_) throw rlgpu::Error(RLGPU_ERR_STATE, "Learner: obs standardisation is not enabled");
-    std::vector<char> h(8 + 16 * (size_t)OBS);
+    std::vector<char> h(8 + 16 * (size_t)OBS_);
     hipCheck(hipMemcpyAsync(h.data(), obsStat_.p, h.size(), hipMemcpyDeviceToHost, s_), "obs stat");
     hipCheck(hipStreamSynchronize(s_), "sync");
     if (count) std::memcpy(count, h.data(), 8);
-    if (means) std::memcpy(means, h.data() + 8, 8 * (size_t)OBS);
-    if (m2s) std::memcpy(m2s, h.data() + 8 + 8 * (size_t)OBS, 8 * (size_t)OBS);
+    if (means) std::memcpy(means, h.data() + 8, 8 * (size_t)OBS_);
+    if (m2s) std::memcpy(m2s, h.data() + 8 + 8 * (size_t)OBS_, 8 * (size_t)OBS_);
 }
 
 void Learner::SetObsStat(int64_t count, const double* means, const double* m2s) {
@@ -586,10 +592,10 @@ void Learner::SetObsStat(int64_t count, const double* means, const double* m2s) 
     if (collected_)
         throw rlgpu::Error(RLGPU_ERR_STATE, "Learner: the obs statistic cannot be set after the first collection");
     RLGPU_REQUIRE(count >= 0 && means && m2s, "Learner: obs statistic: count must be >= 0, means / m2s non-null");
-    std::vector<char> h(8 + 16 * (size_t)OBS);
+    std::vector<char> h(8 + 16 * (size_t)OBS_);
     std::memcpy(h.data(), &count, 8);
-    std::memcpy(h.data() + 8, means, 8 * (size_t)OBS);
-    std::memcpy(h.data() + 8 + 8 * (size_t)OBS, m2s, 8 * (size_t)OBS);
+    std::memcpy(h.data() + 8, means, 8 * (size_t)OBS_);
+    std::memcpy(h.data() + 8 + 8 * (size_t)OBS_, m2s, 8 * (size_t)OBS_);
     hipCheck(hipMemcpyAsync(obsStat_.p, h.data(), h.size(), hipMemcpyHostToDevice, s_), "obs stat");
     hipCheck(hipStreamSynchronize(s_), "sync");
 }
@@ -622,12 +628,12 @@ void Learner::StepEnv(const int32_t* d_actions, const rlgpu_step_outputs& o) {
     hipCheck(hipStreamSynchronize(s_), "sync");
     if (hook_(hookUser_, RLGPU_HOOK_AFTER_STEP) != 0)
         throw rlgpu::Error(RLGPU_ERR_STATE, std::string("Learner: step hook failed: ") + rlgpu_last_error());
-    lk::host_step_finish(st.terminals, o.terminals, st.rewards, o.rewards, st.obs, st.trunc_obs, o.trunc_obs, P, OBS, s_);
+    lk::host_step_finish(st.terminals, o.terminals, st.rewards, o.rewards, st.obs, st.trunc_obs, o.trunc_obs, P, OBS_, s_);
     RlgpuCheck(rlgpu_envset_reset(e, s_), "EnvSet reset (hooked)");
     hipCheck(hipStreamSynchronize(s_), "sync");
     if (hook_(hookUser_, RLGPU_HOOK_AFTER_RESET) != 0)
         throw rlgpu::Error(RLGPU_ERR_STATE, std::string("Learner: step hook failed: ") + rlgpu_last_error());
-    if (o.obs) hipCheck(hipMemcpyAsync(o.obs, st.obs, (size_t)P * OBS * 4, hipMemcpyDeviceToDevice, s_), "obs append");
+    if (o.obs) hipCheck(hipMemcpyAsync(o.obs, st.obs, (size_t)P * OBS_ * 4, hipMemcpyDeviceToDevice, s_), "obs append");
     if (o.masks) hipCheck(hipMemcpyAsync(o.masks, st.action_masks, (size_t)P * ACT, hipMemcpyDeviceToDevice, s_), "mask append");
 }
 

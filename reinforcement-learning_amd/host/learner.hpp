@@ -118,7 +118,7 @@ struct PinnedFree {
 // = the state the step at row r acted on) and the outputs (values, GAE, truncation rows) live in the
 // combined batch instead (rollout_outputs = false).
 struct ExperienceBuffer {
-    int T = 0, P = 0, W = 0;  // W: obs row width (RLGPU_OBS x frames)
+    int T = 0, P = 0, W = 0;  // W: obs row width (the env set's obs width x frames)
     rlgpu_rollout_view v{};  // views of the arrays below
     DevArray<float> obs, logp, rewards, truncObs, values, truncVals, adv, target, ret;
     DevArray<uint8_t> masks;
@@ -223,7 +223,7 @@ public:
     // the policy sees first increments a BatchedWelfordStat from min(P, maxSamples) drawn rows and is then rewritten in
     // place; the truncation rows stay raw, as in the reference.  Before the first collection only.
     void SetObsStandardization(bool enable, float minStd, float maxMeanRange, int maxSamples);
-    void GetObsStat(int64_t* count, double* means, double* m2s);  // [OBS] each; synchronises
+    void GetObsStat(int64_t* count, double* means, double* m2s);  // [obs width] each; synchronises
     void SetObsStat(int64_t count, const double* means, const double* m2s);
 
     const rlgpu_learner_config& config() const { return cfg_; }
@@ -260,15 +260,16 @@ private:
     rlgpu_grad_hook_fn gradHook_ = nullptr;
     void* gradHookUser_ = nullptr;
     int K_ = 1;                 // frames stacked (config C4)
-    DevArray<float> hist_;      // [K-1][P][OBS] frame history
+    int OBS_ = RLGPU_OBS;       // the env set's obs row width (its obs builder's; a rollout row is OBS_ x K_ wide)
+    DevArray<float> hist_;      // [K-1][P][OBS_] frame history
     // obs standardisation: the statistic and the coefficient table it yields, in one block (empty while off)
-    DevArray<char> obsStat_;    // lk::obs_stat_bytes(OBS): count, means, m2, then coef [2][OBS] and the active word
+    DevArray<char> obsStat_;    // lk::obs_stat_bytes(OBS_): count, means, m2, then coef [2][OBS_] and the active word
     bool obsStd_ = false;
     bool row0Raw_ = false;      // rollout / store row 0 still holds the env's raw initial obs
     bool collected_ = false;    // the first collection has started
     float obsMinStd_ = 0.1f, obsMeanRange_ = 3.f;
     int obsSamples_ = 100;
-    void StandardizeObs(float* d_rows);  // one reference step on [P][OBS] rows: increment, then normalise
+    void StandardizeObs(float* d_rows);  // one reference step on [P][OBS_] rows: increment, then normalise
     std::vector<hipEvent_t> ev_;
     // the rollout collection in arena groups (rlgpu_learner_config.collect_groups): one stream per group, each on
     // its own CU partition (host/cu_partition.hpp), joined to s_ by events at the phase's start and end

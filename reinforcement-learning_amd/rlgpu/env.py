@@ -29,9 +29,11 @@ class _Config(ctypes.Structure):
                 ("mesh_tris", ctypes.c_void_p), ("mesh_ntris", ctypes.c_int32), ("mesh_objects", ctypes.c_int32),
                 ("mesh_object_ntris", ctypes.c_void_p), ("rewards", ctypes.c_void_p), ("n_rewards", ctypes.c_int32),
                 ("terminals", ctypes.c_void_p), ("n_terminals", ctypes.c_int32), ("arith", ctypes.c_int32),
-                ("arena_offset", ctypes.c_int32), ("state_setter", ctypes.c_int32),
-                ("state_setter_flags", ctypes.c_int32), ("state_setters", ctypes.c_void_p),
-                ("n_state_setters", ctypes.c_int32)]
+                ("arena_offset", ctypes.c_int32), ("obs_builder", ctypes.c_int32),
+                ("obs_max_players", ctypes.c_int32), ("obs_pos_coef", ctypes.c_float * 3),
+                ("obs_vel_coef", ctypes.c_float), ("obs_ang_vel_coef", ctypes.c_float),
+                ("state_setter", ctypes.c_int32), ("state_setter_flags", ctypes.c_int32),
+                ("state_setters", ctypes.c_void_p), ("n_state_setters", ctypes.c_int32)]
 
 # the reference build whose Bullet arithmetic the arenas follow (include/rlgpu_arith.h)
 ARITH_MSVC_X64, ARITH_GCC_X64, ARITH_SCALAR = 0, 1, 2
@@ -102,6 +104,87 @@ def state_setter_spec(setter):
     return _SS_COMBINED, 0, out
 
 
+class _AdvancedObs:
+    """RLGC::AdvancedObs (RLGPU_OBS_ADVANCED), the default obs builder: 167 floats."""
+    kind, obs_size, max_players = 0, OBS, 0
+
+    def __repr__(self):
+        return "ADVANCED_OBS"
+
+
+ADVANCED_OBS = _AdvancedObs()
+
+
+class DefaultObs:
+    """RLGC::DefaultObs(posCoef, velCoef, angVelCoef) (RG/ObsBuilders/DefaultObs.h, RLGPU_OBS_DEFAULT): 127 floats.
+    The defaults are the reference's: (1/4096, 1/5120, 1/2044), 1/2300, 1/5.5 in float32."""
+    kind, obs_size, max_players = 1, 127, 0
+
+    def __init__(self, pos_coef=None, vel_coef=None, ang_vel_coef=None):
+        f = np.float32
+        pos = (f(1) / f(4096), f(1) / f(5120), f(1) / f(2044)) if pos_coef is None else tuple(pos_coef)
+        if len(pos) != 3:
+            raise ValueError(f"{type(self).__name__}: pos_coef must have 3 components, got {len(pos)}")
+        self.pos_coef = tuple(float(f(x)) for x in pos)
+        self.vel_coef = float(f(1) / f(2300) if vel_coef is None else f(vel_coef))
+        self.ang_vel_coef = float(f(1) / f(5.5) if ang_vel_coef is None else f(ang_vel_coef))
+        for name, v in (("pos_coef", self.pos_coef), ("vel_coef", (self.vel_coef,)),
+                        ("ang_vel_coef", (self.ang_vel_coef,))):
+            if not all(np.isfinite(x) for x in v):
+                raise ValueError(f"{type(self).__name__}: {name} is not finite ({v})")
+        if not any(self.pos_coef) and not self.vel_coef and not self.ang_vel_coef:
+            raise ValueError(f"{type(self).__name__}: all coefficients are zero, which the C ABI reads as "
+                             "\"the defaults\" (rlgpu_envset_config)")
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.pos_coef}, {self.vel_coef}, {self.ang_vel_coef})"
+
+
+class DefaultObsPadded(DefaultObs):
+    """RLGC::DefaultObsPadded(maxPlayers, posCoef, velCoef, angVelCoef) (RLGPU_OBS_DEFAULT_PADDED): the row of a
+    DefaultObs with max_players - 1 teammate and max_players opponent slots, each list shuffled, 51 + 38 x
+    max_players floats.  max_players is 2 or 3 in 2v2."""
+    kind = 2
+
+    def __init__(self, max_players, pos_coef=None, vel_coef=None, ang_vel_coef=None):
+        if isinstance(max_players, bool) or not isinstance(max_players, (int, np.integer)):
+            raise ValueError(f"DefaultObsPadded: max_players must be an integer, got {max_players!r}")
+        self.max_players = int(max_players)
+        if self.max_players < 2:
+            raise ValueError(f"DefaultObsPadded: max_players {self.max_players} leaves {self.max_players - 1} "
+                             "teammate slots, and a 2v2 player has one teammate")
+        if self.max_players > 3:
+            raise ValueError(f"DefaultObsPadded: max_players {self.max_players} makes rows of "
+                             f"{51 + 38 * self.max_players} floats, and the env kernel's staging rows hold {OBS} "
+                             "(max_players 2 or 3)")
+        self.obs_size = 51 + 38 * self.max_players
+        super().__init__(pos_coef, vel_coef, ang_vel_coef)
+
+    def __repr__(self):
+        return f"DefaultObsPadded({self.max_players}, {self.pos_coef}, {self.vel_coef}, {self.ang_vel_coef})"
+
+
+def obs_builder_spec(builder):
+    """The obs builder as an ADVANCED_OBS / DefaultObs / DefaultObsPadded object (None = ADVANCED_OBS); raises
+    ValueError naming anything else."""
+    if builder is None:
+        return ADVANCED_OBS
+    if isinstance(builder, (_AdvancedObs, DefaultObs)):
+        return builder
+    raise ValueError(f"obs_builder: {builder!r} is no obs builder (ADVANCED_OBS, DefaultObs(...) or "
+                     "DefaultObsPadded(max_players, ...))")
+
+
+def set_obs_builder(cfg, builder):
+    """Fill the obs_* fields of an rlgpu_envset_config / rlgpu_learner_config mirror from a builder object."""
+    b = obs_builder_spec(builder)
+    cfg.obs_builder, cfg.obs_max_players = b.kind, b.max_players
+    if b.kind:
+        cfg.obs_pos_coef = (ctypes.c_float * 3)(*b.pos_coef)
+        cfg.obs_vel_coef, cfg.obs_ang_vel_coef = b.vel_coef, b.ang_vel_coef
+    return b
+
+
 class StepOutputs(ctypes.Structure):
     """rlgpu_step_outputs: experience-append destinations of the fused step (device pointers)."""
     _fields_ = [("obs", ctypes.c_void_p), ("masks", ctypes.c_void_p), ("rewards", ctypes.c_void_p),
@@ -138,6 +221,8 @@ def _bind():
     L.rlgpu_envset_create.argtypes = [ctypes.POINTER(_Config), ctypes.POINTER(vp)]
     L.rlgpu_envset_destroy.argtypes = [vp]
     L.rlgpu_envset_buffers_get.argtypes = [vp, ctypes.POINTER(_Buffers)]
+    L.rlgpu_envset_obs_size.argtypes = [vp]
+    L.rlgpu_obs_builder_size.argtypes = [i32, i32]
     L.rlgpu_envset_reset.argtypes = [vp, vp]
     L.rlgpu_envset_reset_arenas.argtypes = [vp, vp, vp]
     L.rlgpu_envset_step_first_half.argtypes = [vp, vp]
@@ -160,6 +245,15 @@ def _bind():
     L.rlgpu_envset_reward_values.restype = vp
     _bound = True
     return L
+
+
+def obs_builder_size(kind, max_players=0):
+    """rlgpu_obs_builder_size: the row width of an obs builder kind (167 / 127 / 51 + 38 x max_players); raises
+    RLGPUError naming a refused kind or max_players."""
+    w = _bind().rlgpu_obs_builder_size(int(kind), int(max_players))
+    if w < 0:
+        _lib.check(1, "rlgpu_obs_builder_size")
+    return w
 
 
 def arena_state_size():
@@ -188,20 +282,21 @@ def gamestates_from_arenas(buf, tick_skip=8):
 
 
 class EnvSet:
-    """Vectorised 2v2 arena set resident in HBM (AdvancedObs, DefaultAction, KickoffState, and a
+    """Vectorised 2v2 arena set resident in HBM (AdvancedObs / DefaultObs / DefaultObsPadded, DefaultAction, a state setter, and a
     reward / terminal list from the device registry -- ExampleMain's 13 rewards and NoTouch(8 s) +
     ScoreLimit(3) by default)."""
 
     def __init__(self, num_arenas, seed=1234, tick_skip=8, action_delay=7, save_rewards=True, device="cuda:0",
                  max_episode_steps=0, mesh=None, rewards=None, terminals=None, arith=ARITH_MSVC_X64, arena_offset=0,
-                 state_setter=KICKOFF_STATE):
+                 state_setter=KICKOFF_STATE, obs_builder=None):
         """mesh: an rlgpu.mesh.ArenaMesh (e.g. ArenaMesh.from_folder("collision_meshes")), or None for
         the built-in synthetic arena mesh.  rewards / terminals: lists of rlgpu.plugins.reward(...) /
         terminal(...) specs (or structured arrays), None = ExampleMain's.  arith: the reference build
         whose Bullet arithmetic the step follows (ARITH_MSVC_X64 = build.ps1's, ARITH_GCC_X64, ARITH_SCALAR).
         arena_offset: global index of arena 0 for the arenas' random streams (a rank's first arena).
         state_setter: KICKOFF_STATE, FUZZED_KICKOFF_STATE (the skill tracker's, rlgpu.skill), a RandomState or a
-        CombinedState of those."""
+        CombinedState of those.  obs_builder: ADVANCED_OBS (None), a DefaultObs or a DefaultObsPadded; self.obs_size
+        is its row width."""
         import torch
         if not torch.cuda.is_available():
             raise _lib.RLGPUError("EnvSet needs an MI355X: the product path has no CPU fallback")
@@ -215,6 +310,7 @@ class EnvSet:
         if self._ss is not None:
             cfg.state_setters, cfg.n_state_setters = self._ss.ctypes.data, self._ss.size
         self.arith = int(arith)
+        self.obs_builder = set_obs_builder(cfg, obs_builder)
         if mesh is not None:
             cfg.mesh_tris = mesh.tris.ctypes.data
             cfg.mesh_ntris = mesh.num_tris
@@ -256,12 +352,13 @@ class EnvSet:
         _lib.check(L.rlgpu_envset_buffers_get(self._h, ctypes.byref(b)), "rlgpu_envset_buffers_get")
         self.num_arenas, self.num_players, self.num_rewards = b.num_arenas, b.num_players, b.num_rewards
         P, N, dev = b.num_players, b.num_arenas, self.device
-        self.obs = _alias(b.obs, (P, OBS), torch.float32, dev)
+        self.obs_size = W = L.rlgpu_envset_obs_size(self._h)
+        self.obs = _alias(b.obs, (P, W), torch.float32, dev)
         self.action_masks = _alias(b.action_masks, (P, ACTIONS), torch.uint8, dev)
         self.rewards = _alias(b.rewards, (P,), torch.float32, dev)
         self.terminals = _alias(b.terminals, (N,), torch.uint8, dev)
         self.last_rewards = _alias(b.last_rewards, (N, self.num_rewards), torch.float32, dev)
-        self.trunc_obs = _alias(b.trunc_obs, (P, OBS), torch.float32, dev)
+        self.trunc_obs = _alias(b.trunc_obs, (P, W), torch.float32, dev)
         self.arena_player_start = _alias(b.arena_player_start, (N,), torch.int32, dev)
 
     def close(self):

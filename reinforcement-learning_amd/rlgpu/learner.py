@@ -298,6 +298,8 @@ class LearnerConfig:
         self.terminals = None              # terminal conditions (rlgpu.plugins.terminal specs); None = ExampleMain's
         self.state_setter = 0              # EnvCreateResult::stateSetter of the training arenas: rlgpu.env KICKOFF_STATE (0),
                                            # FUZZED_KICKOFF_STATE, RandomState(...) or CombinedState([...])
+        self.obs_builder = None            # EnvCreateResult::obsBuilder: rlgpu.env ADVANCED_OBS (None), DefaultObs(...) or
+                                           # DefaultObsPadded(max_players, ...); its obs_size x frame_stack is the models' input
         self.mesh = None                   # arena collision meshes (rlgpu.mesh.ArenaMesh); None = the built-in synthetic arena
         self.max_episode_duration = 300.0  # seconds (ExampleMain)
         self.deterministic = False
@@ -360,6 +362,9 @@ class _CConfig(ctypes.Structure):
                 ("terminals", ctypes.c_void_p), ("n_terminals", ctypes.c_int32),
                 ("state_setter", ctypes.c_int32), ("state_setter_flags", ctypes.c_int32),
                 ("state_setters", ctypes.c_void_p), ("n_state_setters", ctypes.c_int32),
+                ("obs_builder", ctypes.c_int32), ("obs_max_players", ctypes.c_int32),
+                ("obs_pos_coef", ctypes.c_float * 3), ("obs_vel_coef", ctypes.c_float),
+                ("obs_ang_vel_coef", ctypes.c_float),
                 ("experience_mode", ctypes.c_int32), ("ts_per_itr", ctypes.c_int64),
                 ("experience_capacity", ctypes.c_int32), ("arith", ctypes.c_int32),
                 ("activation", ctypes.c_int32), ("no_layer_norm", ctypes.c_int32), ("optimizer", ctypes.c_int32),
@@ -464,8 +469,9 @@ class _ObsStat:
         self._L = learner
 
     def get(self):
-        """(count, means [OBS] float64, m2 [OBS] float64)"""
-        n, mean, m2 = ctypes.c_int64(), np.zeros(OBS, np.float64), np.zeros(OBS, np.float64)
+        """(count, means [obs width] float64, m2 [obs width] float64)"""
+        w = self._L.env.obs_size
+        n, mean, m2 = ctypes.c_int64(), np.zeros(w, np.float64), np.zeros(w, np.float64)
         _lib.check(_lib.lib().rlgpu_learner_get_obs_stat(self._L._h, ctypes.byref(n), mean.ctypes.data, m2.ctypes.data),
                    "rlgpu_learner_get_obs_stat")
         return n.value, mean, m2
@@ -473,8 +479,9 @@ class _ObsStat:
     def set(self, count, means, m2):
         mean = np.ascontiguousarray(means, np.float64).ravel()
         m2 = np.ascontiguousarray(m2, np.float64).ravel()
-        if mean.size != OBS or m2.size != OBS:
-            raise ValueError(f"obs_stat: expected {OBS} means and vars, got {mean.size} and {m2.size}")
+        w = self._L.env.obs_size
+        if mean.size != w or m2.size != w:
+            raise ValueError(f"obs_stat: expected {w} means and vars, got {mean.size} and {m2.size}")
         _lib.check(_lib.lib().rlgpu_learner_set_obs_stat(self._L._h, int(count), mean.ctypes.data, m2.ctypes.data),
                    "rlgpu_learner_set_obs_stat")
 
@@ -530,7 +537,8 @@ class Learner:
             tc = plugins.terminals_array(cfg.terminals)
             self._tc = np.ascontiguousarray(tc if tc.size else np.zeros(1, plugins.TERMINAL_SPEC))
             c.terminals, c.n_terminals = self._tc.ctypes.data, tc.size
-        from .env import state_setter_spec
+        from .env import set_obs_builder, state_setter_spec
+        set_obs_builder(c, cfg.obs_builder)
         c.state_setter, c.state_setter_flags, self._ss = state_setter_spec(cfg.state_setter)
         if self._ss is not None:
             c.state_setters, c.n_state_setters = self._ss.ctypes.data, self._ss.size
@@ -567,7 +575,7 @@ class Learner:
         rows_cap = cfg.mini_batch_size if cfg.experience_mode == 1 else cfg.rollout_len * 4 * cfg.num_arenas
         max_rows = max(min(cfg.mini_batch_size, rows_cap), min(4 * cfg.num_arenas, 65536))  # host/learner.cpp
         self.ppo = PPO.wrap(ph.value, self.device, cfg.policy_layers, cfg.critic_layers, max_rows,
-                            obs_size=OBS * max(1, cfg.frame_stack), metrics_source=self._metrics, owner=self,
+                            obs_size=self.env.obs_size * max(1, cfg.frame_stack), metrics_source=self._metrics, owner=self,
                             shared_layers=cfg.shared_layers, layer_norm=bool(cfg.layer_norm), activation=cfg.activation,
                             leaky_slope=0.0 if cfg.activation == "relu" else 0.01, infer_fp16=int(cfg.infer_fp16),
                             optim_options={"lr": (cfg.policy_lr, cfg.critic_lr, min(cfg.policy_lr, cfg.critic_lr)),
@@ -611,7 +619,7 @@ class Learner:
         if cfg.skill_tracker is not None and cfg.skill_tracker.enabled and rank == 0:  # PolicyVersionManager.cpp:24-31
             from .skill import SkillTracker
             self.skill = SkillTracker(cfg.skill_tracker, self.ppo, self.device, cfg.tick_skip, cfg.action_delay,
-                                      seed=cfg.seed, mesh=cfg.mesh, arith=cfg.arith)
+                                      seed=cfg.seed, mesh=cfg.mesh, arith=cfg.arith, obs_builder=cfg.obs_builder)
         if cfg.train_against_old_versions or self.skill is not None:  # Learner.cpp:131-142
             import os
             from .versions import PolicyVersionManager

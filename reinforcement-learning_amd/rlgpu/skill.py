@@ -95,14 +95,19 @@ class SkillTracker:
 
     RNG_STEP_BASE = 1 << 40  # Philox counter range of the matches' policy draws (the rollout uses small steps)
 
-    def __init__(self, cfg, ppo, device, tick_skip=8, action_delay=7, seed=0, mesh=None, arith=0):
+    def __init__(self, cfg, ppo, device, tick_skip=8, action_delay=7, seed=0, mesh=None, arith=0, obs_builder=None):
         self.cfg = cfg
         self.ppo = ppo
         self.device = device
         self.env = _env.EnvSet(cfg.num_arenas, seed=seed + 7919, tick_skip=tick_skip, action_delay=action_delay,
                                save_rewards=False, device=device, rewards=[],
                                terminals=[_plugins.terminal("GoalScoreCondition")], mesh=mesh, arith=arith,
-                               state_setter=_env.FUZZED_KICKOFF_STATE)
+                               state_setter=_env.FUZZED_KICKOFF_STATE, obs_builder=obs_builder)
+        if self.env.obs_size != ppo.obs_size:  # the matches feed the set's rows to the policy as they are
+            w = self.env.obs_size
+            self.env.close()
+            raise ValueError(f"SkillTracker: the env set builds obs rows of {w} floats, the policy reads {ppo.obs_size} "
+                             "(obs_builder must be the training arenas')")
         self.cur_ratings = SkillRating()
         self.cur_goals = 0
         self.do_continuation = False
