@@ -118,8 +118,10 @@ typedef struct {
     int32_t no_layer_norm;         /* 1: PartialModelConfig::addLayerNorm = false for every model (hidden layers
                                       are Linear -> activation); 0 (a zero-initialised config): LayerNorm on */
     int32_t optimizer;             /* PartialModelConfig::optimType of every model (Models.h:40-56):
-                                      RLGPU_OPT_ADAMW (0, libtorch AdamW: weight decay 1e-2) or RLGPU_OPT_ADAM
-                                      (libtorch Adam: no weight decay) */
+                                      RLGPU_OPT_ADAMW (0, libtorch AdamW: weight decay 1e-2), RLGPU_OPT_ADAM
+                                      (libtorch Adam: no weight decay), RLGPU_OPT_ADAGRAD, RLGPU_OPT_RMSPROP or
+                                      RLGPU_OPT_MAGSGD (rlgpu_ppo.h: rlgpu_ppo_set_optimizer, applied to every
+                                      model) */
     int32_t collect_groups;        /* the rollout collection's arena groups, each stepped and inferred on its own
                                       stream and its own partition of the device's CUs, so one group's launch tail
                                       overlaps the others' work (same results bit for bit); 0 = automatic (2 groups
@@ -139,8 +141,6 @@ typedef struct {
                                       collection, old versions and Learn alike; 0 = 1 */
     int32_t mask_entropy;          /* rlgpu_ppo_config.mask_entropy (PPOLearnerConfig::maskEntropy) */
 } rlgpu_learner_config;
-
-enum { RLGPU_OPT_ADAMW = 0, RLGPU_OPT_ADAM = 1 };
 
 enum { RLGPU_EXP_ROLLOUT = 0, RLGPU_EXP_TRAJECTORIES = 1 };
 

@@ -250,8 +250,8 @@ int rlgpu_ppo_minibatch_guided(rlgpu_ppo* h, const float* d_obs, const uint8_t* 
                                float* d_metrics, void* stream);
 
 /* clip_grad_norm_(model, max_grad_norm) per model (policy, critic, shared head: PPOLearner.cpp:521-526),
- * AdamW step (libtorch semantics), zero grads, refresh the bf16 copy.  Grad norms written to
- * d_metrics (optional). */
+ * AdamW step (libtorch semantics; or each model's rlgpu_ppo_set_optimizer type), zero grads, refresh the bf16 copy.
+ * Grad norms written to d_metrics (optional). */
 int rlgpu_ppo_optimizer_step(rlgpu_ppo* h, float* d_metrics, void* stream);
 int rlgpu_ppo_zero_grad(rlgpu_ppo* h, void* stream);
 /* Optimizer state (step count + moments) for checkpointing; moments are device pointers. */
@@ -265,6 +265,26 @@ int rlgpu_ppo_set_optimizer_step(rlgpu_ppo* h, int64_t step);
  * write one model's (model 2 without a shared head: RLGPU_ERR_INVALID_ARG). */
 int rlgpu_ppo_model_optimizer_step(rlgpu_ppo* h, int32_t model, int64_t* step);
 int rlgpu_ppo_set_model_optimizer_step(rlgpu_ppo* h, int32_t model, int64_t step);
+
+/* PartialModelConfig::optimType (Util/ModelConfig.h; Util/Models.h: MakeOptimizer(type, params, lr), libtorch's defaults
+ * with nothing but lr set).  With gr = grad * the model's clip coefficient (the transfer step: gr = grad), every
+ * operation rounded on its own:
+ *   ADAMW / ADAM  the handle's Adam arithmetic with rlgpu_ppo_config.weight_decay (ADAM is a config with weight_decay 0)
+ *   ADAGRAD       sum += gr*gr;                    p += -lr * (gr / (sqrt(sum) + 1e-10))
+ *   RMSPROP       sq = sq*0.99 + 0.01*gr*gr;       p += -lr * (gr / (sqrt(sq) + 1e-8))
+ *   MAGSGD        (Util/MagSGD.h, then SGD at momentum 0) p += -lr * (gr / ||gr||), ||gr|| over the model's own
+ *                 parameters after the clip: a step of length lr.  rlgpu_ppo_optimizer_step forms ||gr|| as the
+ *                 clip's norm * coefficient; the transfer step reduces the gradient itself.
+ * Adagrad's sum and RMSprop's square_avg live in the model's exp_avg_sq span; exp_avg is not touched; MagSGD touches
+ * neither.  The step count advances for every type. */
+enum { RLGPU_OPT_ADAMW = 0, RLGPU_OPT_ADAM = 1, RLGPU_OPT_ADAGRAD = 2, RLGPU_OPT_RMSPROP = 3, RLGPU_OPT_MAGSGD = 4 };
+/* The optimizer of one model (0 policy, 1 critic, 2 shared head) or, with model -1, of every model; ADAMW on a new
+ * handle.  To be called before the first rlgpu_ppo_optimizer_step / rlgpu_ppo_transfer_step that steps the model:
+ * afterwards, and for an unknown model or type, RLGPU_ERR_INVALID_ARG.
+ * MAGSGD on a model whose gradient is all zero divides 0 by 0 and writes NaN into every parameter of that model, as
+ * the reference's MagSGD::step does (grad / grad.norm()); it is not guarded here either. */
+int rlgpu_ppo_set_optimizer(rlgpu_ppo* h, int32_t model, int32_t type);
+int rlgpu_ppo_get_optimizer(rlgpu_ppo* h, int32_t model, int32_t* type);
 
 /* ---- Transfer learning (Learner::StartTransferLearn, Learner.cpp:299-480; PPOLearner::TransferLearn,
  * PPOLearner.cpp:583-637): distil an old policy (the teacher, any architecture) into this one.
@@ -304,8 +324,8 @@ int rlgpu_ppo_transfer_chunk(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_
                              int64_t total_rows, int32_t use_kl, float loss_scale, float loss_exponent, float* d_metrics,
                              void* stream);
 /* The optimiser step of a transfer-learning epoch (ModelSet::StepOptims after SetOptimLR(tlConfig.lr); no
- * clip_grad_norm_): the handle's AdamW arithmetic at learning rate lr on the policy and the shared head, without a clip
- * coefficient; zeroes those models' gradients, advances their step counts and refreshes their 16-bit copies.  The
+ * clip_grad_norm_): the handle's AdamW arithmetic (or each model's rlgpu_ppo_set_optimizer type) at learning rate lr on
+ * the policy and the shared head, without a clip coefficient; zeroes those models' gradients, advances their step counts and refreshes their 16-bit copies.  The
  * critic's parameters, gradients, moments and step count are not touched. */
 int rlgpu_ppo_transfer_step(rlgpu_ppo* h, float lr, void* stream);
 /* ||a - b|| of two device spans of n floats into d_out[0] ("Policy Update Magnitude": the policy model before and after

@@ -111,6 +111,11 @@ void launch_transfer_loss(const TransferLossArgs& a, hipStream_t s);
 // adamw's arithmetic without a clip coefficient on one span of n parameters; zeroes g
 void launch_adam_models(float* p, float* g, float* m, float* v, int64_t n, float decay_mul, float beta1, float beta2,
                         float step_size, float bc2_sqrt, float eps, hipStream_t s);
+// one unclipped step of a non-Adam optimizer (kind: RLGPU_OPT_ADAGRAD / _RMSPROP / _MAGSGD; ppo::optim_step) on one span
+// of n parameters, v the span's exp_avg_sq; zeroes g.  MagSGD reduces ||g|| first: part512 is 512 floats of scratch and
+// norm one float, both untouched by the other kinds
+void launch_optim_models(int kind, float* p, float* g, float* v, int64_t n, float lr, float* part512, float* norm,
+                         hipStream_t s);
 // *out = ||a - b|| over n floats (part512: 512 floats of scratch)
 void launch_diff_norm(const float* a, const float* b, int64_t n, float* part512, float* out, hipStream_t s);
 

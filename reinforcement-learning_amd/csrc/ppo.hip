@@ -172,6 +172,8 @@ struct rlgpu_ppo {
     // minibatch.
     bool split_dirty[3] = {true, true, true};
     int64_t step[3] = {0, 0, 0};  // AdamW step count per model (libtorch keeps it per parameter)
+    int32_t opt[3] = {RLGPU_OPT_ADAMW, RLGPU_OPT_ADAMW, RLGPU_OPT_ADAMW};  // rlgpu_ppo_set_optimizer
+    bool opt_stepped[3] = {false, false, false};  // the model's optimizer has stepped: its type is fixed
     int hmax = 0;
     float *scratch = nullptr;  // clip partials + coefficients
     hipStream_t aux = nullptr;  // second stream: the critic's minibatch pass overlaps the policy's
@@ -975,6 +977,20 @@ void build_model(rlgpu_ppo* h, Model& m, int in, const int32_t* layers, int nl, 
     m.count = h->nparams - m.off;
 }
 
+// h->scratch: [0, 512) the sum-of-squares partials, 600 + mi the clip coefficients, kScratchNorm + mi a model's gradient
+// norm where no metrics buffer takes it
+constexpr int kScratchNorm = 608;
+
+// one step of a non-Adam optimizer on a model's span (ppo::optim_step); coef null: unclipped
+void launch_optim_step(int kind, float* p, float* g, float* v, int64_t n, const float* coef, const float* norm, float lr,
+                       hipStream_t s) {
+    auto* fn = kind == RLGPU_OPT_ADAGRAD   ? &ppo::optim_step<ppo::kOptAdagrad>
+               : kind == RLGPU_OPT_RMSPROP ? &ppo::optim_step<ppo::kOptRmsprop>
+                                           : &ppo::optim_step<ppo::kOptMagSgd>;
+    hipLaunchKernelGGL(fn, dim3(ceil_div(n, 256)), dim3(256), 0, s, p, g, v, n, coef, norm, lr);
+    RLGPU_CHECK_HIP(hipGetLastError());
+}
+
 void sumsq_coef(rlgpu_ppo* h, const float* x, int64_t n, float max_norm, float* coef, float* norm_out, hipStream_t s) {
     const int nb = 512;
     hipLaunchKernelGGL(ppo::sumsq_partial, dim3(nb), dim3(256), 0, s, x, n, h->scratch);
@@ -1495,7 +1511,16 @@ extern "C" int rlgpu_ppo_optimizer_step(rlgpu_ppo* h, float* d_metrics, void* st
             double bc2 = 1.0 - std::pow((double)c.beta2, (double)h->step[mi]);
             float* coef = h->scratch + 600 + mi;
             float* norm_out = d_metrics ? d_metrics + slot[mi] : nullptr;
+            const bool adam = h->opt[mi] == RLGPU_OPT_ADAMW || h->opt[mi] == RLGPU_OPT_ADAM;
+            // MagSGD reads the norm back on the device: without a metrics buffer it goes to the scratch
+            if (h->opt[mi] == RLGPU_OPT_MAGSGD && !norm_out) norm_out = h->scratch + kScratchNorm + mi;
             sumsq_coef(h, h->grads + m.off, m.count, c.max_grad_norm, coef, norm_out, s);
+            h->opt_stepped[mi] = true;
+            if (!adam) {
+                launch_optim_step(h->opt[mi], h->params + m.off, h->grads + m.off, h->exp_avg_sq + m.off, m.count, coef,
+                                  norm_out, (float)m.lr, s);
+                continue;
+            }
             double lr = m.lr;
             float decay_mul = (float)(1.0 - lr * (double)c.weight_decay);
             float step_size = (float)(lr / bc1);
@@ -1522,6 +1547,27 @@ extern "C" int rlgpu_ppo_optimizer_state(rlgpu_ppo* h, int64_t* step, float** d_
         if (step) *step = h->step[0];
         if (d_exp_avg) *d_exp_avg = h->exp_avg;
         if (d_exp_avg_sq) *d_exp_avg_sq = h->exp_avg_sq;
+    });
+}
+
+extern "C" int rlgpu_ppo_set_optimizer(rlgpu_ppo* h, int32_t model, int32_t type) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h, "null handle");
+        RLGPU_REQUIRE(model >= -1 && model < h->nm, "rlgpu_ppo_set_optimizer: model must be -1 (every model) or one of the handle's");
+        RLGPU_REQUIRE(type >= RLGPU_OPT_ADAMW && type <= RLGPU_OPT_MAGSGD,
+                      "rlgpu_ppo_set_optimizer: type must be RLGPU_OPT_ADAMW, ADAM, ADAGRAD, RMSPROP or MAGSGD");
+        for (int mi = 0; mi < h->nm; mi++)
+            RLGPU_REQUIRE((model >= 0 && model != mi) || !h->opt_stepped[mi],
+                          "rlgpu_ppo_set_optimizer: the model's optimizer has already stepped (set the type before the first step)");
+        for (int mi = 0; mi < h->nm; mi++)
+            if (model < 0 || model == mi) h->opt[mi] = type;
+    });
+}
+
+extern "C" int rlgpu_ppo_get_optimizer(rlgpu_ppo* h, int32_t model, int32_t* type) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(h && type && model >= 0 && model < h->nm, "rlgpu_ppo_get_optimizer: bad argument");
+        *type = h->opt[model];
     });
 }
 
@@ -1631,13 +1677,19 @@ extern "C" int rlgpu_ppo_transfer_step(rlgpu_ppo* h, float lr, void* stream) {
         for (int mi = 0; mi < h->nm; mi += 2) {  // GetPolicyModels(): the policy and the shared head
             Model& m = h->M[mi];
             h->step[mi]++;
-            // rlgpu_ppo_optimizer_step's scalars with lr in place of the model's
-            const double bc1 = 1.0 - std::pow((double)c.beta1, (double)h->step[mi]);
-            const double bc2 = 1.0 - std::pow((double)c.beta2, (double)h->step[mi]);
-            const double dlr = lr;
-            rlgpu::launch_adam_models(h->params + m.off, h->grads + m.off, h->exp_avg + m.off, h->exp_avg_sq + m.off, m.count,
-                                      (float)(1.0 - dlr * (double)c.weight_decay), c.beta1, c.beta2, (float)(dlr / bc1),
-                                      (float)std::sqrt(bc2), c.eps, s);
+            h->opt_stepped[mi] = true;
+            if (h->opt[mi] == RLGPU_OPT_ADAMW || h->opt[mi] == RLGPU_OPT_ADAM) {
+                // rlgpu_ppo_optimizer_step's scalars with lr in place of the model's
+                const double bc1 = 1.0 - std::pow((double)c.beta1, (double)h->step[mi]);
+                const double bc2 = 1.0 - std::pow((double)c.beta2, (double)h->step[mi]);
+                const double dlr = lr;
+                rlgpu::launch_adam_models(h->params + m.off, h->grads + m.off, h->exp_avg + m.off, h->exp_avg_sq + m.off,
+                                          m.count, (float)(1.0 - dlr * (double)c.weight_decay), c.beta1, c.beta2,
+                                          (float)(dlr / bc1), (float)std::sqrt(bc2), c.eps, s);
+            } else {  // optim_step without a clip coefficient; MagSGD's own reduction goes through the scratch
+                rlgpu::launch_optim_models(h->opt[mi], h->params + m.off, h->grads + m.off, h->exp_avg_sq + m.off, m.count, lr,
+                                           h->scratch, h->scratch + kScratchNorm + mi, s);
+            }
             half_from(h, mi, h->params + m.off, h->half, h->frag, s);
             h->split_dirty[mi] = true;
         }

@@ -533,6 +533,39 @@ __global__ void adamw(float* p, float* g, float* m, float* v, int64_t n, const f
     g[e] = 0.f;
 }
 
+// The other optimizers of MakeOptimizer (Util/Models.h), libtorch defaults with nothing but lr set; KIND is the
+// RLGPU_OPT_* value.  coef: the clip coefficient, or null for an unclipped step (the transfer step).  The operations
+// are rounded one by one, as adamw's are; grads zeroed after use.
+//   ADAGRAD (adagrad.cpp: lr_decay 0, initial_accumulator_value 0, eps 1e-10): v = sum
+//   RMSPROP (rmsprop.cpp: alpha 0.99, eps 1e-8, momentum 0, not centered):     v = square_avg
+//   MAGSGD  (Util/MagSGD.h, then SGD at momentum 0): p -= lr * gr / ||gr||, with ||gr|| = *norm * coef (norm: the
+//           model's unclipped gradient norm); v is not touched.  An all-zero gradient gives 0 / 0 = NaN, as there.
+constexpr int kOptAdagrad = 2, kOptRmsprop = 3, kOptMagSgd = 4;
+template <int KIND>
+__global__ void optim_step(float* p, float* g, float* v, int64_t n, const float* coef, const float* norm, float lr) {
+#pragma clang fp contract(off)
+    static_assert(KIND == kOptAdagrad || KIND == kOptRmsprop || KIND == kOptMagSgd, "optim_step: unknown optimizer");
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const float c = coef ? *coef : 1.f;
+    const float gr = coef ? g[e] * c : g[e];
+    float denom;
+    if constexpr (KIND == kOptAdagrad) {
+        const float sum = v[e] + gr * gr;
+        v[e] = sum;
+        denom = sqrtf(sum) + 1e-10f;
+    } else if constexpr (KIND == kOptRmsprop) {
+        constexpr float alpha = 0.99f, one_m_alpha = (float)(1.0 - 0.99);  // libtorch forms 1 - alpha in double
+        const float sq = v[e] * alpha + one_m_alpha * gr * gr;
+        v[e] = sq;
+        denom = sqrtf(sq) + 1e-8f;
+    } else {
+        denom = coef ? *norm * c : *norm;
+    }
+    p[e] = p[e] + (-lr) * (gr / denom);
+    g[e] = 0.f;
+}
+
 template <bool F16>
 __global__ void to_half(const float* p, uint16_t* h, int64_t n) {
     int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

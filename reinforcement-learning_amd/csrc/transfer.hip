@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "../../include/rlgpu_detmath.h"
+#include "../../include/rlgpu_ppo.h"
 #include "common.hpp"
 
 namespace {
@@ -47,6 +48,25 @@ void launch_adam_models(float* p, float* g, float* m, float* v, int64_t n, float
     if (n <= 0) return;
     hipLaunchKernelGGL(ppo::adam_models, dim3(ceil_div(n, 256)), dim3(256), 0, s, p, g, m, v, n, decay_mul, beta1, beta2,
                        1.f - beta1, 1.f - beta2, step_size, bc2_sqrt, eps);
+    RLGPU_CHECK_HIP(hipGetLastError());
+}
+
+void launch_optim_models(int kind, float* p, float* g, float* v, int64_t n, float lr, float* part512, float* norm,
+                         hipStream_t s) {
+    if (n <= 0) return;
+    const dim3 grid(ceil_div(n, 256)), block(256);
+    const float* no_coef = nullptr;
+    if (kind == RLGPU_OPT_ADAGRAD) {
+        hipLaunchKernelGGL(ppo::optim_step<ppo::kOptAdagrad>, grid, block, 0, s, p, g, v, n, no_coef, no_coef, lr);
+    } else if (kind == RLGPU_OPT_RMSPROP) {
+        hipLaunchKernelGGL(ppo::optim_step<ppo::kOptRmsprop>, grid, block, 0, s, p, g, v, n, no_coef, no_coef, lr);
+    } else {
+        RLGPU_REQUIRE(kind == RLGPU_OPT_MAGSGD, "launch_optim_models: unknown optimizer");
+        const int nb = 512;  // MagSGD::step's grad.norm() over the model: the clip's reduction, its result the norm alone
+        hipLaunchKernelGGL(ppo::sumsq_partial, dim3(nb), dim3(256), 0, s, (const float*)g, n, part512);
+        hipLaunchKernelGGL(ppo::diff_norm_final, dim3(1), dim3(64), 0, s, (const float*)part512, nb, norm);
+        hipLaunchKernelGGL(ppo::optim_step<ppo::kOptMagSgd>, grid, block, 0, s, p, g, v, n, no_coef, (const float*)norm, lr);
+    }
     RLGPU_CHECK_HIP(hipGetLastError());
 }
 

@@ -494,6 +494,23 @@ inline std::filesystem::path TempFile(const char* tag) {
 
 inline void HipOk(hipError_t e, const char* what) { RLGC::RlgpuCheckHip(e, what); }
 
+// ModelOptimType as RLGPU_OPT_* (rlgpu_ppo.h) and as rlgpu_optim_lt's --optimizer names it
+inline int OptimId(ModelOptimType t) {
+    switch (t) {
+        case ModelOptimType::ADAM: return RLGPU_OPT_ADAM;
+        case ModelOptimType::ADAGRAD: return RLGPU_OPT_ADAGRAD;
+        case ModelOptimType::RMSPROP: return RLGPU_OPT_RMSPROP;
+        case ModelOptimType::MAGSGD: return RLGPU_OPT_MAGSGD;
+        default: return RLGPU_OPT_ADAMW;
+    }
+}
+inline const char* OptimName(int id) {
+    static const char* const names[] = {"adamw", "adam", "adagrad", "rmsprop", "magsgd"};
+    return id >= 0 && id < 5 ? names[id] : "unknown";
+}
+// whether an optimizer of type b can use the state of type a: the same type, or Adam and AdamW (the same moments)
+inline bool OptimSameState(int a, int b) { return a == b || (a <= RLGPU_OPT_ADAM && b <= RLGPU_OPT_ADAM && a >= 0 && b >= 0); }
+
 }  // namespace detail
 
 // ---------------------------------------------------------------------------------------------------------
@@ -733,8 +750,10 @@ inline void Learner::ValidateConfig(const LearnerConfig& c) {
         // one setting for every model: per-model activationType / addLayerNorm are not supported
         if (m.activationType != c.ppo.policy.activationType) bad("every model must use the same activationType");
         if (m.addLayerNorm != c.ppo.policy.addLayerNorm) bad("every model must use the same addLayerNorm");
-        if (m.optimType != ModelOptimType::ADAMW && m.optimType != ModelOptimType::ADAM)
-            bad(std::string("ppo.") + names[k] + ".optimType must be ADAMW or ADAM");
+        if (m.optimType != ModelOptimType::ADAMW && m.optimType != ModelOptimType::ADAM &&
+            m.optimType != ModelOptimType::ADAGRAD && m.optimType != ModelOptimType::RMSPROP &&
+            m.optimType != ModelOptimType::MAGSGD)
+            bad(std::string("ppo.") + names[k] + ".optimType must be ADAM, ADAMW, ADAGRAD, RMSPROP or MAGSGD");
         if (m.optimType != c.ppo.policy.optimType) bad("every model must use the same optimType");
         if (k < 2 && !m.addOutputLayer) bad(std::string("ppo.") + names[k] + ".addOutputLayer must be true");
         if (k == 2 && m.addOutputLayer) bad("ppo.sharedHead.addOutputLayer must be false (PPOLearner.cpp:57)");
@@ -809,7 +828,7 @@ inline Learner::Learner(RLGC::EnvCreateFn envCreateFunc, LearnerConfig cfg, Step
                    : at == ModelActivationType::TANH    ? RLGPU_ACT_TANH
                                                         : RLGPU_ACT_LEAKY_RELU;
     c.no_layer_norm = config.ppo.policy.addLayerNorm ? 0 : 1;
-    c.optimizer = config.ppo.policy.optimType == ModelOptimType::ADAM ? RLGPU_OPT_ADAM : RLGPU_OPT_ADAMW;
+    c.optimizer = detail::OptimId(config.ppo.policy.optimType);
     c.rank = options.rank;
     c.world = options.world;
     static const rlgpu_reward_spec kNoRewards{};
@@ -1328,7 +1347,13 @@ inline void Learner::SaveModels(const std::filesystem::path& folder, bool saveOp
     }
     const float lrs[3] = {config.ppo.policyLR, config.ppo.criticLR, std::min(config.ppo.policyLR, config.ppo.criticLR)};
     const bool adam = config.ppo.policy.optimType == ModelOptimType::ADAM;
+    const int64_t optimId = detail::OptimId(config.ppo.policy.optimType);  // one optimType for every model (ValidateConfig)
     for (const ModelSpec& m : models) {
+        {
+            detail::Tensor t{"I64", {1}, std::vector<char>(8)};
+            std::memcpy(t.bytes.data(), &optimId, 8);
+            ts[std::string(m.name) + ".optim_type"] = std::move(t);
+        }
         int64_t off = 0, cnt = 0;
         RLGC::RlgpuCheck(rlgpu_ppo_model_range(ppo_, m.index, &off, &cnt), "model range");
         std::vector<float> mv((size_t)cnt * 2);
@@ -1353,6 +1378,10 @@ inline void Learner::SaveModels(const std::filesystem::path& folder, bool saveOp
         std::vector<std::string> a{"save", (folder / m.FileName("_OPTIM")).string(), tmp.string(), std::to_string(steps[m.index]), lr,
                                    "0.9", "0.999", "1e-08", wd};
         for (auto& s : m.ParamShapes()) a.push_back(s);
+        if (optimId > RLGPU_OPT_ADAM) {  // the matching libtorch class; Adam / AdamW: the command line it always was
+            a.push_back("--optimizer");
+            a.push_back(detail::OptimName((int)optimId));
+        }
         try {
             detail::RunHelper(a);
         } catch (...) {
@@ -1428,13 +1457,31 @@ inline void Learner::Load() {
     const std::filesystem::path st = folder / "RLGPU_OPTIM.safetensors";
     if (std::filesystem::exists(st)) {
         auto ts = detail::ReadSafetensors(st);
+        const int optimId = detail::OptimId(config.ppo.policy.optimType);
+        std::vector<int> reset;
         for (const ModelSpec& m : models) {
             int64_t off = 0, cnt = 0;
             RLGC::RlgpuCheck(rlgpu_ppo_model_range(ppo_, m.index, &off, &cnt), "model range");
+            // the state's own type; a file without the key holds Adam / AdamW state.  State the model's optimizer cannot
+            // use is reset, as the reference resets an optimizer whose file it cannot use (Models.cpp:168-186)
+            int64_t stored = RLGPU_OPT_ADAMW;
+            const std::string tkey = std::string(m.name) + ".optim_type";
+            if (ts.count(tkey) && ts[tkey].bytes.size() == 8) std::memcpy(&stored, ts[tkey].bytes.data(), 8);
+            const bool usable = detail::OptimSameState((int)stored, optimId);
+            if (!usable) {
+                std::printf("WARNING: the optimizer state of model \"%s\" in %s is %s's and the model's optimizer is %s, "
+                            "optimizer will be reset\n",
+                            m.name, st.string().c_str(), detail::OptimName((int)stored), detail::OptimName(optimId));
+                reset.push_back(m.index);
+            }
             for (int k = 0; k < 2; k++) {
                 const std::string key = std::string(m.name) + (k ? ".exp_avg_sq" : ".exp_avg");
                 if (!ts.count(key) || (int64_t)ts[key].bytes.size() != cnt * 4)
                     throw std::runtime_error("optimizer state in " + st.string() + " does not match the model sizes");
+                if (!usable) {
+                    detail::HipOk(hipMemset((k ? dv : dm) + off, 0, (size_t)cnt * 4), "reset");
+                    continue;
+                }
                 detail::HipOk(hipMemcpy((k ? dv : dm) + off, ts[key].bytes.data(), (size_t)cnt * 4, hipMemcpyHostToDevice),
                               "optimizer state");
             }
@@ -1448,6 +1495,7 @@ inline void Learner::Load() {
             std::memcpy(&s, ts.at(key).bytes.data(), 8);
             RLGC::RlgpuCheck(rlgpu_ppo_set_model_optimizer_step(ppo_, m.index, s), "optimizer step");
         }
+        for (int mi : reset) RLGC::RlgpuCheck(rlgpu_ppo_set_model_optimizer_step(ppo_, mi, 0), "optimizer step");
     } else {  // the reference's <NAME>_OPTIM.lt archives (Models.cpp:168-186); a model without one is reset
         int64_t s = 0;
         std::map<int, int64_t> own;  // each archive's own count (they differ after transfer learning)
@@ -1465,6 +1513,10 @@ inline void Learner::Load() {
             const auto tmp = detail::TempFile("optim.bin");
             std::vector<std::string> a{"load", p.string(), tmp.string()};
             for (auto& x : m.ParamShapes()) a.push_back(x);
+            if (const int id = detail::OptimId(config.ppo.policy.optimType); id > RLGPU_OPT_ADAM) {
+                a.push_back("--optimizer");
+                a.push_back(detail::OptimName(id));
+            }
             detail::RunHelper(a);
             const std::string raw = detail::ReadFile(tmp);
             std::filesystem::remove(tmp);

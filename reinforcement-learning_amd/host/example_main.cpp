@@ -22,6 +22,7 @@
 //   rlgpu_train [--iterations N] [--arenas A] [--rollout T] [--trajectories] [--f32-gemm] [--c2-model] [--seed S]
 //               [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] [--self-play] [--fp32-inference]
 //               [--policy-temperature X] [--mask-entropy] [--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm]
+//               [--optimizer adamw|adam|adagrad|rmsprop|magsgd]
 //               [--guiding-policy DIR [--guiding-strength X]] [--state-setter kickoff|random|combined:K:R]
 //               [--obs advanced|default|padded:N] [--skill-tracker N:T]
 //               [--rank r --world N --rccl-id FILE [--rccl-nonce STR]]
@@ -257,6 +258,16 @@ int main(int argc, char** argv) {
                 else if (a == "tanh") t = ModelActivationType::TANH;
                 else throw std::invalid_argument("activationType must be relu, leaky_relu, sigmoid or tanh, not " + a);
                 for (PartialModelConfig* m : {&cfg.ppo.policy, &cfg.ppo.critic, &cfg.ppo.sharedHead}) m->activationType = t;
+            } else if (!std::strcmp(argv[i], "--optimizer")) {  // ModelConfig::optimType of every model
+                const std::string a = next();
+                ModelOptimType t;
+                if (a == "adamw") t = ModelOptimType::ADAMW;
+                else if (a == "adam") t = ModelOptimType::ADAM;
+                else if (a == "adagrad") t = ModelOptimType::ADAGRAD;
+                else if (a == "rmsprop") t = ModelOptimType::RMSPROP;
+                else if (a == "magsgd") t = ModelOptimType::MAGSGD;
+                else throw std::invalid_argument("optimType must be adamw, adam, adagrad, rmsprop or magsgd, not " + a);
+                for (PartialModelConfig* m : {&cfg.ppo.policy, &cfg.ppo.critic, &cfg.ppo.sharedHead}) m->optimType = t;
             } else if (!std::strcmp(argv[i], "--no-layer-norm")) {  // ModelConfig::addLayerNorm = false, every model
                 for (PartialModelConfig* m : {&cfg.ppo.policy, &cfg.ppo.critic, &cfg.ppo.sharedHead}) m->addLayerNorm = false;
             }
@@ -275,7 +286,7 @@ int main(int argc, char** argv) {
                                  "[--c2-model] [--seed S] [--checkpoint-folder DIR [--ts-per-save N] [--resave-to DIR2]] "
                                  "[--self-play] [--fp32-inference] [--policy-temperature X] [--mask-entropy] "
                                  "[--standardize-obs [--min-obs-std X]] [--state-setter kickoff|random|combined:K:R] "
-                                 "[--obs advanced|default|padded:N] [--skill-tracker N:T] [--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm] [--guiding-policy DIR "
+                                 "[--obs advanced|default|padded:N] [--skill-tracker N:T] [--activation relu|leaky_relu|sigmoid|tanh] [--no-layer-norm] [--optimizer adamw|adam|adagrad|rmsprop|magsgd] [--guiding-policy DIR "
                                  "[--guiding-strength X]] [--transfer-learn DIR [--old-policy-layers a,b,..] [--old-shared-layers a,b,..] "
                                  "[--tl-lr X] [--tl-epochs N] [--tl-kl] [--tl-loss-scale X] [--tl-loss-exponent X] [--tl-map-acts]] "
                                  "[--rank r --world N --rccl-id FILE]\n", e.what(), argv[0]);

@@ -251,8 +251,9 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     RLGPU_REQUIRE(cfg.activation >= RLGPU_ACT_LEAKY_RELU && cfg.activation <= RLGPU_ACT_TANH,
                   "Learner: activation must be RLGPU_ACT_LEAKY_RELU, _RELU, _SIGMOID or _TANH");
     RLGPU_REQUIRE(cfg.no_layer_norm == 0 || cfg.no_layer_norm == 1, "Learner: no_layer_norm must be 0 or 1");
-    RLGPU_REQUIRE(cfg.optimizer == RLGPU_OPT_ADAMW || cfg.optimizer == RLGPU_OPT_ADAM,
-                  "Learner: optimizer must be RLGPU_OPT_ADAMW or RLGPU_OPT_ADAM");
+    RLGPU_REQUIRE(cfg.optimizer >= RLGPU_OPT_ADAMW && cfg.optimizer <= RLGPU_OPT_MAGSGD,
+                  "Learner: optimizer must be RLGPU_OPT_ADAMW, RLGPU_OPT_ADAM, RLGPU_OPT_ADAGRAD, RLGPU_OPT_RMSPROP or "
+                  "RLGPU_OPT_MAGSGD");
     pc.layer_norm = cfg.no_layer_norm ? 0 : 1;
     pc.activation = cfg.activation;
     pc.leaky_slope = 0.01f;  // torch::nn::LeakyReLU's default; RLGPU_ACT_RELU is slope 0 in rlgpu_ppo_create
@@ -276,6 +277,7 @@ Learner::Learner(const rlgpu_learner_config& cfg, const rlgpu_collective* coll, 
     pc.policy_temperature = cfg.policy_temperature;  // validated by rlgpu_ppo_create (0 = 1)
     pc.mask_entropy = cfg.mask_entropy;
     ppo_ = std::make_unique<PPOLearnerGPU>(pc, s_);
+    RlgpuCheck(rlgpu_ppo_set_optimizer(ppo_->handle(), -1, cfg.optimizer), "optimizer");
     if (hasColl_) {  // identical initial weights on every rank: rank 0's (sum of zeros elsewhere)
         float* params = nullptr;
         float* g = nullptr;

@@ -11,8 +11,8 @@
 // false) saved with torch::save(seq, stream) and
 // read with torch::load(seq, stream), with Model::Load's parameter-size check.
 //
-// usage: rlgpu_optim_lt save <out.lt> <state.f32> <step> <lr> <beta1> <beta2> <eps> <weight_decay> <shape>...
-//        rlgpu_optim_lt load <in.lt> <state.f32> <shape>...
+// usage: rlgpu_optim_lt save <out.lt> <state.f32> <step> <lr> <beta1> <beta2> <eps> <weight_decay> <shape>... [--optimizer NAME]
+//        rlgpu_optim_lt load <in.lt> <state.f32> <shape>... [--optimizer NAME]
 //        rlgpu_optim_lt model-save <out.lt> <params.f32> <obs> <out> <h1> [h2 ...] [--no-layer-norm] [--activation NAME]
 //        rlgpu_optim_lt model-load <in.lt> <params.f32> <obs> <out> <h1> [h2 ...] [--no-layer-norm] [--activation NAME]
 //   --no-layer-norm: ModelConfig::addLayerNorm = false (no LayerNorm modules: the module indices, the archive's
@@ -21,6 +21,11 @@
 //   shape: dimensions joined by 'x' (e.g. 384x167), one per model parameter in parameters() order;
 //   state.f32: every parameter's exp_avg (flat, parameter order), then every exp_avg_sq.  load writes
 //   it preceded by the step as an int64 (0 and zero moments for parameters without state).
+//   --optimizer adamw | adam | adagrad | rmsprop | magsgd (MakeOptimizer, Models.h:40-56; default adamw, and adam is
+//   written and read as adamw, as it always was): the libtorch class that writes / reads the archive.  state.f32 keeps
+//   its layout: torch::optim::Adagrad's sum and RMSprop's square_avg (no momentum, not centered: those buffers stay
+//   undefined) are the second half, the first half zeros; torch::optim::SGD at momentum 0 (MagSGD is an SGD) has no
+//   state -- its file is still written, so Model::Load finds one -- and loads as step 0 and zeros.
 #include <torch/torch.h>
 
 #include <cstdio>
@@ -130,10 +135,54 @@ int model_mode(bool save, int argc, char** argv) {
     return out ? 0 : 3;
 }
 
+// the flat state of one optimizer class: per parameter the step and one tensor (Adagrad's sum, RMSprop's square_avg),
+// kept in the second half of state.f32
+template <class Opt, class State, class Get>
+void put_state(Opt& opt, std::vector<torch::Tensor>& ps, std::vector<float>& buf, int64_t total, int64_t step, Get span) {
+    int64_t off = 0;
+    for (auto& p : ps) {
+        auto st = std::make_unique<State>();
+        st->step(step);
+        span(*st)(torch::from_blob(buf.data() + total + off, p.sizes(), torch::kFloat32).clone());
+        opt.state()[p.unsafeGetTensorImpl()] = std::move(st);
+        off += p.numel();
+    }
+}
+template <class Opt, class State, class Get>
+bool get_state(Opt& opt, std::vector<torch::Tensor>& ps, std::vector<float>& buf, int64_t total, int64_t& step, Get span) {
+    int64_t off = 0;
+    for (auto& p : ps) {
+        auto it = opt.state().find(p.unsafeGetTensorImpl());
+        if (it != opt.state().end()) {
+            auto& st = static_cast<State&>(*it->second);
+            step = st.step();
+            const torch::Tensor v = span(st).to(torch::kCPU).to(torch::kFloat32).contiguous();
+            if (v.numel() != p.numel()) return false;
+            std::copy(v.data_ptr<float>(), v.data_ptr<float>() + v.numel(), buf.begin() + total + off);
+        }
+        off += p.numel();
+    }
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     try {
+        // --optimizer NAME, anywhere after the mode
+        std::string optimizer = "adamw";
+        for (int i = 2; i + 1 < argc; i++)
+            if (std::string(argv[i]) == "--optimizer") {
+                optimizer = argv[i + 1];
+                for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+                argc -= 2;
+                break;
+            }
+        if (optimizer == "adam") optimizer = "adamw";
+        if (optimizer != "adamw" && optimizer != "adagrad" && optimizer != "rmsprop" && optimizer != "magsgd") {
+            std::cerr << "--optimizer must be adamw, adam, adagrad, rmsprop or magsgd\n";
+            return 2;
+        }
         if (argc < 4) return 2;
         const std::string mode = argv[1];
         if (mode == "model-save" || mode == "model-load") return model_mode(mode == "model-save", argc, argv);
@@ -151,6 +200,25 @@ int main(int argc, char** argv) {
             if (!in) {
                 std::cerr << "state file too short\n";
                 return 3;
+            }
+            if (optimizer != "adamw") {  // MakeOptimizer(type, parameters(), lr): the class's defaults but lr
+                torch::serialize::OutputArchive archive;
+                if (optimizer == "adagrad") {
+                    torch::optim::Adagrad opt(ps, torch::optim::AdagradOptions(lr));
+                    put_state<torch::optim::Adagrad, torch::optim::AdagradParamState>(
+                        opt, ps, buf, total, step, [](auto& st) { return [&st](torch::Tensor t) { st.sum(t); }; });
+                    opt.save(archive);
+                } else if (optimizer == "rmsprop") {
+                    torch::optim::RMSprop opt(ps, torch::optim::RMSpropOptions(lr));
+                    put_state<torch::optim::RMSprop, torch::optim::RMSpropParamState>(
+                        opt, ps, buf, total, step, [](auto& st) { return [&st](torch::Tensor t) { st.square_avg(t); }; });
+                    opt.save(archive);
+                } else {
+                    torch::optim::SGD opt(ps, torch::optim::SGDOptions(lr));  // MagSGD : SGD, momentum 0: no state
+                    opt.save(archive);
+                }
+                archive.save_to(argv[2]);
+                return 0;
             }
             // Model::Model: MakeOptimizer(AdamW, parameters(), lr) (Models.h:40-56)
             torch::optim::AdamW opt(ps, torch::optim::AdamWOptions(lr).betas({b1, b2}).eps(eps).weight_decay(wd));
@@ -170,6 +238,37 @@ int main(int argc, char** argv) {
         }
         if (mode == "load") {
             std::vector<torch::Tensor> ps = make_params(argv + 4, argc - 4);
+            if (optimizer != "adamw") {
+                int64_t step = 0, total = 0;
+                for (auto& p : ps) total += p.numel();
+                std::vector<float> buf((size_t)(2 * total), 0.f);
+                torch::serialize::InputArchive archive;
+                archive.load_from(argv[2]);
+                bool ok = true;
+                if (optimizer == "adagrad") {
+                    torch::optim::Adagrad opt(ps, torch::optim::AdagradOptions(1e-3));
+                    opt.state().clear();  // the constructor's zero sums: only what the file holds counts
+                    opt.load(archive);
+                    ok = get_state<torch::optim::Adagrad, torch::optim::AdagradParamState>(
+                        opt, ps, buf, total, step, [](auto& st) { return st.sum(); });
+                } else if (optimizer == "rmsprop") {
+                    torch::optim::RMSprop opt(ps, torch::optim::RMSpropOptions(1e-3));
+                    opt.load(archive);
+                    ok = get_state<torch::optim::RMSprop, torch::optim::RMSpropParamState>(
+                        opt, ps, buf, total, step, [](auto& st) { return st.square_avg(); });
+                } else {
+                    torch::optim::SGD opt(ps, torch::optim::SGDOptions(1e-3));
+                    opt.load(archive);
+                }
+                if (!ok) {
+                    std::cerr << "optimizer state does not match the parameter shapes\n";
+                    return 3;
+                }
+                std::ofstream out(argv[3], std::ios::binary);
+                out.write(reinterpret_cast<const char*>(&step), sizeof step);
+                out.write(reinterpret_cast<const char*>(buf.data()), (std::streamsize)(buf.size() * sizeof(float)));
+                return out ? 0 : 3;
+            }
             torch::optim::AdamW opt(ps, torch::optim::AdamWOptions(1e-3));
             torch::serialize::InputArchive archive;  // Model::Load (Models.cpp:177-180)
             archive.load_from(argv[2]);

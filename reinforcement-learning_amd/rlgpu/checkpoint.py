@@ -25,6 +25,14 @@ warning, Models.cpp:168-186).  Here the same archives are written and read by li
 (rlgpu/rlgpu_optim_lt, host/optim_archive.cpp), so a reference checkpoint resumes with its AdamW state
 and a GPU checkpoint resumes in the reference with ours.  The exact state (step, exp_avg, exp_avg_sq
 in the flat torch parameter order) is also kept in RLGPU_OPTIM.safetensors, which load() prefers.
+
+The other optimizers of ModelConfig::optimType keep their state in the same spans: Adagrad's `sum` and RMSprop's
+`square_avg` in exp_avg_sq (exp_avg stays zero), MagSGD none.  Their <NAME>_OPTIM.lt is written and read by the matching
+libtorch class (torch::optim::Adagrad, RMSprop, SGD: MagSGD is an SGD, and its stateless file is still written so the
+reference's Model::Load finds one).  RLGPU_OPTIM.safetensors records each model's type as <NAME>.optim_type (one
+int64, RLGPU_OPT_*); a file without the key holds Adam / AdamW state.  A stored type whose state the handle's optimizer
+cannot use (anything but Adam <-> AdamW) warns by name and resets that model's state, as the reference resets an
+optimizer whose file it cannot use.
 """
 import json
 import os
@@ -35,6 +43,24 @@ STATS_FILE = "RUNNING_STATS.json"          # Learner.cpp:221
 MODEL_NAMES = ("policy", "critic", "shared_head")  # PPOLearner model names (PPOLearner.cpp:42-74)
 OPTIM_FILE = "RLGPU_OPTIM.safetensors"
 OPTIM_TOOL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "rlgpu_optim_lt")
+OPTIMIZERS = {"adamw": 0, "adam": 1, "adagrad": 2, "rmsprop": 3, "magsgd": 4}  # RLGPU_OPT_* (rlgpu.ppo.OPTIMIZERS)
+
+
+def _optimizer_name(name):
+    if name not in OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, not {name!r}")
+    return name
+
+
+def _model_optimizers(ppo):
+    """The optimizer name of each model of a PPO (its optim_options; AdamW where it carries none)."""
+    names = (getattr(ppo, "optim_options", None) or {}).get("optimizer", ("adamw",) * 3)
+    return {mi: _optimizer_name(names[mi]) for mi in ppo.models}
+
+
+def _same_state(a, b):
+    """Whether optimizer b can use optimizer a's state: the same type, or Adam and AdamW (the same moments)."""
+    return a == b or {a, b} == {"adam", "adamw"}
 
 
 def model_path(folder, name, suffix=""):
@@ -53,9 +79,17 @@ def _shape_args(shapes):
     return ["x".join(str(int(d)) for d in s) for s in shapes]
 
 
-def write_optim_archive(path, shapes, step, lr, betas, eps, weight_decay, exp_avg, exp_avg_sq):
+def _optimizer_args(optimizer):
+    # the default stays the command line it always was
+    return [] if _optimizer_name(optimizer) == "adamw" else ["--optimizer", optimizer]
+
+
+def write_optim_archive(path, shapes, step, lr, betas, eps, weight_decay, exp_avg, exp_avg_sq, optimizer="adamw"):
     """<NAME>_OPTIM.lt via libtorch's AdamW::save (Models.cpp:122-125).  shapes: the model's parameter
-    shapes in parameters() order; exp_avg / exp_avg_sq: their moments, flat in that order."""
+    shapes in parameters() order; exp_avg / exp_avg_sq: their moments, flat in that order.  optimizer: the libtorch
+    class that writes the file -- "adamw" / "adam" (AdamW, as always), "adagrad" (Adagrad: step and sum = exp_avg_sq),
+    "rmsprop" (RMSprop: step and square_avg = exp_avg_sq) or "magsgd" (SGD, no state); betas, eps and weight_decay
+    matter to AdamW alone."""
     import subprocess
     import tempfile
 
@@ -68,7 +102,8 @@ def write_optim_archive(path, shapes, step, lr, betas, eps, weight_decay, exp_av
         tmp = f.name
     try:
         r = subprocess.run([OPTIM_TOOL, "save", path, tmp, str(int(step)), repr(float(lr)), repr(float(betas[0])),
-                            repr(float(betas[1])), repr(float(eps)), repr(float(weight_decay)), *_shape_args(shapes)],
+                            repr(float(betas[1])), repr(float(eps)), repr(float(weight_decay)), *_shape_args(shapes),
+                            *_optimizer_args(optimizer)],
                            capture_output=True, text=True)
     finally:
         os.unlink(tmp)
@@ -76,9 +111,11 @@ def write_optim_archive(path, shapes, step, lr, betas, eps, weight_decay, exp_av
         raise RuntimeError(f"writing {path} failed: {r.stderr.strip()}")
 
 
-def read_optim_archive(path, shapes):
+def read_optim_archive(path, shapes, optimizer="adamw"):
     """(step, exp_avg, exp_avg_sq) of a <NAME>_OPTIM.lt read by libtorch's AdamW::load
-    (Models.cpp:177-180) into parameters of `shapes`; parameters without state read as zeros."""
+    (Models.cpp:177-180) into parameters of `shapes`; parameters without state read as zeros.  optimizer: the
+    libtorch class that reads it, as in write_optim_archive; Adagrad's sum / RMSprop's square_avg come back as
+    exp_avg_sq with exp_avg zero, an SGD file as step 0 and zeros."""
     import subprocess
     import tempfile
 
@@ -88,7 +125,8 @@ def read_optim_archive(path, shapes):
     with tempfile.NamedTemporaryFile(suffix=".bin", delete=False) as f:
         tmp = f.name
     try:
-        r = subprocess.run([OPTIM_TOOL, "load", path, tmp, *_shape_args(shapes)], capture_output=True, text=True)
+        r = subprocess.run([OPTIM_TOOL, "load", path, tmp, *_shape_args(shapes), *_optimizer_args(optimizer)],
+                           capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"reading {path} failed: {r.stderr.strip()}")
         raw = open(tmp, "rb").read()
@@ -209,9 +247,11 @@ def save(learner, folder, keep=8):
     # while they are equal the file is what it always was ("step" alone, the policy's)
     steps = {mi: ppo.model_optimizer_step(mi) for mi in ppo.models}
     t = {"step": torch.tensor([step], dtype=torch.int64)}
+    kinds = _model_optimizers(ppo)
     for mi in ppo.models:
         name = MODEL_NAMES[mi]
         o, c = ppo.model_range(mi)
+        t[name + ".optim_type"] = torch.tensor([OPTIMIZERS[kinds[mi]]], dtype=torch.int64)
         if len(set(steps.values())) > 1:
             t[name + ".step"] = torch.tensor([steps[mi]], dtype=torch.int64)
         t[name + ".exp_avg"] = m[o:o + c].detach().cpu().contiguous()
@@ -225,7 +265,8 @@ def save(learner, folder, keep=8):
         for mi in ppo.models:
             name = MODEL_NAMES[mi]
             write_optim_archive(model_path(path, name, "_OPTIM"), shapes[mi], steps[mi], opts["lr"][mi], opts["betas"], opts["eps"],
-                                opts["weight_decay"], t[name + ".exp_avg"].numpy(), t[name + ".exp_avg_sq"].numpy())
+                                opts["weight_decay"], t[name + ".exp_avg"].numpy(), t[name + ".exp_avg_sq"].numpy(),
+                                optimizer=kinds[mi])
     if keep != -1:
         dirs = numbered_dirs(folder)
         while len(dirs) > keep:
@@ -278,17 +319,31 @@ def load(learner, folder, allow_missing_models=True):
         from safetensors.torch import load_file
         t = load_file(op)
         step, m, v = ppo.optimizer_state()
+        kinds = _model_optimizers(ppo)
+        names = {v_: k for k, v_ in OPTIMIZERS.items()}
+        reset = []
         for mi in ppo.models:
             name = MODEL_NAMES[mi]
             o, c = ppo.model_range(mi)
             if name + ".exp_avg" not in t or t[name + ".exp_avg"].numel() != c:
                 raise ValueError(f"optimizer state in {op} does not match the model sizes")
+            # a file without the key is Adam / AdamW
+            stored = names.get(int(t[name + ".optim_type"][0]), "unknown") if name + ".optim_type" in t else "adamw"
+            if not _same_state(stored, kinds[mi]):
+                warnings.warn(f'the optimizer state of model "{name}" in {op} is {stored}\'s and the model\'s optimizer is '
+                              f"{kinds[mi]}, optimizer will be reset")
+                m[o:o + c].zero_()
+                v[o:o + c].zero_()
+                reset.append(mi)
+                continue
             m[o:o + c].copy_(t[name + ".exp_avg"].to(m.device))
             v[o:o + c].copy_(t[name + ".exp_avg_sq"].to(v.device))
         ppo.set_optimizer_step(int(t["step"][0]))
         for mi in ppo.models:  # per-model counts, written when they differ
             if MODEL_NAMES[mi] + ".step" in t:
                 ppo.set_model_optimizer_step(mi, int(t[MODEL_NAMES[mi] + ".step"][0]))
+        for mi in reset:
+            ppo.set_model_optimizer_step(mi, 0)
     elif any(os.path.exists(model_path(path, MODEL_NAMES[mi], "_OPTIM")) for mi in ppo.models):
         # a reference checkpoint: its AdamW archives (Model::Load, Models.cpp:168-186); a model
         # without one resets its moments, as the reference resets that model's optimizer
@@ -310,7 +365,7 @@ def load(learner, folder, allow_missing_models=True):
                 v[o:o + c].zero_()
                 continue
             shapes = [tuple(q.shape) for q in ppo.torch_module(mi).parameters()]
-            s_, ea, eas = read_optim_archive(p, shapes)
+            s_, ea, eas = read_optim_archive(p, shapes, optimizer=_model_optimizers(ppo)[mi])
             m[o:o + c].copy_(torch.from_numpy(ea).to(m.device))
             v[o:o + c].copy_(torch.from_numpy(eas).to(v.device))
             steps.append(s_)

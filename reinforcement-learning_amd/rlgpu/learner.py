@@ -308,6 +308,7 @@ class LearnerConfig:
         self.frame_stack = 1              # K >= 2: stacked AdvancedObs frames (C4; no reference counterpart)
         self.activation = "leaky_relu"    # ModelConfig::activationType of every model: leaky_relu, relu, sigmoid, tanh
         self.layer_norm = True            # ModelConfig::addLayerNorm of every model
+        self.optimizer = "adamw"          # ModelConfig::optimType of every model: adamw, adam, adagrad, rmsprop, magsgd
         self.policy_temperature = 1.0     # PPOLearnerConfig::policyTemperature: collection, old versions and Learn
         self.mask_entropy = False         # PPOLearnerConfig::maskEntropy: entropy over log(legal actions) per row
         self.collect_groups = 0           # rollout collection in arena groups on their own streams and CU partitions
@@ -340,6 +341,8 @@ class LearnerConfig:
             if not hasattr(self, k):
                 raise AttributeError(f"unknown LearnerConfig field {k}")
             setattr(self, k, v)
+        from .ppo import optimizer_id
+        optimizer_id(self.optimizer)  # an unknown name is refused here, before anything is built
 
 
 class _CConfig(ctypes.Structure):
@@ -552,6 +555,8 @@ class Learner:
         c.arith = cfg.arith
         from .ppo import activation_id
         c.activation, c.no_layer_norm = activation_id(cfg.activation), int(not cfg.layer_norm)
+        from .ppo import optimizer_id
+        c.optimizer = optimizer_id(cfg.optimizer)
         c.collect_groups = cfg.collect_groups
         c.policy_temperature, c.mask_entropy = cfg.policy_temperature, int(cfg.mask_entropy)
         c.rank, c.world = rank, world
@@ -579,7 +584,9 @@ class Learner:
                             shared_layers=cfg.shared_layers, layer_norm=bool(cfg.layer_norm), activation=cfg.activation,
                             leaky_slope=0.0 if cfg.activation == "relu" else 0.01, infer_fp16=int(cfg.infer_fp16),
                             optim_options={"lr": (cfg.policy_lr, cfg.critic_lr, min(cfg.policy_lr, cfg.critic_lr)),
-                                           "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 1e-2})
+                                           "betas": (0.9, 0.999), "eps": 1e-8,
+                                           "weight_decay": 0.0 if cfg.optimizer == "adam" else 1e-2,
+                                           "optimizer": (cfg.optimizer,) * 3})
         r = _CRollout()
         _lib.check(L.rlgpu_learner_rollout(h, ctypes.byref(r)), "rlgpu_learner_rollout")
         T, P, W = r.T, r.P, r.obs_width

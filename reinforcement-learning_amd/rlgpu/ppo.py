@@ -46,6 +46,18 @@ GEMM_F32X6, GEMM_F32, GEMM_F16X3 = 0, 1, 2  # rlgpu_ppo_config.train_gemm (inclu
 ACTIVATIONS = {"leaky_relu": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
 
 
+# rlgpu_ppo_set_optimizer / rlgpu_learner_config.optimizer (RLGPU_OPT_*, ModelOptimType)
+OPTIMIZERS = {"adamw": 0, "adam": 1, "adagrad": 2, "rmsprop": 3, "magsgd": 4}
+OPTIMIZER_NAMES = {v: k for k, v in OPTIMIZERS.items()}
+
+
+def optimizer_id(name):
+    """RLGPU_OPT_* of an optimizer name."""
+    if name not in OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {sorted(OPTIMIZERS)}, not {name!r}")
+    return OPTIMIZERS[name]
+
+
 def activation_id(name):
     """RLGPU_ACT_* of an activation name."""
     if name not in ACTIVATIONS:
@@ -83,6 +95,8 @@ def _bind():
     L.rlgpu_ppo_set_optimizer_step.argtypes = [vp, i64]
     L.rlgpu_ppo_model_optimizer_step.argtypes = [vp, i32, ctypes.POINTER(i64)]
     L.rlgpu_ppo_set_model_optimizer_step.argtypes = [vp, i32, i64]
+    L.rlgpu_ppo_set_optimizer.argtypes = [vp, i32, i32]
+    L.rlgpu_ppo_get_optimizer.argtypes = [vp, i32, ctypes.POINTER(i32)]
     L.rlgpu_ppo_teacher_probs.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp, vp]
     L.rlgpu_teacher_probs_from_logits.argtypes = [vp, vp, i64, i32, vp, i32, f32, i32, vp, vp, vp, vp]
     L.rlgpu_ppo_transfer_chunk.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i64, i32, f32, f32, vp, vp]
@@ -120,12 +134,18 @@ class PPO:
                  layer_norm=True, policy_lr=2.5e-4, critic_lr=2.5e-4, clip_range=0.2, entropy_scale=0.035,
                  max_grad_norm=0.5, max_rows=50_000, seed=42, init=True, device="cuda:0",
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, leaky_slope=0.01, train_gemm=GEMM_F16X3,
-                 infer_fp16=False, shared_layers=(), policy_temperature=1.0, mask_entropy=False, activation="leaky_relu"):
+                 infer_fp16=False, shared_layers=(), policy_temperature=1.0, mask_entropy=False, activation="leaky_relu",
+                 optimizer="adamw"):
         """activation (ModelConfig::activationType of every model): "leaky_relu" (with leaky_slope), "relu", "sigmoid"
-        or "tanh".  policy_temperature (PPOLearnerConfig::policyTemperature): sampling and the minibatch loss divide the
+        or "tanh".  optimizer (ModelConfig::optimType of every model): "adamw", "adam" (AdamW's arithmetic with
+        weight_decay 0), "adagrad", "rmsprop" or "magsgd" (libtorch's defaults, rlgpu_ppo_set_optimizer; set_optimizer
+        changes one model's before its first step).  policy_temperature (PPOLearnerConfig::policyTemperature): sampling and the minibatch loss divide the
         logits by it (0 = the C default, 1).  mask_entropy (maskEntropy): each row's entropy over log(its legal
         actions) instead of log(num_actions)."""
         import torch
+        opt_type = optimizer_id(optimizer)
+        if optimizer == "adam":
+            weight_decay = 0.0
         if not torch.cuda.is_available():
             raise _lib.RLGPUError("PPO needs an MI355X: the product path has no CPU fallback")
         L = _bind()
@@ -154,9 +174,11 @@ class PPO:
         _lib.check(L.rlgpu_ppo_create(ctypes.byref(c), ctypes.byref(h)), "rlgpu_ppo_create")
         self._h = h
         self.cfg = c
-        # AdamW options per model (checkpoint.py's *_OPTIM.lt): the shared head steps at min(LR)
+        # optimizer options per model (checkpoint.py's *_OPTIM.lt): the shared head steps at min(LR)
         self.optim_options = {"lr": (policy_lr, critic_lr, min(policy_lr, critic_lr)), "betas": tuple(betas), "eps": eps,
-                              "weight_decay": weight_decay}
+                              "weight_decay": weight_decay, "optimizer": (optimizer,) * 3}
+        if opt_type != OPTIMIZERS["adamw"]:
+            _lib.check(L.rlgpu_ppo_set_optimizer(h, -1, opt_type), "rlgpu_ppo_set_optimizer")
         self.obs_size, self.num_actions = obs_size, num_actions
         self.policy_layers, self.critic_layers, self.layer_norm = tuple(policy_layers), tuple(critic_layers), layer_norm
         self.shared_layers = tuple(shared_layers)
@@ -205,6 +227,25 @@ class PPO:
     _guided = False  # a guide was used since the metrics were last reset: read_metrics reports "Guiding Loss"
     infer_fp16 = 0
     optim_options = None
+
+    def set_optimizer(self, model, optimizer):
+        """rlgpu_ppo_set_optimizer: the optimizer (a name of OPTIMIZERS) of one model (0 policy, 1 critic, 2 shared
+        head) or of every model (-1), before that model's first step.  "adam" and "adamw" both mean the handle's Adam
+        arithmetic with its weight_decay."""
+        t = optimizer_id(optimizer)
+        _lib.check(_bind().rlgpu_ppo_set_optimizer(self._h, int(model), t), "rlgpu_ppo_set_optimizer")
+        if self.optim_options is not None:
+            names = list(self.optim_options.get("optimizer", ("adamw",) * 3))
+            for mi in range(3):
+                if model < 0 or model == mi:
+                    names[mi] = optimizer
+            self.optim_options["optimizer"] = tuple(names)
+
+    def get_optimizer(self, model):
+        """The optimizer name of one model (rlgpu_ppo_get_optimizer)."""
+        t = ctypes.c_int32()
+        _lib.check(_bind().rlgpu_ppo_get_optimizer(self._h, int(model), ctypes.byref(t)), "rlgpu_ppo_get_optimizer")
+        return OPTIMIZER_NAMES[t.value]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -521,7 +562,7 @@ class PPO:
             _lib.ptr(self.metrics), _lib.stream_ptr()), "rlgpu_ppo_transfer_chunk")
 
     def transfer_step(self, lr):
-        """rlgpu_ppo_transfer_step: AdamW at learning rate lr on the policy and the shared head, no gradient clipping; the
+        """rlgpu_ppo_transfer_step: AdamW (or the models' optimizer) at learning rate lr on the policy and the shared head, no gradient clipping; the
         critic, its moments and its step count stay."""
         _lib.check(_lib.lib().rlgpu_ppo_transfer_step(self._h, lr, _lib.stream_ptr()), "rlgpu_ppo_transfer_step")
 
