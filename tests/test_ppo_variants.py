@@ -256,6 +256,13 @@ OPT = dict(policy_lr=1e-3, critic_lr=3e-4, weight_decay=0.05)
 OPT_SHARE = 1e-4
 
 
+def adamw_optimizers(param_lists, lrs, weight_decay):
+    """The AdamW statement of the optimizer tests (and of learn_reference.optimizer_step_ref): one torch.optim.AdamW
+    per model with nothing but its lr and the weight decay set."""
+    import torch
+    return [torch.optim.AdamW(ps, lr=lr, weight_decay=weight_decay) for ps, lr in zip(param_lists, lrs)]
+
+
 def optimizer_reference(max_norm, steps=2):
     """Two AdamW steps after clip_grad_norm_ in float64 and in torch fp32: per step the batches, the gradient norms
     (policy, critic) and the fp32 gradient error; the final flat parameters of both."""
@@ -265,8 +272,7 @@ def optimizer_reference(max_norm, steps=2):
     tr = {}
     for dt in (torch.float64, torch.float32):
         ms = [copy.deepcopy(m).to(dt) for m in mods]
-        opts = [torch.optim.AdamW(ms[0].parameters(), lr=OPT["policy_lr"], weight_decay=OPT["weight_decay"]),
-                torch.optim.AdamW(ms[1].parameters(), lr=OPT["critic_lr"], weight_decay=OPT["weight_decay"])]
+        opts = adamw_optimizers([m.parameters() for m in ms], (OPT["policy_lr"], OPT["critic_lr"]), OPT["weight_decay"])
         norms, grads, batches = [], [], []
         for it in range(steps):
             b = build_batch(c, copy.deepcopy(mods[0]).double(), seed=100 + it)
