@@ -396,6 +396,15 @@ int rlgpu_envset_build_obs(rlgpu_envset* env, void* stream);
  * NULL disables (the default).  capacity: entries of d_counters (>= 64 + 24 * workgroups + arenas, else
  * RLGPU_ERR_INVALID_ARG). */
 int rlgpu_envset_set_profile(rlgpu_envset* env, unsigned long long* d_counters, int64_t capacity);
+/* Diagnostics of the collection loop: when d_slots (uint64, device, RLGPU_COLLECT_SPLIT_SLOTS x workgroups, a
+ * workgroup is 4 arenas) is non-NULL, rlgpu_envset_collect_loop launches its profiled instantiation, in which lane 0
+ * of every workgroup adds the 100 MHz wall-clock ticks of each part of each step to d_slots[workgroup *
+ * RLGPU_COLLECT_SPLIT_SLOTS + part]: 0 the forward's staging of its obs and mask rows, 1 the rest of the forward,
+ * 2 the barrier after it, 3 the record load, 4 the env step body, 5 the record store's issue, 6 the barrier that ends
+ * the step.  The outputs are the default instantiation's bit for bit.  NULL (the default) selects the default
+ * instantiation, which carries no trace of this.  The caller zeroes the buffer and keeps it alive while it is set. */
+#define RLGPU_COLLECT_SPLIT_SLOTS 8
+int rlgpu_envset_set_collect_split(rlgpu_envset* env, unsigned long long* d_slots, int64_t capacity);
 
 /* ExampleMain's StepCallback metrics on the device.  Replaces the StepCallbackFn that
  * Learner::Start calls after every StepSecondHalf (GL/public/GigaLearnCPP/Learner.h:11,

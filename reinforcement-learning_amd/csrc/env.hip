@@ -222,6 +222,7 @@ struct rlgpu_envset {
     float *d_obs = nullptr, *d_rewards = nullptr, *d_last_rewards = nullptr, *d_trunc_obs = nullptr;
     uint8_t *d_masks = nullptr, *d_terminals = nullptr;
     unsigned long long* d_prof = nullptr;  // the caller's (rlgpu_envset_set_profile), not owned
+    unsigned long long* d_split = nullptr;  // the caller's (rlgpu_envset_set_collect_split), not owned
     double* d_metrics = nullptr;   // StepCallback slots [num_arenas][RLGPU_STEP_METRIC_SLOTS] or null
     uint64_t metric_calls = 0;     // ExampleMain's stepCounter
     bool metric_players = false;   // this step's player-metrics flag (launch)
@@ -745,6 +746,16 @@ extern "C" int rlgpu_envset_set_profile(rlgpu_envset* e, unsigned long long* d_c
     });
 }
 
+extern "C" int rlgpu_envset_set_collect_split(rlgpu_envset* e, unsigned long long* d_slots, int64_t capacity) {
+    return rlgpu::guarded([&] {
+        RLGPU_REQUIRE(e, "null envset");
+        const int64_t need = (int64_t)rl::kSplitSlots * rlgpu::ceil_div(e->cfg.num_arenas, rl::kArenas);
+        RLGPU_REQUIRE(!d_slots || capacity >= need, "rlgpu_envset_set_collect_split: buffer of " + std::to_string(capacity) +
+                                                        " slots, needs " + std::to_string(need));
+        e->d_split = d_slots;
+    });
+}
+
 namespace {
 const char* const kStepMetricNames[RLGPU_NUM_STEP_METRICS] = {
     "Player/In Air Ratio", "Player/Ball Touch Ratio", "Player/Demoed Ratio", "Player/Speed",
@@ -937,6 +948,7 @@ extern "C" int rlgpu_envset_collect_loop(rlgpu_envset* e, rlgpu_ppo* policy, int
         }
         c.T = steps;
         c.P = P;
+        c.split = e->d_split;
         bool f16 = false;
         rlgpu::ppo_wave_args(policy, ro->obs, ro->masks, P, deterministic, rng_step, ro->actions, ro->logp, c.inf.b,
                              sizeof c.inf.b, &f16);

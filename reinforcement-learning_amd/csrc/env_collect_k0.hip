@@ -29,8 +29,14 @@ void env_collect_k0_upload(const EnvConst& k, const RsqrtLut* lut) {
     if (lut) RLGPU_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(kRsqrtLut), lut, sizeof *lut));
 }
 void env_collect_k0_launch(const CollectArgs& c, bool f16, int blocks, hipStream_t s) {
-    if (f16) hipLaunchKernelGGL(env_collect_a0<true>, dim3(blocks), dim3(kWG), 0, s, c);
-    else hipLaunchKernelGGL(env_collect_a0<false>, dim3(blocks), dim3(kWG), 0, s, c);
+    // c.split selects the profiled instantiation (env_step.hpp SplitClock)
+    if (c.split) {
+        if (f16) hipLaunchKernelGGL((env_collect_a0<true, true>), dim3(blocks), dim3(kWG), 0, s, c);
+        else hipLaunchKernelGGL((env_collect_a0<false, true>), dim3(blocks), dim3(kWG), 0, s, c);
+    } else {
+        if (f16) hipLaunchKernelGGL((env_collect_a0<true, false>), dim3(blocks), dim3(kWG), 0, s, c);
+        else hipLaunchKernelGGL((env_collect_a0<false, false>), dim3(blocks), dim3(kWG), 0, s, c);
+    }
     RLGPU_CHECK_HIP(hipGetLastError());
 }
 }  // namespace rl

@@ -67,7 +67,16 @@ struct CollectArgs {
     int metric_calls;  // the set's StepCallback call counter at launch, mod 4 (step t is call metric_calls + t + 1)
     int64_t P;         // players per rollout row
     InferBlob inf;
+    // null, or [workgroups][kSplitSlots] (zeroed by the caller): the launch runs the profiled instantiation, whose
+    // workgroups add up where their steps' time went (rlgpu_envset_set_collect_split, tools/collect_loop_split.py)
+    unsigned long long* split;
 };
+// CollectArgs::split, per workgroup: the sum over the T steps, in ticks of the 100 MHz wall clock as the workgroup's
+// lane 0 reads it.  forward = staging (the obs and mask rows read back and converted) + the layers and the sampler;
+// sync_a = the barrier after the forward (its action stores drain); load = the records staged into LDS up to their
+// barrier; body = the env step up to the record write-back; store = the write-back's issue; sync_b = the barrier that
+// ends the step (the stores of the step drain).
+enum { kSplitStage = 0, kSplitForward, kSplitSyncA, kSplitLoad, kSplitBody, kSplitStore, kSplitSyncB, kSplitSlots = 8 };
 
 #if defined(RLGPU_ENV_KERNEL) || defined(RLGPU_ENV_COLLECT_KERNEL)
 
@@ -428,10 +437,12 @@ DEV void copy_rows(ArenaLDS* A, const Plugins* B, int l, int arena, float* obs, 
 }
 
 #ifdef RLGPU_ENV_KERNEL
+#define RLGPU_BODY_STAMP(k)
 __global__ void __launch_bounds__(kWG) RLGPU_ENV_KERNEL(StepArgs g) {
     __shared__ ArenaLDS lds[kArenas];
 #include "env_step_body.inc"
 }
+#undef RLGPU_BODY_STAMP
 #endif
 
 #ifdef RLGPU_ENV_COLLECT_KERNEL
@@ -442,38 +453,127 @@ __global__ void __launch_bounds__(kWG) RLGPU_ENV_KERNEL(StepArgs g) {
 // arenas (env_step_body.inc), which appends row t + 1.  What a step reads was written by this workgroup (its rows of the rollout, its records) or is
 // constant during the launch (weights, mesh), so the steps of different workgroups need no order among them.  The
 // inference buffers alias the arena staging area: between two steps the records are in HBM.
-template <bool F16>
+//
+// The forward and the step body are functions of their own.  Between two steps almost nothing is live, so a call there
+// costs little, and a called function gets a register allocation of its own: inlined into one loop, the body's
+// launch-invariant values stay in registers across the forward and the forward's weight fragments across the body,
+// and the kernel spills (profiles/collect_loop_codegen.txt).  RLGPU_COLLECT_CALLS says which
+// of the two are called (bit 0: the forward, bit 1: the body), RLGPU_COLLECT_BATCH whether the forward stages its rows
+// with batched loads (infer::wave_infer); the defaults are what measured best, the command line may set others.
+// A called function reads the launch arguments where the kernel does, in the kernel argument segment (CollectArgs is
+// the kernel's only parameter, so it starts the segment: collect_args), and the staging area by its name: both keep
+// their address spaces, which a pointer parameter would lose.
+#ifndef RLGPU_COLLECT_CALLS
+#define RLGPU_COLLECT_CALLS 3
+#endif
+#ifndef RLGPU_COLLECT_BATCH
+#define RLGPU_COLLECT_BATCH 1
+#endif
+#ifndef RLGPU_COLLECT_FN_ATTR  // further attributes of the called functions
+#define RLGPU_COLLECT_FN_ATTR
+#endif
+#if RLGPU_COLLECT_CALLS & 1
+#define RLGPU_COLLECT_FWD __device__ __noinline__ RLGPU_COLLECT_FN_ATTR
+#else
+#define RLGPU_COLLECT_FWD DEV
+#endif
+#if RLGPU_COLLECT_CALLS & 2
+#define RLGPU_COLLECT_BODY __device__ __noinline__ RLGPU_COLLECT_FN_ATTR
+#else
+#define RLGPU_COLLECT_BODY DEV
+#endif
+
+static __shared__ ArenaLDS g_collect_lds[kArenas];
+// The launch arguments as a called function finds them.  The kernel argument segment's own address is null inside a
+// called function (only kernels get it); the address of the implicit arguments is passed on, and they follow the
+// explicit ones at the next multiple of 8 bytes.
+static_assert(sizeof(CollectArgs) % 8 == 0, "the implicit kernel arguments start where CollectArgs ends");
+DEV const CollectArgs& collect_args() {
+    typedef const __attribute__((address_space(4))) char* KernargBytes;
+    return *(const CollectArgs*)((KernargBytes)__builtin_amdgcn_implicitarg_ptr() - sizeof(CollectArgs));
+}
+
+// The profiled instantiation's clock (CollectArgs::split): mark(k) adds the time since the previous mark to the
+// workgroup's slot k.  An add that returns nothing: the wave does not wait for it.  The default instantiation's clock
+// is empty: it holds nothing, is passed in no register and leaves no instruction.
+template <bool ON>
+struct SplitClock;
+template <>
+struct SplitClock<false> {
+    static constexpr bool kOn = false;
+    DEV void mark(int) {}
+};
+template <>
+struct SplitClock<true> {
+    static constexpr bool kOn = true;
+    unsigned long long* slot;
+    unsigned long long last;
+    DEV void mark(int k) {
+        const unsigned long long now = wall_clock64();
+        if (threadIdx.x == 0) atomicAdd(slot + k, now - last);
+        last = wall_clock64();
+    }
+};
+
+// step t's policy forward of the workgroup's rows of rollout row t
+template <bool F16, bool SPLIT>
+RLGPU_COLLECT_FWD SplitClock<SPLIT> collect_forward(int t, SplitClock<SPLIT> clk) {
+    const CollectArgs& c = collect_args();
+    const infer::InferArgs& a = *reinterpret_cast<const infer::InferArgs*>(c.inf.b);
+    infer::WaveLDS& S = *reinterpret_cast<infer::WaveLDS*>(g_collect_lds);
+    const int64_t P = c.P, r0 = (int64_t)blockIdx.x * infer::WR;
+    const int rows = (int)(P - r0 < infer::WR ? P - r0 : infer::WR), A = a.width[a.nl];
+    const int64_t row = (int64_t)t * P + r0;  // this workgroup's first row of rollout row t
+    // rows of t > 0 were stored by this workgroup in the previous trip: the barrier that ended it made them visible
+    infer::wave_infer<F16, mlp::ACT_LEAKY, RLGPU_COLLECT_BATCH != 0>(a, S, a.X + row * a.in, a.masks + row * A, rows, a.row0 + r0,
+                                                                a.step + t, a.row_sel ? a.row_sel + r0 : nullptr, a.act + row,
+                                                                a.logp ? a.logp + row : nullptr, nullptr, (int)threadIdx.x, &clk);
+    clk.mark(kSplitForward);
+    return clk;
+}
+
+// step t's env step of the workgroup's arenas, which appends rollout row t + 1
+template <bool SPLIT>
+RLGPU_COLLECT_BODY SplitClock<SPLIT> collect_body(int t, SplitClock<SPLIT> clk) {
+    const CollectArgs& c = collect_args();
+    ArenaLDS(&lds)[kArenas] = g_collect_lds;
+    StepArgs s = c.g;
+    const int64_t tp = (int64_t)t * c.P;
+    s.actions = c.g.actions + tp;
+    if (s.out_obs) s.out_obs = c.g.out_obs + tp * c.g.plug->obs_w;
+    if (s.out_masks) s.out_masks = c.g.out_masks + tp * RLGPU_ACTIONS;
+    if (s.out_rew) s.out_rew = c.g.out_rew + tp;
+    if (s.out_term) s.out_term = c.g.out_term + tp;
+    if (s.out_trunc) s.out_trunc = c.g.out_trunc + tp * c.g.plug->obs_w;
+    // ExampleMain's every-4th-call flag: the set's call counter at launch plus this step (env.hip launch())
+    if (s.metrics) s.metrics_players = (c.metric_calls + t + 1) % 4 == 0;
+#define RLGPU_BODY_STAMP(k) clk.mark(k);
+    {
+        const StepArgs& g = s;
+#include "env_step_body.inc"
+    }
+#undef RLGPU_BODY_STAMP
+    clk.mark(kSplitStore);
+    return clk;
+}
+
+template <bool F16, bool SPLIT>
 __global__ void __launch_bounds__(kWG) RLGPU_ENV_COLLECT_KERNEL(CollectArgs c) {
-    __shared__ ArenaLDS lds[kArenas];
     static_assert(sizeof(infer::WaveLDS) <= sizeof(ArenaLDS) * kArenas, "the inference buffers fit the arena staging area");
     static_assert(sizeof(infer::InferArgs) <= sizeof(c.inf) && alignof(infer::InferArgs) <= alignof(InferBlob), "InferBlob");
     static_assert(infer::WR == 4 * kArenas, "a workgroup's players are one wave's rows");
-    const infer::InferArgs& a = *reinterpret_cast<const infer::InferArgs*>(c.inf.b);
-    infer::WaveLDS& S = *reinterpret_cast<infer::WaveLDS*>(lds);
-    const int64_t P = c.P, r0 = (int64_t)blockIdx.x * infer::WR;
-    const int rows = (int)(P - r0 < infer::WR ? P - r0 : infer::WR), A = a.width[a.nl];
+    SplitClock<SPLIT> clk;
+    if constexpr (SPLIT) {
+        clk.slot = c.split + (size_t)blockIdx.x * kSplitSlots;
+        clk.last = wall_clock64();
+    }
     for (int t = 0; t < c.T; t++) {
-        const int64_t row = (int64_t)t * P + r0;  // this workgroup's first row of rollout row t
-        // rows of t > 0 were stored by this workgroup in the previous trip: the barrier that ended it made them visible
-        infer::wave_infer<F16, mlp::ACT_LEAKY>(a, S, a.X + row * a.in, a.masks + row * A, rows, a.row0 + r0, a.step + t,
-                                                a.row_sel ? a.row_sel + r0 : nullptr, a.act + row, a.logp ? a.logp + row : nullptr,
-                                                nullptr, (int)threadIdx.x);
+        clk = collect_forward<F16, SPLIT>(t, clk);
         sync();  // the actions are stored (the step reads them back), the inference buffers are free
-        StepArgs s = c.g;
-        const int64_t tp = (int64_t)t * P;
-        s.actions = c.g.actions + tp;
-        if (s.out_obs) s.out_obs = c.g.out_obs + tp * c.g.plug->obs_w;
-        if (s.out_masks) s.out_masks = c.g.out_masks + tp * RLGPU_ACTIONS;
-        if (s.out_rew) s.out_rew = c.g.out_rew + tp;
-        if (s.out_term) s.out_term = c.g.out_term + tp;
-        if (s.out_trunc) s.out_trunc = c.g.out_trunc + tp * c.g.plug->obs_w;
-        // ExampleMain's every-4th-call flag: the set's call counter at launch plus this step (env.hip launch())
-        if (s.metrics) s.metrics_players = (c.metric_calls + t + 1) % 4 == 0;
-        {
-            const StepArgs& g = s;
-#include "env_step_body.inc"
-        }
+        clk.mark(kSplitSyncA);
+        clk = collect_body<SPLIT>(t, clk);
         sync();  // the records and the rollout rows are stored; the staging area is free for the next forward
+        clk.mark(kSplitSyncB);
     }
 }
 #endif  // RLGPU_ENV_COLLECT_KERNEL

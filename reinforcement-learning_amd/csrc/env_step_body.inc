@@ -20,6 +20,7 @@
         }
     }
     sync(); P.mark(11);
+    RLGPU_BODY_STAMP(kSplitLoad)  // empty but in the collection loop's profiled instantiation (env_step.hpp)
     if (valid && l < 5) {
         A->a.force[l] = zero3();
         A->a.torque[l] = zero3();
@@ -227,6 +228,7 @@
         sync(); P.mark(14);
     }
     // ---- write the records back
+    RLGPU_BODY_STAMP(kSplitBody)
     {
         int first = blockIdx.x * kArenas;
         int cnt = g.n - first < kArenas ? g.n - first : kArenas;

@@ -443,6 +443,14 @@ struct WaveLDS {
     uint8_t Sel[WR];                 // mode 1: row is written
 };
 
+// wave_infer's optional stamp hook (the collection loop's profiled instantiation, env_step.hpp): mark(kStampStaged)
+// when the obs rows and masks are staged.  The default does nothing and leaves no code.
+struct NoStamp {
+    static constexpr bool kOn = false;
+    DEV void mark(int) {}
+};
+constexpr int kStampStaged = 0;
+
 // acc[c] = Xs[rows 0..15 | 16 zero rows] . W[column tile min(jt0 + c, JT - 1)]^T; tiles jt0 + c >= JT skip their MFMAs
 template <int NC, bool F16>
 DEV void linear_tiles_wave(const uint16_t (*Xs)[IPITCH], const uint16_t* F, int KS, int jt0, int JT, int lane,
@@ -495,30 +503,73 @@ DEV void linear_tiles_wave(const uint16_t (*Xs)[IPITCH], const uint16_t* F, int 
 // The forward of `rows` <= WR rows by the calling wave (64 lanes, all of them call): X [rows][a.in] f32 obs, masks
 // [rows][outputs] (mode 1), row0 the global number of row 0 (the sampler's Philox counter) and `step` its step;
 // row_sel / act / logp / out_f are the rows' own (indexed from row 0).  The network is a's (P, F, widths, offsets,
-// slope, use_ln, mode, det, temp, seed, sel); a's row pointers, n, row0 and step are not read.
-template <bool F16, int ACT>
+// slope, use_ln, mode, det, temp, seed, sel); a's row pointers, n, row0 and step are not read.  BATCH (the collection
+// loop, where no other wave hides a load's latency): the obs and mask rows are staged with all loads of a group of
+// columns issued before the first conversion -- one round trip to memory, not one per element; the values and their
+// conversion are the same.  stamp: see NoStamp.
+template <bool F16, int ACT, bool BATCH = false, class Stamp = NoStamp>
 DEV void wave_infer(const InferArgs& a, WaveLDS& S, const float* X, const uint8_t* masks, int rows, int64_t row0,
-                    uint64_t step, const uint8_t* row_sel, int32_t* act, float* logp, float* out_f, int lane) {
+                    uint64_t step, const uint8_t* row_sel, int32_t* act, float* logp, float* out_f, int lane,
+                    Stamp* stamp = nullptr) {
     uint16_t (*in)[IPITCH] = S.X[0];
     uint16_t (*out)[IPITCH] = S.X[1];
     const int A = a.width[a.nl];
     {  // obs -> 16-bit (mlp::rows_to_bf16), zeros past `in` up to the first MFMA step boundary and in the rows past `rows`
         const int k16 = (a.in + 15) / 16 * 16;
-#pragma unroll 4
-        for (int r = 0; r < WR; r++)
-            for (int c = lane; c < k16; c += 64) {
-                const float x = X[(int64_t)min(r, rows - 1) * a.in + min(c, a.in - 1)];
-                in[r][c] = (r < rows && c < a.in) ? f2h<F16>(x) : (uint16_t)0;
+        if constexpr (BATCH) {
+            constexpr int CB = 3;  // 64-column batches per trip: 48 loads in flight per lane
+            for (int c0 = lane; c0 < k16; c0 += 64 * CB) {
+                float x[WR][CB];
+#pragma unroll
+                for (int r = 0; r < WR; r++)
+#pragma unroll
+                    for (int j = 0; j < CB; j++)
+                        x[r][j] = X[(int64_t)min(r, rows - 1) * a.in + min(c0 + 64 * j, a.in - 1)];
+#pragma unroll
+                for (int r = 0; r < WR; r++)
+#pragma unroll
+                    for (int j = 0; j < CB; j++) {
+                        const int c = c0 + 64 * j;
+                        if (c < k16) in[r][c] = (r < rows && c < a.in) ? f2h<F16>(x[r][j]) : (uint16_t)0;
+                    }
             }
+        } else {
+#pragma unroll 4
+            for (int r = 0; r < WR; r++)
+                for (int c = lane; c < k16; c += 64) {
+                    const float x = X[(int64_t)min(r, rows - 1) * a.in + min(c, a.in - 1)];
+                    in[r][c] = (r < rows && c < a.in) ? f2h<F16>(x) : (uint16_t)0;
+                }
+        }
     }
     if (a.mode == 1) {
-        for (int f = lane; f < rows * A; f += 64) S.M[f] = masks[f];
+        if constexpr (BATCH) {
+            const int nb = rows * A;
+            if (nb >= 4 && (reinterpret_cast<uintptr_t>(masks) & 3) == 0) {  // whole words, all loads first; then the tail bytes
+                constexpr int MW = (WR * ppo::kMaxA + 255) / 256;            // words per lane
+                const uint32_t* mw = reinterpret_cast<const uint32_t*>(masks);
+                uint32_t* sw = reinterpret_cast<uint32_t*>(S.M);
+                const int nw = nb / 4;
+                uint32_t w[MW];
+#pragma unroll
+                for (int j = 0; j < MW; j++) w[j] = mw[min(lane + 64 * j, nw - 1)];
+#pragma unroll
+                for (int j = 0; j < MW; j++)
+                    if (lane + 64 * j < nw) sw[lane + 64 * j] = w[j];
+                for (int f = nw * 4 + lane; f < nb; f += 64) S.M[f] = masks[f];
+            } else {
+                for (int f = lane; f < nb; f += 64) S.M[f] = masks[f];
+            }
+        } else {
+            for (int f = lane; f < rows * A; f += 64) S.M[f] = masks[f];
+        }
         if (lane < WR) {
             uint8_t selv = 1;
             if (row_sel) selv = (row_sel[min(lane, rows - 1)] != 0) == (a.sel != 0);
             S.Sel[lane] = lane < rows && selv;
         }
     }
+    if constexpr (Stamp::kOn) stamp->mark(kStampStaged);
     f32x16 acc[WNC];
     for (int l = 0; l + 1 < a.nl; l++) {
         const int KS = (a.width[l] + 15) / 16, N = a.width[l + 1], JT = (N + 31) / 32;
