@@ -130,4 +130,20 @@ namespace rlgpu {
 bool ppo_wave_policy(rlgpu_ppo* h, int obs_size, int num_actions);
 void ppo_wave_args(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int64_t n, int deterministic, uint64_t rng_step,
                    int32_t* d_actions, float* d_logp, void* blob, size_t cap, bool* f16);
+// ppo.hip, for infer_unit.hip (rlgpu_infer_unit_*): the handle's obs / action widths, and the handle's own sampling
+// path (fused, layered or fp32, in chunks of max_rows) over n rows numbered from row0 + sample_row_offset with
+// `temperature` in place of the handle's policy_temperature
+void ppo_widths(rlgpu_ppo* h, int* obs_size, int* num_actions);
+void ppo_infer_actions_temp(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int64_t n, int64_t row0,
+                            int deterministic, float temperature, uint64_t rng_step, int32_t* d_actions, float* d_logp,
+                            hipStream_t s);
+}  // namespace rlgpu
+
+// env.hip, for infer_unit.hip: a config's obs builder as the kernels read it (the obs_* fields of rl::Plugins at
+// `plugins`, validated as rlgpu_envset_create validates them; seed keys DefaultObsPadded's shuffles), and
+// DefaultAction's table [RLGPU_ACTIONS][8] with its mask bits [RLGPU_ACTIONS] (rl::EnvConst::action / mask_bits)
+namespace rlgpu {
+void obs_builder_plugins(int kind, int max_players, const float pos_coef[3], float vel_coef, float ang_vel_coef, uint64_t seed,
+                         void* plugins);
+void default_action_tables(float* action, uint8_t* mask_bits);
 }  // namespace rlgpu

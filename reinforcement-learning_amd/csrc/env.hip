@@ -443,6 +443,24 @@ void obs_builder_from(const rlgpu_envset_config* cfg, rl::Plugins& p) {
 }
 }  // namespace
 
+// infer_unit.hip's view of the obs builder and of DefaultAction (common.hpp)
+void rlgpu::obs_builder_plugins(int kind, int max_players, const float pos_coef[3], float vel_coef, float ang_vel_coef,
+                                uint64_t seed, void* plugins) {
+    rlgpu_envset_config cfg{};
+    cfg.obs_builder = kind;
+    cfg.obs_max_players = max_players;
+    for (int i = 0; i < 3; i++) cfg.obs_pos_coef[i] = pos_coef[i];
+    cfg.obs_vel_coef = vel_coef;
+    cfg.obs_ang_vel_coef = ang_vel_coef;
+    cfg.seed = seed;
+    obs_builder_from(&cfg, *static_cast<rl::Plugins*>(plugins));
+}
+void rlgpu::default_action_tables(float* action, uint8_t* mask_bits) {
+    const rl::EnvConst k = rl::make_env_const();
+    std::memcpy(action, k.action, sizeof k.action);
+    std::memcpy(mask_bits, k.mask_bits, sizeof k.mask_bits);
+}
+
 extern "C" int rlgpu_obs_builder_size(int32_t kind, int32_t max_players) {
     int w = -1;
     const int rc = rlgpu::guarded([&] { w = obs_builder_width(kind, max_players); });

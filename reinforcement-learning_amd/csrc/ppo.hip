@@ -1370,6 +1370,27 @@ void rlgpu::ppo_wave_args(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_mas
     *f16_out = f16(h);
 }
 
+void rlgpu::ppo_widths(rlgpu_ppo* h, int* obs_size, int* num_actions) {
+    RLGPU_REQUIRE(h, "null policy handle");
+    *obs_size = h->cfg.obs_size;
+    *num_actions = h->cfg.num_actions;
+}
+// fused_args and sample_pass read the temperature from the handle's config: it holds the call's for the time of the
+// enqueue (a handle is used from one thread at a time, as everywhere in this ABI)
+void rlgpu::ppo_infer_actions_temp(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int64_t n, int64_t row0,
+                                   int deterministic, float temperature, uint64_t rng_step, int32_t* d_actions, float* d_logp,
+                                   hipStream_t s) {
+    RLGPU_REQUIRE(h && d_obs && d_masks && d_actions && n >= 0 && row0 >= 0, "ppo_infer_actions_temp: bad argument");
+    struct Restore {
+        float& slot;
+        float old;
+        ~Restore() { slot = old; }
+    } restore{h->cfg.policy_temperature, h->cfg.policy_temperature};
+    h->cfg.policy_temperature = temperature;
+    infer_policy(h, Rows{d_obs, n, row0 + h->cfg.sample_row_offset, d_masks}, Draw{deterministic, rng_step, d_actions, d_logp},
+                 nullptr, h->cfg.max_rows, s);
+}
+
 extern "C" int rlgpu_ppo_wave_infer(rlgpu_ppo* h, int32_t model) { return h && model >= 0 && model < 3 && wave_ok(h, model); }
 
 extern "C" int rlgpu_ppo_infer_actions_wave(rlgpu_ppo* h, const float* d_obs, const uint8_t* d_masks, int32_t n, int64_t row0,
