@@ -31,7 +31,8 @@ SHAPE_IDS = ["odd-bf16", "noln-bf16", "fp16", "c2-bf16"]
 
 
 def close_16bit(got, want):
-    """test_forward_bf16_close_to_fp32's bound."""
+    """test_forward_bf16_close_to_fp32's bound: a sanity bound on the distance, not the 16-bit contract, which
+    test_infer_reference_gpu.py pins (tests/infer_reference.py: this bound passes six of its nine wrong variants)."""
     scale = np.abs(want).max()
     err = np.abs(got - want).max()
     return err <= 2e-2 * scale + 1e-3, err, scale

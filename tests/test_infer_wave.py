@@ -28,13 +28,15 @@ def blank(n, gpu):
     return torch.full((n,), -1, dtype=torch.int32, device=gpu), torch.full((n,), float("nan"), device=gpu)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("temp", (1.0, 0.7))
-@pytest.mark.parametrize("model", sorted(MODELS))
-def test_wave_matches_fused_kernel(gpu, model, temp):
+def wave_vs_fused(gpu, model, temp, random_ln):
+    """random_ln: every LayerNorm weight and bias drawn by infer_reference.randomise_layer_norm instead of the initial
+    1 / 0 (the one-wave kernel reads them from the 16-bit parameter copy, the 8-wave kernel from its LDS copy)."""
     import torch
     from rlgpu.ppo import PPO
     p = PPO(max_rows=64, seed=5, policy_temperature=temp, **MODELS[model])
+    if random_ln:
+        from infer_reference import randomise_layer_norm
+        randomise_layer_norm(p, 77)
     assert p.wave_infer_ok(0) and p.wave_infer_ok(1)
     p.set_version(p.model_slice(0) * 0.5)
     for n in ROWS:
@@ -57,6 +59,20 @@ def test_wave_matches_fused_kernel(gpu, model, temp):
             a2, _ = p.infer_actions_wave(obs, masks, row0=38, step=11)
             w2, _ = p.infer_actions_rows(obs, masks, row0=38, step=11)
             assert torch.equal(a2, w2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("temp", (1.0, 0.7))
+@pytest.mark.parametrize("model", sorted(MODELS))
+def test_wave_matches_fused_kernel(gpu, model, temp):
+    wave_vs_fused(gpu, model, temp, random_ln=False)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("temp", (1.0, 0.7))
+def test_wave_matches_fused_kernel_random_layer_norm(gpu, temp):
+    """The same body with randomised LayerNorm parameters (the model that has a LayerNorm)."""
+    wave_vs_fused(gpu, "c2", temp, random_ln=True)
 
 
 @pytest.mark.gpu
